@@ -5,10 +5,12 @@ RCCL broadcast of the weights at start-up and gather of the refined label maps p
 
 A step = one pass of the hot path over one resident batch:
     encode initial masks -> network (fp32 MFMA) -> grouping / merge / scores -> per-instance masks.
-Prints ONE JSON line on rank 0: value = whole-job masks/s; `roofline` for the dominant kernel (the implicit-GEMM
-convolution, MFMA-bound) plus one `hbm_stages` entry per HBM-bound stage, all measured live with HIP events on the
-launch stream (quber_profile_begin/end); `cpu_baseline` = the oracle (pure-torch CPU restatement of the reference
-path) timed on this box's host cores over a bounded sample.
+Prints ONE JSON line on rank 0: value = whole-job masks/s, ms_per_step = wall time of one timed step.  A plain run does
+only that (set-up, --warmup steps, --steps timed steps, --dump-outputs, the line).  With --full the line also carries
+`roofline` for the dominant kernel (the implicit-GEMM convolution, MFMA-bound) plus one `hbm_stages` entry per HBM-bound
+stage, all measured live with HIP events on the launch stream (quber_profile_begin/end); `cpu_baseline` = the oracle
+(pure-torch CPU restatement of the reference path) timed on this box's host cores over a bounded sample; and the
+auxiliary records (predict_api, fp32_equivalent_bf16x3, configs).
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment launches the N ranks itself (child processes
 started BEFORE anything touches the GPU); under the driver's torchrun launch it just joins the group.  A world
@@ -86,6 +88,14 @@ def parse():
                          "with ProcessGroupNCCL / RCCL a one-GPU box allows; the auxiliary records are skipped")
     ap.add_argument("--dry", action="store_true",
                     help="no GPU work: exercise the launch / rendezvous / broadcast / gather path only (CPU tests, gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: stage profile and `roofline`, `cpu_baseline` (with the oracle "
+                         "parity check), `predict_api`, `fp32_equivalent_bf16x3`, `configs`, the synchronous gather alone.  Without it "
+                         "a run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line (`roofline` and "
+                         "`cpu_baseline` null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's frames) to DIR/<name>.npy, float32, "
+                         "< 64 MB in all (dump_outputs)")
     return ap.parse_args()
 
 
@@ -476,9 +486,11 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, logits, post, out_masks)
     # the gather alone, synchronous, nothing beside it: what a step would pay if it were NOT overlapped
     gather_alone_ms = None
-    if dist is not None and not a.no_gather:
+    if a.full and dist is not None and not a.no_gather:
         ts = []
         for _ in range(5):
             dist.barrier()
@@ -518,17 +530,17 @@ def main():
                            out_masks=out_masks, max_inst=max_inst), gpu_step)
         if host_io is not None:
             line["host_io"] = host_io
-        if not multi and a.predict_calls > 0 and a.dtype == "f32":
+        if a.full and not multi and a.predict_calls > 0 and a.dtype == "f32":
             line["predict_api"] = predict_api_run(a, sd, host, dev)
             if H == 480 and W == 640:        # the adapter resizes every frame to 640x480 (eval/refiner_model.py:246)
                 try:
                     line["predict_api"]["streamed"] = predict_stream_run(a, sd, host, dev)
                 except Exception as e:           # an auxiliary figure must never cost the line its headline
                     line["predict_api"]["streamed"] = {"error": repr(e)}
-        if a.dtype == "f32" and not multi and not a.no_split_mode:
+        if a.full and a.dtype == "f32" and not multi and not a.no_split_mode:
             line["fp32_equivalent_bf16x3"] = split_mode_run(a, make_engine, sd, gpu_step_args=(masks, bgr, depth, offsets, max_inst),
                                                             exact_logits=logits, exact_pan=post["panoptic"])
-        if (a.dtype == "f32" and not multi and not a.no_configs and not a.tuning and (B, H, W, N) == (16, 480, 640, 20)
+        if (a.full and a.dtype == "f32" and not multi and not a.no_configs and not a.tuning and (B, H, W, N) == (16, 480, 640, 20)
                 and a.heads == "loud" and not a.graph and not a.foreground_filter):
             eng.close()              # the headline engine's buffers are not needed any more
             line["configs"] = {}
@@ -849,6 +861,44 @@ def host_io_run(a, eng, host, offsets, logits, post, max_inst, dev):
                     "double-buffered copy streams; single GPU"}
 
 
+DUMP_SAMPLE = 1 << 21         # elements: an output larger than its limit below is dumped as a seeded sample of this many
+
+
+def dump_outputs(d, logits, post, out_masks):
+    """What a caller of the timed step receives from its last step, as float32 DIR/<name>.npy: the label maps and the instance
+    records of grouping (entries past each frame's `count` / `ncenters` are not outputs and are written as 0), and fixed seeded
+    samples of the logits and of the instance masks (masks of the instances past `count` as 0).  The inputs and weights are
+    seeded, so two builds run with the same arguments compare file by file.  At most 32 + 8 + 8 MB + the per-instance records."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    B, cap = post["labels"].shape
+    slot = torch.arange(cap, device=post["count"].device)[None, :]
+    live = slot < post["count"].long()[:, None]
+    live_c = slot < post["ncenters"].long()[:, None]
+    g = torch.Generator().manual_seed(0)
+
+    def sample(name, x, whole_max):
+        """x whole, or a seeded sample of it (name + "_sample") and the flat indices drawn"""
+        if x.numel() <= whole_max:
+            return name, x, None
+        idx = torch.randint(0, x.numel(), (DUMP_SAMPLE,), generator=g).to(x.device)
+        return name + "_sample", x.reshape(-1)[idx], idx
+
+    arrays = {"count": post["count"], "ncenters": post["ncenters"],
+              "labels": torch.where(live, post["labels"], 0.0), "scores": torch.where(live, post["scores"], 0.0),
+              "boxes": torch.where(live[..., None], post["boxes"], 0.0),
+              "centers": torch.where(live_c[..., None], post["centers"], torch.zeros_like(post["centers"]))}
+    for name, x, whole_max in (("panoptic", post["panoptic"], 1 << 23), ("logits", logits, DUMP_SAMPLE)):
+        name, x, _ = sample(name, x, whole_max)
+        arrays[name] = x
+    name, mk, idx = sample("masks", out_masks, DUMP_SAMPLE)
+    m_inst, hw = out_masks.shape[1], out_masks.shape[2] * out_masks.shape[3]
+    keep = live[:, :m_inst, None, None] if idx is None else live[:, :m_inst].reshape(-1)[idx // hw]
+    arrays[name] = mk.float() * keep
+    for name, x in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), x.float().cpu().numpy())
+
+
 def _rccl_version(torch):
     """RCCL's version as torch reports it (backend "nccl" IS RCCL on ROCm), or the reason it cannot."""
     try:
@@ -861,6 +911,37 @@ def _rccl_version(torch):
 def report(a, eng, world, elapsed, ranks, center_bias, sd, host, step_ms, t, gpu_step):
     import torch
     B, H, W, N = a.batch, a.height, a.width, a.instances
+    count = t["post"]["count"].cpu().numpy()
+    ms_per_step = elapsed / a.steps * 1e3
+    line = {
+        "metric": f"refined masks/sec on {W}x{H} RGB-D (N={N} inst)",
+        "value": world * B * N * a.steps / elapsed,
+        "unit": "refined masks/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step,
+        "step_ms_min_median_max_rank0": [float(np.min(step_ms)), float(np.median(step_ms)), float(np.max(step_ms))],
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": a.dtype, "data": "synthetic",
+        "config": {"workload": f"batch={B} {W}x{H} RGB-D, {N} initial instances/frame, ResNet-50 RGB-D refiner "
+                               f"(boundary-error -> fg/centre/offset), encode+network+grouping+mask extraction",
+                   "frames_per_step_per_gpu": B, "parallelism": f"dp{world}", "hipgraph": bool(ranks[0].get("hipgraph", a.graph)),
+                   "foreground_filter": bool(a.foreground_filter),
+                   "weights": ("seeded synthetic, loud predictors N(0, %.2f), centre bias %.4f calibrated for ~N peaks per frame"
+                               % (arch_sigma(), center_bias)) if a.heads == "loud"
+                              else "seeded synthetic, reference init (predictors N(0, 0.001): K = 0)",
+                   "instances_out_per_frame_mean": float(count.mean()),
+                   "instances_out_per_frame_min_max": [int(count.min()), int(count.max())]},
+        "rccl_ranks": ranks,
+        "gather": None if ranks[0].get("backend") is None else {
+            "ms_per_step_max_over_ranks": max(r["gather_ms_per_step"] for r in ranks),
+            "alone_ms_max_over_ranks": max((r["gather_alone_ms"] or 0.0) for r in ranks) if a.full else None,
+            "bytes_per_rank_per_step": B * H * W * 2, "wire_dtype": "int16 (labels -1, 1000 ... 1200; f32 again on rank 0)",
+            "note": "ms_per_step = host time inside the asynchronous gather's issue + wait calls per step (what the overlapped "
+                    "gather costs the step loop); alone = one synchronous gather with nothing beside it (what it would cost "
+                    "un-overlapped); per-rank values and step medians in rccl_ranks"},
+        "roofline": None, "cpu_baseline": None,
+    }
+    if not a.full:
+        return line
     # ---- stage profile: HIP events around every kernel of one step (+ the explicit error maps, a2), median of 3 ----
     runs = []
     for _ in range(3):
@@ -904,34 +985,8 @@ def report(a, eng, world, elapsed, ranks, center_bias, sd, host, step_ms, t, gpu
                 traffic_note = "profiles/conv_hbm_traffic.json was measured on other kernel sources (or another dtype): not reported"
         except Exception:
             traffic_note = "profiles/conv_hbm_traffic.json unreadable"
-    count = t["post"]["count"].cpu().numpy()
-    ms_per_step = elapsed / a.steps * 1e3
     ex_tf = executed / (fam_ms_pipe * 1e-3) / 1e12 if fam_ms_pipe else 0.0
-    line = {
-        "metric": f"refined masks/sec on {W}x{H} RGB-D (N={N} inst)",
-        "value": world * B * N * a.steps / elapsed,
-        "unit": "refined masks/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step,
-        "step_ms_min_median_max_rank0": [float(np.min(step_ms)), float(np.median(step_ms)), float(np.max(step_ms))],
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": a.dtype, "data": "synthetic",
-        "config": {"workload": f"batch={B} {W}x{H} RGB-D, {N} initial instances/frame, ResNet-50 RGB-D refiner "
-                               f"(boundary-error -> fg/centre/offset), encode+network+grouping+mask extraction",
-                   "frames_per_step_per_gpu": B, "parallelism": f"dp{world}", "hipgraph": bool(ranks[0].get("hipgraph", a.graph)),
-                   "foreground_filter": bool(a.foreground_filter),
-                   "weights": ("seeded synthetic, loud predictors N(0, %.2f), centre bias %.4f calibrated for ~N peaks per frame"
-                               % (arch_sigma(), center_bias)) if a.heads == "loud"
-                              else "seeded synthetic, reference init (predictors N(0, 0.001): K = 0)",
-                   "instances_out_per_frame_mean": float(count.mean()),
-                   "instances_out_per_frame_min_max": [int(count.min()), int(count.max())]},
-        "rccl_ranks": ranks,
-        "gather": None if ranks[0].get("backend") is None else {
-            "ms_per_step_max_over_ranks": max(r["gather_ms_per_step"] for r in ranks),
-            "alone_ms_max_over_ranks": max((r["gather_alone_ms"] or 0.0) for r in ranks),
-            "bytes_per_rank_per_step": B * H * W * 2, "wire_dtype": "int16 (labels -1, 1000 ... 1200; f32 again on rank 0)",
-            "note": "ms_per_step = host time inside the asynchronous gather's issue + wait calls per step (what the overlapped "
-                    "gather costs the step loop); alone = one synchronous gather with nothing beside it (what it would cost "
-                    "un-overlapped); per-rank values and step medians in rccl_ranks"},
+    line.update({
         "roofline": {"bound": "mfma", "achieved": ex_tf, "peak": peak, "unit": "TFLOP/s", "frac": ex_tf / peak,
                      # SURVEY 8(d)'s definition beside the conservative one above: the ALGORITHMIC FLOPs of the direct convolutions
                      # (2 x MAC) over the same time and peak - above `frac`, and possibly above 1, exactly by what Winograd does not multiply
@@ -967,7 +1022,7 @@ def report(a, eng, world, elapsed, ranks, center_bias, sd, host, step_ms, t, gpu
                      "hbm_note": "bytes = algorithmic (every operand of the stage read / written once), ms = HIP-event device time "
                                  "per step, frac = GB/s / 8000 (HBM3E spec; 6.3 TB/s is the measured copy ceiling)"},
         "stage_ms_other": {k: stages[k]["ms"] for k in stages if k not in CONV_FAMILY and k not in hbm},
-    }
+    })
     if world == 1 and a.cpu_frames > 0 and not a.rccl_selftest:
         bt = {"logits": t["logits"], "panoptic": t["post"]["panoptic"], "host": host}
         gpu_step()

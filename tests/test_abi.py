@@ -103,8 +103,8 @@ def test_param_specs_match_oracle_module_tree():
 
 def test_reference_config_zoo_fixture():
     """tests/golden/configs.json (oracle/gen_golden.py configs): what quber_amd/config.py makes of every refiner yaml the
-    reference ships.  Asserts (a) the counts the documentation quotes, (b) where the reference tree is present (the build
-    container) that the reader still derives exactly the stored result from the reference's own files, (c) that every distinct
+    reference ships.  Asserts (a) the counts the documentation quotes, (b) where the reference's configs/ directory is given
+    (QUBER_REFERENCE_CONFIGS) that the reader still derives exactly the stored result from the reference's own files, (c) that every distinct
     architecture the zoo asks for is one the parameter inventory AND the oracle network build, with identical state_dict keys."""
     import json
     import os
@@ -125,8 +125,9 @@ def test_reference_config_zoo_fixture():
     # whose HIERARCHY omits an enabled head, for which the reference raises KeyError at inference (model.py:701-708)
     why = sorted({v["unsupported"][:40] for v in zoo.values() if "unsupported" in v})
     assert len(why) == 2 and sum("unsupported" in v for v in zoo.values()) == 125, why
-    root = "/root/reference/configs"
-    if os.path.isdir(root):
+    root = os.environ.get("QUBER_REFERENCE_CONFIGS")
+    if root:
+        assert os.path.isdir(root), f"QUBER_REFERENCE_CONFIGS={root} is not a directory"
         for rel, want in zoo.items():
             path = os.path.join(root, rel)
             try:

@@ -7,7 +7,7 @@ cd $R
 # usage: tools/bench_lines.sh <tag> [traffic]: with "traffic", profiles/conv_hbm_traffic.json is first replaced by gpurun_out/<tag>_conv_hbm_traffic.json
 # (tools/profile_round.sh <tag> ran before), so that the default line carries roofline.traffic of the sources it runs on
 if [ "${2:-}" = traffic ] && [ -f $O/${TAG}_conv_hbm_traffic.json ]; then cp $O/${TAG}_conv_hbm_traffic.json $R/profiles/conv_hbm_traffic.json; fi
-run() { out=$1; shift; python3 bench.py "$@" 2> $O/${TAG}_$out.err | tail -1 > $O/${TAG}_$out.json; python3 - $O/${TAG}_$out.json <<'PY'
+run() { out=$1; shift; python3 bench.py --full "$@" 2> $O/${TAG}_$out.err | tail -1 > $O/${TAG}_$out.json; python3 - $O/${TAG}_$out.json <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1]))
 print(sys.argv[1].split("/")[-1], round(j["value"], 1), j["unit"], round(j["ms_per_step"], 2), "ms", "frac", round(j["roofline"]["frac"], 3))

@@ -7,7 +7,7 @@ cd $R
 for rep in $(seq $REPS); do
 for v in "$@"; do
   if [ $v = new ]; then unset QUBER_LIB; else export QUBER_LIB=$R/quber_amd/libquber_hip_$v.so; fi
-  python3 bench.py --steps 20 --warmup 5 --cpu-frames 0 --predict-calls 0 --no-split-mode --no-configs 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py --full --steps 20 --warmup 5 --cpu-frames 0 --predict-calls 0 --no-split-mode --no-configs 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read()); cs=j['roofline']['conv_stages']; hs=j.get('roofline',{})
 print('$rep $v', round(j['ms_per_step'],3), ' '.join('%s %.3f' % (k, v['ms']) for k, v in cs.items()))" | tee -a gpurun_out/${TAG}_stage_ab.txt

@@ -3,7 +3,7 @@
 # up to 160 channels: the default of option key 27), and with wider layers admitted (27=...), for the WF_SPLIT builds given.  usage (GPU box): tools/wino_fused_ab.sh "9 7"
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R
-B="python bench.py --steps 12 --warmup 4 --cpu-frames 0 --predict-calls 0 --no-split-mode"
+B="python bench.py --full --steps 12 --warmup 4 --cpu-frames 0 --predict-calls 0 --no-split-mode"
 for sp in ${1:-9}; do
   DL=$(tools/diag_build.sh wfsplit$sp WFX=-DWF_SPLIT=$sp) || exit 1      # scratch copy: the product library is never touched
   export QUBER_LIB=$DL
