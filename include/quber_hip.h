@@ -165,6 +165,24 @@ int quber_postprocess(quber_ctx* ctx, const float* dev_logits, int32_t n_planes,
 int quber_extract_masks(quber_ctx* ctx, const float* dev_panoptic, const float* dev_labels, int32_t batch,
                         int32_t max_inst, uint8_t* dev_masks, void* stream);
 
+/* horizontal-flip test-time augmentation: one forward of 2B frames, originals in slots [0, B), their W-mirrors in [B, 2B).
+ * The reference's driver builds MaskRefinerTTA for --refiner_model maskrefiner-tta (eval/un_eval_utils.py:78-81) but never
+ * defines it; SemanticSegmentorWithTTA (maskrefiner/test_time_augmentation.py:72-95) runs the original and the flipped input,
+ * flips the second sem_seg back and averages, and model.py:304-307 keeps a hook that hands centre and offset to that caller.
+ *
+ * Mirrors frames [0, batch) of each input into [batch, 2 * batch), in place; the caller fills the first half.
+ *   dev_bgr u8 [2B][H][W][3], dev_depth u8 [2B][H][W][3] or null, dev_masks u8 [2B][n][H][W] (unused when n == 0).
+ * The mirrored frame's initial-mask encoding is quber_encode_initial_masks on all 2B frames afterwards: a1 of the mirrored
+ * masks, as predict() computes it for a mirrored frame (maskrefiner/predictor.py:304-348) - not a mirror of the
+ * originals' offsets, which is not bit-equal. */
+int quber_tta_flip_inputs(quber_ctx* ctx, uint8_t* dev_bgr, uint8_t* dev_depth, uint8_t* dev_masks, int32_t batch,
+                          int32_t n_masks, void* stream);
+/* The merge of the 2B full-resolution logits of quber_forward, plane by plane, in fp32:
+ *   out[b][c][y][x] = (L[b][c][y][x] + s_c * L[B+b][c][y][W-1-x]) * 0.5f,  s_c = -1 for plane 3 (off_x), +1 otherwise
+ *   dev_logits2 f32 [2B][n_planes][H][W] -> dev_out f32 [B][n_planes][H][W]; quber_postprocess then runs on dev_out. */
+int quber_tta_merge(quber_ctx* ctx, const float* dev_logits2, int32_t n_planes, int32_t batch, float* dev_out,
+                    void* stream);
+
 /* evaluation support - all pairwise overlap counts of two label maps in one pass.  Replaces the per-pair
  * np.count_nonzero loops of eval/evaluation.py:180-199 (multilabel_metrics).
  *   dev_pred, dev_gt i32 [n_pixels], label values in 0..65535, at most `cap` (<= 1024) distinct values per map

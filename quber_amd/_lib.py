@@ -56,6 +56,8 @@ SIGNATURES = {
                                       C.POINTER(C.c_double), C.POINTER(_I)]),
     "quber_postprocess": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "quber_extract_masks": (C.c_int, [_P, _P, _P, _I, _I, _P, _P]),
+    "quber_tta_flip_inputs": (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
+    "quber_tta_merge": (C.c_int, [_P, _P, _I, _I, _P, _P]),
     "quber_contingency_workspace_bytes": (C.c_int64, [_I]),
     "quber_label_contingency": (C.c_int, [_P, _P, C.c_int64, _I, _P, _P]),
     "quber_boundary_workspace_bytes": (C.c_int64, [_I, _I, _I]),

@@ -289,6 +289,10 @@ int launch_postprocess(const float* logits, int nch, int B, int H, int W, const 
 size_t postprocess_ws_bytes(int B, int H, int W, int cap);
 int launch_extract_masks(const float* pan, const float* labels, int B, int H, int W, int cap, int max_inst,
                          uint8_t* out, hipStream_t st);
+// horizontal-flip test-time augmentation (tta.hip): the W-mirror of `planes` u8 [H][W][C] planes (C = 1 or 3) into dst; the merge of
+// the 2B logits [2B][planes][H][W] of (originals, mirrored frames) into [B][planes][H][W]
+int launch_tta_flip_u8(const uint8_t* src, uint8_t* dst, long planes, int H, int W, int C, hipStream_t st);
+int launch_tta_merge(const float* logits2, int planes, int B, int H, int W, float* out, hipStream_t st);
 int launch_group_pixels(const float* logits, int nch, int B, int H, int W, int cap, const int* centers, const int* ncenters,
                         uint8_t* idmap, unsigned* area, hipStream_t st);
 

@@ -1694,6 +1694,33 @@ int quber_extract_masks(quber_ctx* c, const float* pan, const float* labels, int
                                 (hipStream_t)stream);
 }
 
+// 2 * batch frames on the engine: originals in [0, batch), their mirrors in [batch, 2 * batch)
+static int check_tta_batch(quber_ctx* c, int batch) {
+    if (!c) return fail("null context");
+    if (batch < 1 || 2L * batch > c->cfg.max_batch) return fail("test-time augmentation: 2 * batch outside 2..max_batch");
+    return 0;
+}
+
+int quber_tta_flip_inputs(quber_ctx* c, uint8_t* bgr, uint8_t* depth, uint8_t* masks, int32_t batch, int32_t n, void* stream) {
+    if (check_tta_batch(c, batch)) return -1;
+    if (n < 0 || n > c->cfg.max_instances) return fail("initial masks outside 0..max_instances");
+    if (!bgr || (!masks && n > 0)) return fail("null tensor");
+    const int H = c->cfg.height, W = c->cfg.width;
+    const long hw = (long)H * W;
+    hipStream_t st = (hipStream_t)stream;
+    if (launch_tta_flip_u8(bgr, bgr + batch * hw * 3, batch, H, W, 3, st)) return -1;
+    if (depth && launch_tta_flip_u8(depth, depth + batch * hw * 3, batch, H, W, 3, st)) return -1;
+    if (n > 0 && launch_tta_flip_u8(masks, masks + (long)batch * n * hw, (long)batch * n, H, W, 1, st)) return -1;
+    return 0;
+}
+
+int quber_tta_merge(quber_ctx* c, const float* logits2, int32_t n_planes, int32_t batch, float* out, void* stream) {
+    if (check_tta_batch(c, batch)) return -1;
+    if (n_planes < 4) return fail("test-time augmentation: fewer than 4 logit planes");
+    if (!logits2 || !out) return fail("null tensor");
+    return launch_tta_merge(logits2, n_planes, batch, c->cfg.height, c->cfg.width, out, (hipStream_t)stream);
+}
+
 int64_t quber_contingency_workspace_bytes(int32_t cap) { return (int64_t)contingency_ws_bytes(cap); }
 
 int quber_label_contingency(const int32_t* pred, const int32_t* gt, int64_t n_pixels, int32_t cap, void* workspace,

@@ -306,6 +306,34 @@ class Engine:
             _ptr(o["scores"]), _ptr(o["boxes"]), _ptr(o["centers"]), _ptr(o["ncenters"]), _stream()))
         return o
 
+    # ---- horizontal-flip test-time augmentation: one forward of 2B frames, mirrors in slots [B, 2B) ----
+    def tta_flip_inputs(self, bgr, depth, masks):
+        """bgr (and depth, or None) u8 [2B,H,W,3], masks u8 [2B,N,H,W] or None (device): frames [0,B) are the caller's; their
+        W-mirrors are written into [B,2B) in place.  encode() on all 2B frames afterwards gives the mirrored frames' a1."""
+        B2 = bgr.shape[0]
+        assert B2 % 2 == 0, "the test-time-augmentation buffers hold 2B frames"
+        assert bgr.dtype == torch.uint8 and bgr.is_contiguous() and bgr.shape == (B2, self.H, self.W, 3)
+        if depth is not None:
+            assert depth.dtype == torch.uint8 and depth.is_contiguous() and depth.shape == bgr.shape
+        n = 0
+        if masks is not None:
+            assert masks.dtype == torch.uint8 and masks.is_contiguous() and masks.shape[0] == B2 and masks.shape[2:] == (self.H, self.W)
+            n = masks.shape[1]
+        _lib.check(self.lib.quber_tta_flip_inputs(self.h, _ptr(bgr), _ptr(depth), _ptr(masks if n else None), B2 // 2, n,
+                                                  _stream()))
+
+    def tta_merge(self, logits, out=None):
+        """logits f32 [2B,planes,H,W] of (originals, mirrors) -> f32 [B,planes,H,W]:
+        (L[b] + s * mirror_W(L[B+b])) * 0.5, s = -1 on plane 3 (off_x), +1 elsewhere."""
+        B2, planes = logits.shape[:2]
+        assert B2 % 2 == 0, "the test-time-augmentation logits hold 2B frames"
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape[2:] == (self.H, self.W)
+        if out is None:
+            out = torch.empty((B2 // 2, planes, self.H, self.W), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B2 // 2, planes, self.H, self.W)
+        _lib.check(self.lib.quber_tta_merge(self.h, _ptr(logits), planes, B2 // 2, _ptr(out), _stream()))
+        return out
+
     def extract_masks(self, post, max_inst, out=None):
         B = post["panoptic"].shape[0]
         if out is None:

@@ -21,6 +21,10 @@ unpinned, own tolerance - OpenCV is not in the image) on the calling thread, as 
 csrc/inpaint_dev.hip, which marches the independent hole regions one wave each and equals the host function bit for bit
 (tests/test_gpu_inpaint.py).  ``MaskRefiner(inpaint=False)`` skips it.
 cv2 / imageio are absent from the image, so files are read with PIL.
+
+``MaskRefinerTTA`` is the refiner the reference's driver builds for ``--refiner_model maskrefiner-tta``
+(eval/un_eval_utils.py:78-81) and never defines: ``MaskRefiner`` with horizontal-flip test-time augmentation (``tta=True``; the
+definition is in INTEGRATION.md).
 """
 import time
 
@@ -73,8 +77,9 @@ def resize_shortest_edge_shape(oldh, oldw, short_edge_length=800, max_size=1333)
 
 class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
-                 lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host"):
-        self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device)
+                 lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False):
+        # tta: every frame and its W-mirror in one forward, logits merged on the device (MaskRefinerPredictor(tta=True))
+        self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, tta=tta)
         self.dataset = dataset
         self.lmffnet = None
         # "host" / True (default): csrc/inpaint.hip on the calling (worker) thread; "device": csrc/inpaint_dev.hip, bit-equal, for hosts
@@ -214,14 +219,24 @@ class MaskRefiner:
             H_, W_ = frs[0]["d_rgb"].shape[:2]
             for f in frs:
                 torch.cuda.current_stream().wait_event(f["ready"])
-            d_masks = torch.zeros((len(frs), n, H_, W_), dtype=torch.uint8, device=dev)
+            two = self.refiner_predictor.depth_on and self.refiner_predictor.rgb_on
+            B_ = len(frs)
+            if model.tta:
+                # test-time augmentation: the frames go straight into the first halves of 2B-frame buffers (the flip fills the rest)
+                d_rgb, d_depth, d_masks = model.tta_alloc(B_, H_, W_, n, two)
+                d_masks[:B_].zero_()
+            else:
+                d_masks = torch.zeros((B_, n, H_, W_), dtype=torch.uint8, device=dev)
             for b, f in enumerate(frs):
                 if f["d_masks"].shape[0]:
                     d_masks[b, :f["d_masks"].shape[0]] = f["d_masks"]
-            d_rgb = torch.stack([f["d_rgb"] for f in frs])
-            two = self.refiner_predictor.depth_on and self.refiner_predictor.rgb_on
-            if not self.refiner_predictor.rgb_on:                 # depth-only: the image IS the depth map (predictor.py:296-298)
-                d_rgb = torch.stack([f["d_depth"] for f in frs])
+            img = [f["d_rgb"] if self.refiner_predictor.rgb_on else f["d_depth"] for f in frs]   # depth-only: the image IS the depth map
+            if model.tta:
+                torch.stack(img, out=d_rgb[:B_])
+                if two:
+                    torch.stack([f["d_depth"] for f in frs], out=d_depth[:B_])
+                return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, halves=True)
+            d_rgb = torch.stack(img)
             d_depth = torch.stack([f["d_depth"] for f in frs]) if two else None
             return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k)
 
@@ -268,3 +283,11 @@ class MaskRefiner:
                 pending = (group, hd)
             if pending is not None:
                 yield from collect(*pending)
+
+
+class MaskRefinerTTA(MaskRefiner):
+    """``MaskRefinerTTA(config_file, weights_file=..., dataset=...)`` of eval/un_eval_utils.py:79-81: MaskRefiner with horizontal-flip
+    test-time augmentation.  predict() and predict_stream(batch=k) work as on MaskRefiner; the engine runs 2k frames."""
+
+    def __init__(self, config_file=None, weights_file=None, dataset="OSD", **kw):
+        super().__init__(config_file, weights_file=weights_file, dataset=dataset, tta=True, **kw)

@@ -8,7 +8,10 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
   * none of the reference constructor's side effects (dataset loader, output dir, hard-coded
     weights path: predictor.py:226-243);
   * the initial-mask encoding, network and grouping all run on the GPU; ``predict_batch`` exposes the
-    batched form the reference lacks (it always runs batch 1, predictor.py:358).
+    batched form the reference lacks (it always runs batch 1, predictor.py:358);
+  * ``tta=True``: horizontal-flip test-time augmentation, which the reference's driver asks for (eval/un_eval_utils.py:78-81)
+    but never defines - every frame and its W-mirror run as one forward of 2B frames, the logits are merged on the device
+    (flip back, x-offset negated, averaged: INTEGRATION.md) and post-processing runs on the merged maps.
 There is no CPU fallback: construction fails if the HIP library or a GPU is missing.
 """
 import os
@@ -36,16 +39,18 @@ def load_checkpoint(path):
 class _FrameStaging:
     """Buffers of the batch-1 call path for one frame size, allocated once: ONE pinned host block and ONE device block for the
     frame's inputs (bgr | depth | initial masks, uploaded in a few pipelined pieces), the device-side intermediates, and pinned
-    word for the instance count."""
+    word for the instance count.  frames = 2 (test-time augmentation): the device block holds every input for two frames - the
+    uploaded frame in slot 0, its mirror in slot 1 (bgr [2,H,W,3] | depth [2,H,W,3] | masks [2,N,H,W]); the host block one."""
 
-    def __init__(self, eng, n_cap):
+    def __init__(self, eng, n_cap, frames=1):
         H, W, dev = eng.H, eng.W, eng.device
         hw = H * W
         self.n_cap = n_cap
+        self.frames = frames
         self.pin_in = torch.empty(6 * hw + n_cap * hw, dtype=torch.uint8).pin_memory()
         self.np_in = self.pin_in.numpy()
-        self.dev_in = torch.empty(self.pin_in.shape, dtype=torch.uint8, device=dev)
-        self.offsets = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev)
+        self.dev_in = torch.empty(frames * (6 * hw + n_cap * hw), dtype=torch.uint8, device=dev)
+        self.offsets = torch.empty((frames, 3, H, W), dtype=torch.float32, device=dev)
         self.post = eng.alloc_post(1)
         self.pin_count = torch.empty((1,), dtype=torch.int32).pin_memory()
         self.done = torch.cuda.Event()
@@ -55,10 +60,11 @@ class RefinerModel:
     """The ``predictor.model`` object: ``model(list[dict]) -> list[dict]`` in the detectron2 convention
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
-    def __init__(self, cfg, state_dict, device):
+    def __init__(self, cfg, state_dict, device, tta=False):
         self.cfg = cfg
         self.state_dict = state_dict
         self.device = torch.device(device)
+        self.tta = bool(tta)      # horizontal-flip test-time augmentation in predict_one / enqueue_batch: engines of capacity 2B
         self._engines = {}
         self._retired = {}        # (H, W) -> the engine a larger one replaced last; see engine_for
         self._staging = {}
@@ -92,8 +98,9 @@ class RefinerModel:
     def staging_for(self, eng, n_masks):
         key = (eng.H, eng.W)
         stg = self._staging.get(key)
-        if stg is None or stg.n_cap < n_masks:
-            stg = _FrameStaging(eng, max(64, n_masks))
+        frames = 2 if self.tta else 1
+        if stg is None or stg.n_cap < n_masks or stg.frames != frames:
+            stg = _FrameStaging(eng, max(64, n_masks), frames)
             self._staging[key] = stg
         return stg
 
@@ -104,6 +111,38 @@ class RefinerModel:
         logits = eng.forward(bgr, depth, offsets)
         post = eng.postprocess(logits)
         return eng, logits, post
+
+    # -- horizontal-flip test-time augmentation --
+    def tta_alloc(self, B, H, W, n, depth=True):
+        """Empty 2B-frame device buffers (bgr, depth or None, masks [2B,n,H,W]): the caller fills frames [0, B) directly, the flip
+        kernel fills [B, 2B)."""
+        dev = self.device
+        bgr = torch.empty((2 * B, H, W, 3), dtype=torch.uint8, device=dev)
+        return bgr, torch.empty_like(bgr) if depth else None, torch.empty((2 * B, n, H, W), dtype=torch.uint8, device=dev)
+
+    def tta_buffers(self, d_bgr, d_depth, d_masks):
+        """2B-frame buffers holding copies of B frames that are already on the device in B-frame tensors (enqueue_batch called without
+        `halves`); callers that can fill the first halves directly use tta_alloc instead."""
+        B, H, W = d_bgr.shape[:3]
+        bufs = self.tta_alloc(B, H, W, d_masks.shape[1], d_depth is not None)
+        for buf, t in zip(bufs, (d_bgr, d_depth, d_masks)):
+            if t is not None:
+                buf[:B].copy_(t)
+        return bufs
+
+    def tta_logits(self, eng, bgr2, depth2, masks2, offsets=None):
+        """The augmented forward on 2B-frame buffers whose first halves hold the frames, all on the current stream: mirror the
+        inputs into the second halves, a1 on all 2B frames (the mirrored frames' own encoding), one forward of 2B frames, merge
+        -> logits f32 [B,planes,H,W] of the B frames.  `offsets`: an optional [2B,3,H,W] buffer for a1."""
+        n = 0 if masks2 is None else masks2.shape[1]
+        eng.tta_flip_inputs(bgr2, depth2, masks2 if n else None)
+        if n:
+            offsets = eng.encode(masks2, offsets)
+        elif offsets is None:
+            offsets = torch.zeros((bgr2.shape[0], 3, eng.H, eng.W), dtype=torch.float32, device=self.device)
+        else:
+            offsets.zero_()
+        return eng.tta_merge(eng.forward(bgr2, depth2, offsets))
 
     def frame_dict(self, eng, logits_b, post, b, k, masks_b):
         """The reference's output dict of one frame (model.py:304-356) from the device-side results."""
@@ -140,7 +179,8 @@ class RefinerModel:
         a pinned word and exactly `count` masks are extracted."""
         H, W = bgr.shape[:2]
         n = int(masks.shape[0])
-        eng = self.engine_for(H, W, 1, n)
+        f = 2 if self.tta else 1                     # frames on the device: the frame [and its mirror]
+        eng = self.engine_for(H, W, f, n)
         stg = self.staging_for(eng, n)
         hw = H * W
         two = depth is not None
@@ -148,10 +188,16 @@ class RefinerModel:
         # host copy into the pinned block and H2D, pipelined: the images first, then the masks in a few pieces - the DMA of a
         # piece runs while the host copies the next one (8 MB at N = 20: 0.3 ms of memcpy + 0.3 ms of PCIe, overlapped)
         o = (6 if two else 3) * hw
+        od, om = 3 * f * hw, (6 if two else 3) * f * hw          # device offsets of depth and masks (f = 1: the host layout)
         np.copyto(stg.np_in[:3 * hw].reshape(H, W, 3), bgr, casting="unsafe")
         if two:
             np.copyto(stg.np_in[3 * hw:6 * hw].reshape(H, W, 3), depth, casting="unsafe")
-        stg.dev_in[:o].copy_(stg.pin_in[:o], non_blocking=True)
+        if f == 1:
+            stg.dev_in[:o].copy_(stg.pin_in[:o], non_blocking=True)
+        else:
+            stg.dev_in[:3 * hw].copy_(stg.pin_in[:3 * hw], non_blocking=True)
+            if two:
+                stg.dev_in[od:od + 3 * hw].copy_(stg.pin_in[3 * hw:6 * hw], non_blocking=True)
         if n:
             # the encoder tests the mask bytes for non-zero (csrc/encode.hip), so uint8 / bool masks upload as they are
             src = masks.view(np.uint8) if masks.dtype == np.bool_ else masks
@@ -159,15 +205,19 @@ class RefinerModel:
             for a in range(0, n, step):
                 b = min(n, a + step)
                 np.copyto(stg.np_in[o + a * hw:o + b * hw].reshape(b - a, H, W), src[a:b], casting="unsafe")
-                stg.dev_in[o + a * hw:o + b * hw].copy_(stg.pin_in[o + a * hw:o + b * hw], non_blocking=True)
+                stg.dev_in[om + a * hw:om + b * hw].copy_(stg.pin_in[o + a * hw:o + b * hw], non_blocking=True)
         stg.done.record()
-        d_bgr = stg.dev_in[:3 * hw].view(1, H, W, 3)
-        d_dep = stg.dev_in[3 * hw:6 * hw].view(1, H, W, 3) if two else None
-        if n:
-            eng.encode(stg.dev_in[o:o + n * hw].view(1, n, H, W), stg.offsets)
+        d_bgr = stg.dev_in[:3 * f * hw].view(f, H, W, 3)
+        d_dep = stg.dev_in[od:od + 3 * f * hw].view(f, H, W, 3) if two else None
+        d_masks = stg.dev_in[om:om + f * n * hw].view(f, n, H, W)
+        if f == 2:
+            logits = self.tta_logits(eng, d_bgr, d_dep, d_masks, stg.offsets)     # merged: owned by the caller through the dict
         else:
-            stg.offsets.zero_()
-        logits = eng.forward(d_bgr, d_dep, stg.offsets)            # fresh tensor: owned by the caller through the dict
+            if n:
+                eng.encode(d_masks, stg.offsets)
+            else:
+                stg.offsets.zero_()
+            logits = eng.forward(d_bgr, d_dep, stg.offsets)        # fresh tensor: owned by the caller through the dict
         post = eng.postprocess(logits, stg.post)
         stg.pin_count.copy_(post["count"], non_blocking=True)
         torch.cuda.current_stream().synchronize()
@@ -182,19 +232,27 @@ class RefinerModel:
         return self.frame_dict(eng, logits[0], post_out, 0, k, masks_b)
 
     # -- batched form on device-resident frames, split into "enqueue" and "collect" so that a caller can keep one batch in flight --
-    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0):
+    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False):
         """d_bgr / d_depth: u8 [B,H,W,3] (depth None for single-stream configs), d_masks: u8 [B,N,H,W] on the device.  Enqueues a1 ...
         a11 and the extraction of the first `slots` instance masks of every frame on the current stream WITHOUT synchronising;
-        returns a handle for collect_batch()."""
+        returns a handle for collect_batch().  halves=True (test-time augmentation only): the tensors are 2B-frame buffers
+        (tta_alloc) whose first halves hold the B frames."""
+        if halves:
+            assert self.tta and d_bgr.shape[0] % 2 == 0
         B, H, W = d_bgr.shape[:3]
-        eng = self.engine_for(H, W, max(B, capacity), d_masks.shape[1])      # (`capacity`: the caller's batch size - a short last batch must not rebuild)
+        B = B // 2 if halves else B
+        f = 2 if self.tta else 1                     # test-time augmentation: the engine runs the B frames and their mirrors
+        eng = self.engine_for(H, W, f * max(B, capacity), d_masks.shape[1])      # (`capacity`: the caller's batch size - a short last batch must not rebuild)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        if d_masks.shape[1]:
-            offsets = eng.encode(d_masks)
+        if self.tta:
+            logits = self.tta_logits(eng, *((d_bgr, d_depth, d_masks) if halves else self.tta_buffers(d_bgr, d_depth, d_masks)))
         else:
-            offsets = torch.zeros((B, 3, H, W), dtype=torch.float32, device=self.device)
-        logits = eng.forward(d_bgr, d_depth, offsets)
+            if d_masks.shape[1]:
+                offsets = eng.encode(d_masks)
+            else:
+                offsets = torch.zeros((B, 3, H, W), dtype=torch.float32, device=self.device)
+            logits = eng.forward(d_bgr, d_depth, offsets)
         post = eng.postprocess(logits)
         slots = min(max(1, slots), eng.cap)
         masks = eng.extract_masks(post, slots)
@@ -285,7 +343,7 @@ class RefinerModel:
 
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
-                 seed=0, state_dict=None):
+                 seed=0, state_dict=None, tta=False):
         if config_file is None:
             self.cfg = qconfig.canonical_cfg()
         else:
@@ -310,7 +368,8 @@ class MaskRefinerPredictor:
                 warnings.warn(f"weights '{weights_file}' not found; using seeded synthetic weights")
             sd = arch.init_state_dict(seed=seed, **kw)
         self.cfg.MODEL.WEIGHTS = path or "<synthetic seed %d>" % seed
-        self.model = RefinerModel(self.cfg, sd, device)
+        self.tta = bool(tta)          # horizontal-flip test-time augmentation in predict() / predict_batch()
+        self.model = RefinerModel(self.cfg, sd, device, tta=self.tta)
         self.device = torch.device(device)
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
@@ -342,11 +401,19 @@ class MaskRefinerPredictor:
             if len(m):
                 mk[b, :len(m)] = np.asarray(m) != 0
         dev = self.device
-        eng = self.model.engine_for(H, W, B, n)
-        d_masks = torch.from_numpy(mk).to(dev)
-        bgr = torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)).to(dev)
-        depth = None if depth_imgs is None else torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)).to(dev)
-        offsets = eng.encode(d_masks)
-        logits = eng.forward(bgr, depth, offsets)
+        eng = self.model.engine_for(H, W, 2 * B if self.tta else B, n)
+        if self.tta:                                      # uploaded straight into the first halves of the 2B-frame buffers
+            bgr, depth, d_masks = self.model.tta_alloc(B, H, W, n, depth_imgs is not None)
+            bgr[:B].copy_(torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)))
+            if depth is not None:
+                depth[:B].copy_(torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)))
+            d_masks[:B].copy_(torch.from_numpy(mk))
+            logits = self.model.tta_logits(eng, bgr, depth, d_masks)
+        else:
+            d_masks = torch.from_numpy(mk).to(dev)
+            bgr = torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)).to(dev)
+            depth = None if depth_imgs is None else torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)).to(dev)
+            offsets = eng.encode(d_masks)
+            logits = eng.forward(bgr, depth, offsets)
         post = eng.postprocess(logits)
         return self.model.results(eng, logits, post)
