@@ -183,6 +183,41 @@ int quber_tta_flip_inputs(quber_ctx* ctx, uint8_t* dev_bgr, uint8_t* dev_depth, 
 int quber_tta_merge(quber_ctx* ctx, const float* dev_logits2, int32_t n_planes, int32_t batch, float* dev_out,
                     void* stream);
 
+/* The predicted error maps (the eee_boundary / eee_mask planes of quber_forward, plane order as at QUBER_LOGIT_BASE), decoded,
+ * attributed and scored without leaving the device (csrc/errhead.hip).  All four work on a context created with with_network = 0;
+ * every output is overwritten (the call clears what it accumulates into, on `stream`).
+ *
+ * Per-pixel class of one head.  Replaces the `argmax` of eval/eval_utils.py:308-328 and explicit_error_estimation/util.py:29-31;
+ * exactly torch.argmax(logits[:, first_plane : first_plane + classes], dim=1): the first index wins ties, a NaN is the maximum.
+ *   dev_logits f32 [B][n_planes][H][W], classes 2..4, n_planes >= first_plane + classes
+ *   -> dev_classes u8 [B][H][W]; dev_hist u32 [B][classes] pixels per class (may be NULL).  Any H, W and alignment. */
+int quber_error_decode(quber_ctx* ctx, const float* dev_logits, int32_t n_planes, int32_t first_plane, int32_t classes,
+                       int32_t batch, uint8_t* dev_classes, uint32_t* dev_hist, void* stream);
+/* Which initial masks carry which predicted class (no reference counterpart: the reference only paints the classes,
+ * eval_utils.py:308-328; with the boundary head of an e3 model FP / (TP + FP) of a row is the share of the mask's own boundary
+ * band the network rejects).
+ *   dev_classes u8 [B][H][W], dev_masks u8 [B][n_masks][H][W] (non-zero = inside), n_masks 0..max_instances (0: no-op)
+ *   -> dev_out u32 [B][n_masks][classes]: pixels of mask n with class c; overlapping masks each count their own pixels; a class
+ *      value >= classes is counted nowhere */
+int quber_error_mask_hist(quber_ctx* ctx, const uint8_t* dev_classes, const uint8_t* dev_masks, int32_t batch, int32_t n_masks,
+                          int32_t classes, uint32_t* dev_out, void* stream);
+/* Confusion table of a class map against the explicit maps.  Replaces compute_metrics' get_stats inputs
+ * (explicit_error_estimation/util.py:29-54); the target class is the training target of
+ * maskrefiner/modeling/mask_refiner/model.py:185-227.
+ *   dev_explicit u8 [B][2][4][H][W]: the output of quber_explicit_error_maps; kind 0 = region (eee_mask), 1 = boundary (eee_boundary)
+ *   error_type 0 = e3 (TP,TN,FP,FN -> 0,1,2,3), 1 = e2 (TP|TN -> 0, FP|FN -> 1), 2 = e33 (TP|TN -> 0, FP -> 1, FN -> 2),
+ *              3 = e32 (FP -> 0, FN -> 1, TP / TN: no target); classes must be 4, 2, 3, 2 respectively
+ *   -> dev_table u64 [B][classes + 1][classes]: row = target class (row `classes`: pixels without one), column = predicted class.
+ *      Every frame's table sums to H * W provided every byte of dev_classes is < classes: a larger value is a caller error, such a
+ *      pixel is counted nowhere (nothing is read or written out of bounds). */
+int quber_error_score(quber_ctx* ctx, const uint8_t* dev_classes, const uint8_t* dev_explicit, int32_t kind, int32_t error_type,
+                      int32_t classes, int32_t batch, uint64_t* dev_table, void* stream);
+/* The picture of eval/eval_utils.py:308-328: class colours painted over the image.
+ *   dev_bgr u8 [B][H][W][3], dev_classes u8 [B][H][W]; colorN: bits 0-7 B, 8-15 G, 16-23 R, bit 24 = paint class N
+ *   -> dev_out u8 [B][H][W][3] (may be dev_bgr itself): the colour where the pixel's class has bit 24 set, the input elsewhere */
+int quber_error_overlay(quber_ctx* ctx, const uint8_t* dev_bgr, const uint8_t* dev_classes, int32_t batch, uint32_t color0,
+                        uint32_t color1, uint32_t color2, uint32_t color3, uint8_t* dev_out, void* stream);
+
 /* evaluation support - all pairwise overlap counts of two label maps in one pass.  Replaces the per-pair
  * np.count_nonzero loops of eval/evaluation.py:180-199 (multilabel_metrics).
  *   dev_pred, dev_gt i32 [n_pixels], label values in 0..65535, at most `cap` (<= 1024) distinct values per map

@@ -58,6 +58,10 @@ SIGNATURES = {
     "quber_extract_masks": (C.c_int, [_P, _P, _P, _I, _I, _P, _P]),
     "quber_tta_flip_inputs": (C.c_int, [_P, _P, _P, _P, _I, _I, _P]),
     "quber_tta_merge": (C.c_int, [_P, _P, _I, _I, _P, _P]),
+    "quber_error_decode": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "quber_error_mask_hist": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "quber_error_score": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "quber_error_overlay": (C.c_int, [_P, _P, _P, _I, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
     "quber_contingency_workspace_bytes": (C.c_int64, [_I]),
     "quber_label_contingency": (C.c_int, [_P, _P, C.c_int64, _I, _P, _P]),
     "quber_boundary_workspace_bytes": (C.c_int64, [_I, _I, _I]),

@@ -293,6 +293,16 @@ int launch_extract_masks(const float* pan, const float* labels, int B, int H, in
 // the 2B logits [2B][planes][H][W] of (originals, mirrored frames) into [B][planes][H][W]
 int launch_tta_flip_u8(const uint8_t* src, uint8_t* dst, long planes, int H, int W, int C, hipStream_t st);
 int launch_tta_merge(const float* logits2, int planes, int B, int H, int W, float* out, hipStream_t st);
+// the predicted error maps (errhead.hip): argmax class map + histogram, per-mask class counts, confusion table against the explicit
+// maps, colour overlay
+int launch_error_decode(const float* logits, int n_planes, int first_plane, int classes, int B, int H, int W, uint8_t* cls,
+                        unsigned* hist, hipStream_t st);
+int launch_error_mask_hist(const uint8_t* cls, const uint8_t* masks, int B, int N, int classes, int H, int W, unsigned* out,
+                           hipStream_t st);
+int launch_error_score(const uint8_t* cls, const uint8_t* expl, int kind, int error_type, int classes, int B, int H, int W,
+                       unsigned long long* table, hipStream_t st);
+int launch_error_overlay(const uint8_t* bgr, const uint8_t* cls, int B, int H, int W, const unsigned* colors, uint8_t* out,
+                         hipStream_t st);
 int launch_group_pixels(const float* logits, int nch, int B, int H, int W, int cap, const int* centers, const int* ncenters,
                         uint8_t* idmap, unsigned* area, hipStream_t st);
 

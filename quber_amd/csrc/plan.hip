@@ -1721,6 +1721,40 @@ int quber_tta_merge(quber_ctx* c, const float* logits2, int32_t n_planes, int32_
     return launch_tta_merge(logits2, n_planes, batch, c->cfg.height, c->cfg.width, out, (hipStream_t)stream);
 }
 
+// ---- the predicted error maps (errhead.hip); usable on a context without a network ----
+int quber_error_decode(quber_ctx* c, const float* logits, int32_t n_planes, int32_t first_plane, int32_t classes, int32_t batch,
+                       uint8_t* classes_out, uint32_t* hist, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (!logits || !classes_out) return fail("null tensor");
+    return launch_error_decode(logits, n_planes, first_plane, classes, batch, c->cfg.height, c->cfg.width, classes_out, hist,
+                               (hipStream_t)stream);
+}
+
+int quber_error_mask_hist(quber_ctx* c, const uint8_t* classes_map, const uint8_t* masks, int32_t batch, int32_t n, int32_t classes,
+                          uint32_t* out, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n < 0 || n > c->cfg.max_instances) return fail("initial masks outside 0..max_instances");
+    if (n == 0) return 0;
+    if (!classes_map || !masks || !out) return fail("null tensor");
+    return launch_error_mask_hist(classes_map, masks, batch, n, classes, c->cfg.height, c->cfg.width, out, (hipStream_t)stream);
+}
+
+int quber_error_score(quber_ctx* c, const uint8_t* classes_map, const uint8_t* explicit_maps, int32_t kind, int32_t error_type,
+                      int32_t classes, int32_t batch, uint64_t* table, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (!classes_map || !explicit_maps || !table) return fail("null tensor");
+    return launch_error_score(classes_map, explicit_maps, kind, error_type, classes, batch, c->cfg.height, c->cfg.width,
+                              (unsigned long long*)table, (hipStream_t)stream);
+}
+
+int quber_error_overlay(quber_ctx* c, const uint8_t* bgr, const uint8_t* classes_map, int32_t batch, uint32_t color0, uint32_t color1,
+                        uint32_t color2, uint32_t color3, uint8_t* out, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (!bgr || !classes_map || !out) return fail("null tensor");
+    const unsigned colors[4] = {color0, color1, color2, color3};
+    return launch_error_overlay(bgr, classes_map, batch, c->cfg.height, c->cfg.width, colors, out, (hipStream_t)stream);
+}
+
 int64_t quber_contingency_workspace_bytes(int32_t cap) { return (int64_t)contingency_ws_bytes(cap); }
 
 int quber_label_contingency(const int32_t* pred, const int32_t* gt, int64_t n_pixels, int32_t cap, void* workspace,

@@ -334,6 +334,78 @@ class Engine:
         _lib.check(self.lib.quber_tta_merge(self.h, _ptr(logits), planes, B2 // 2, _ptr(out), _stream()))
         return out
 
+    # ---- the predicted error maps on the device (csrc/errhead.hip; INTEGRATION.md "Predicted error maps") ----
+    def error_heads(self):
+        """{head name: (first logit plane, classes)} of the enabled error heads, in the plane order of QUBER_LOGIT_BASE:
+        the boundary head first, then the region head."""
+        qc, o, heads = self.qcfg, 4, {}
+        if qc.eee_boundary_on:
+            heads["eee_boundary"] = (o, qc.error_classes)
+            o += qc.error_classes
+        if qc.eee_mask_on:
+            heads["eee_mask"] = (o, qc.error_classes)
+        return heads
+
+    def error_decode(self, logits, head, out=None, hist=None):
+        """logits f32 [B,planes,H,W]; head: a name of error_heads() or (first_plane, classes) -> (class map u8 [B,H,W],
+        pixels per class i32 [B,classes]); exactly torch.argmax(logits[:, first:first + classes], 1)."""
+        first, ncls = self.error_heads()[head] if isinstance(head, str) else head
+        B, planes = logits.shape[:2]
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape[2:] == (self.H, self.W)
+        assert 2 <= ncls <= 4 and 0 <= first and first + ncls <= planes
+        if out is None:
+            out = torch.empty((B, self.H, self.W), dtype=torch.uint8, device=self.device)
+        if hist is None:
+            hist = torch.empty((B, ncls), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (B, self.H, self.W)
+        assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.shape == (B, ncls)
+        _lib.check(self.lib.quber_error_decode(self.h, _ptr(logits), planes, first, ncls, B, _ptr(out), _ptr(hist), _stream()))
+        return out, hist
+
+    def error_mask_hist(self, classes_map, masks, n_classes, out=None):
+        """classes_map u8 [B,H,W], masks u8 [B,N,H,W] (non-zero = inside) -> i32 [B,N,n_classes]: pixels of mask n per class."""
+        B, N = masks.shape[:2]
+        assert classes_map.dtype == torch.uint8 and classes_map.is_contiguous() and classes_map.shape == (B, self.H, self.W)
+        assert masks.dtype == torch.uint8 and masks.is_contiguous() and masks.shape[2:] == (self.H, self.W)
+        if out is None:
+            out = torch.empty((B, N, n_classes), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == (B, N, n_classes)
+        _lib.check(self.lib.quber_error_mask_hist(self.h, _ptr(classes_map), _ptr(masks), B, N, n_classes, _ptr(out), _stream()))
+        return out
+
+    def error_score(self, classes_map, explicit, kind, error_type, out=None):
+        """classes_map u8 [B,H,W], explicit u8 [B,2,4,H,W] (error_maps()); kind 0 / "region" | 1 / "boundary"; error_type a name
+        or index of eval.error_maps.ERROR_TYPES -> confusion table i64 [B,classes+1,classes] (row = target, column = predicted)."""
+        from .eval import error_maps as em
+        et = em.ERROR_TYPES.index(error_type) if isinstance(error_type, str) else int(error_type)
+        kd = ("region", "boundary").index(kind) if isinstance(kind, str) else int(kind)
+        ncls = len(em.CLASS_NAMES[em.ERROR_TYPES[et]])
+        B = classes_map.shape[0]
+        assert classes_map.dtype == torch.uint8 and classes_map.is_contiguous() and classes_map.shape == (B, self.H, self.W)
+        assert explicit.dtype == torch.uint8 and explicit.is_contiguous() and explicit.shape == (B, 2, 4, self.H, self.W)
+        if out is None:
+            out = torch.empty((B, ncls + 1, ncls), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and out.is_contiguous() and out.shape == (B, ncls + 1, ncls)
+        _lib.check(self.lib.quber_error_score(self.h, _ptr(classes_map), _ptr(explicit), kd, et, ncls, B, _ptr(out), _stream()))
+        return out
+
+    def error_overlay(self, bgr, classes_map, palette, out=None):
+        """bgr u8 [B,H,W,3], classes_map u8 [B,H,W]; palette: up to 4 entries, a (B, G, R) colour or None (class not painted)
+        -> u8 [B,H,W,3]; out may be bgr."""
+        B = bgr.shape[0]
+        assert bgr.dtype == torch.uint8 and bgr.is_contiguous() and bgr.shape == (B, self.H, self.W, 3)
+        assert classes_map.dtype == torch.uint8 and classes_map.is_contiguous() and classes_map.shape == (B, self.H, self.W)
+        assert len(palette) <= 4
+        cols = [0, 0, 0, 0]
+        for i, p in enumerate(palette):
+            if p is not None:
+                cols[i] = (int(p[0]) & 255) | (int(p[1]) & 255) << 8 | (int(p[2]) & 255) << 16 | 1 << 24
+        if out is None:
+            out = torch.empty_like(bgr)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == bgr.shape
+        _lib.check(self.lib.quber_error_overlay(self.h, _ptr(bgr), _ptr(classes_map), B, *cols, _ptr(out), _stream()))
+        return out
+
     def extract_masks(self, post, max_inst, out=None):
         B = post["panoptic"].shape[0]
         if out is None:

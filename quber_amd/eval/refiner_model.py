@@ -77,9 +77,12 @@ def resize_shortest_edge_shape(oldh, oldw, short_edge_length=800, max_size=1333)
 
 class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
-                 lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False):
+                 lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
+                 decode_errors=False):
         # tta: every frame and its W-mirror in one forward, logits merged on the device (MaskRefinerPredictor(tta=True))
-        self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, tta=tta)
+        # decode_errors: the error heads' class maps, histograms and per-mask class counts in every output dict
+        self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, tta=tta,
+                                                      decode_errors=decode_errors)
         self.dataset = dataset
         self.lmffnet = None
         # "host" / True (default): csrc/inpaint.hip on the calling (worker) thread; "device": csrc/inpaint_dev.hip, bit-equal, for hosts
@@ -171,6 +174,49 @@ class MaskRefiner:
 
     def predict(self, rgb_path, depth_path, initial_masks, fg_mask=None):
         return self._refine(self._load(rgb_path, depth_path, initial_masks))
+
+    # -- the predicted error maps of one frame: scored against a ground truth, painted over the image (csrc/errhead.hip) --
+    def _error_engine(self, h, w, n_masks=64):
+        return self.refiner_predictor.model.engine_for(h, w, 1, n_masks)
+
+    def _error_classes(self, eng, output, head):
+        """The class map u8 [1,H,W] of `head`: the one decode_errors put into `output`, or decoded from the logits now."""
+        if head + "_classes" in output:
+            return output[head + "_classes"][None].contiguous()
+        logits = output[head]
+        return eng.error_decode(logits[None].contiguous(), (0, logits.shape[0]))[0]
+
+    def score_error_maps(self, output, initial_masks, gt_masks):
+        """How good is the error estimate of one frame: `output` is a dict of predict(); initial_masks / gt_masks are [N,H,W] /
+        [Ng,H,W] arrays (non-zero = inside) at the network's frame size.  The explicit TP / TN / FP / FN maps
+        (explicit_error_estimation/util.py:62-99) and the confusion table against the predicted classes
+        (util.py:29-54, targets of model.py:185-227) are computed on the device.
+        -> {head: {"confusion": int64 [C+1,C], "iou": [C], "iou_all", "iou_err", "accuracy"}} for every error head in `output`."""
+        from . import error_maps as em
+        et = self.refiner_predictor.cfg.MODEL.INS_EMBED_HEAD.ERROR_TYPE
+        u8 = lambda m: np.ascontiguousarray((np.asarray(m) != 0).astype(np.uint8))[None]
+        init, gt = u8(initial_masks), u8(gt_masks)
+        h, w = init.shape[-2:]
+        eng = self._error_engine(h, w, max(init.shape[1], gt.shape[1]))
+        explicit = eng.error_maps(self._dev(init), self._dev(gt))
+        res = {}
+        for head, kind in (("eee_boundary", "boundary"), ("eee_mask", "region")):
+            if head not in output:
+                continue
+            table = eng.error_score(self._error_classes(eng, output, head), explicit, kind, et)[0].cpu().numpy()
+            res[head] = dict(em.iou_from_confusion(table), confusion=table, iou_err=em.iou_err(table, et))
+        return res
+
+    def visualize_errors(self, bgr, output, head="eee_boundary", palette=None):
+        """The picture of eval/eval_utils.py:308-328: the predicted error classes of `head` painted over `bgr` (numpy u8 [H,W,3] at
+        the network's frame size) -> numpy u8 [H,W,3].  palette: per class a (B, G, R) colour or None; default
+        error_maps.DEFAULT_PALETTE of the configured ERROR_TYPE."""
+        from . import error_maps as em
+        if palette is None:
+            palette = em.DEFAULT_PALETTE[self.refiner_predictor.cfg.MODEL.INS_EMBED_HEAD.ERROR_TYPE]
+        bgr = np.ascontiguousarray(bgr, dtype=np.uint8)
+        eng = self._error_engine(bgr.shape[0], bgr.shape[1])
+        return eng.error_overlay(self._dev(bgr[None]), self._error_classes(eng, output, head), palette)[0].cpu().numpy()
 
     def predict_stream(self, items, workers=2, batch=1):
         """items: iterable of (rgb_path, depth_path, initial_masks[, fg_mask]) -> yields predict()'s tuple per item, in order.
@@ -289,5 +335,5 @@ class MaskRefinerTTA(MaskRefiner):
     """``MaskRefinerTTA(config_file, weights_file=..., dataset=...)`` of eval/un_eval_utils.py:79-81: MaskRefiner with horizontal-flip
     test-time augmentation.  predict() and predict_stream(batch=k) work as on MaskRefiner; the engine runs 2k frames."""
 
-    def __init__(self, config_file=None, weights_file=None, dataset="OSD", **kw):
-        super().__init__(config_file, weights_file=weights_file, dataset=dataset, tta=True, **kw)
+    def __init__(self, config_file=None, weights_file=None, dataset="OSD", decode_errors=False, **kw):
+        super().__init__(config_file, weights_file=weights_file, dataset=dataset, tta=True, decode_errors=decode_errors, **kw)

@@ -12,6 +12,9 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
   * ``tta=True``: horizontal-flip test-time augmentation, which the reference's driver asks for (eval/un_eval_utils.py:78-81)
     but never defines - every frame and its W-mirror run as one forward of 2B frames, the logits are merged on the device
     (flip back, x-offset negated, averaged: INTEGRATION.md) and post-processing runs on the merged maps.
+  * ``decode_errors=True``: every dict also carries, per error head, the class map (``eee_boundary_classes`` u8 [H,W] = the argmax
+    of the logits), its histogram and the class counts inside every initial mask, all computed on the device (csrc/errhead.hip;
+    INTEGRATION.md "Predicted error maps").  Off by default: the dicts then have the reference's keys only.
 There is no CPU fallback: construction fails if the HIP library or a GPU is missing.
 """
 import os
@@ -60,11 +63,14 @@ class RefinerModel:
     """The ``predictor.model`` object: ``model(list[dict]) -> list[dict]`` in the detectron2 convention
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
-    def __init__(self, cfg, state_dict, device, tta=False):
+    def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False):
         self.cfg = cfg
         self.state_dict = state_dict
         self.device = torch.device(device)
         self.tta = bool(tta)      # horizontal-flip test-time augmentation in predict_one / enqueue_batch: engines of capacity 2B
+        # every frame dict also carries, per error head, the class map, its histogram and (where the initial masks are on the device)
+        # the per-mask class counts (INTEGRATION.md "Predicted error maps"); off: today's keys, no extra kernel
+        self.decode_errors = bool(decode_errors)
         self._engines = {}
         self._retired = {}        # (H, W) -> the engine a larger one replaced last; see engine_for
         self._staging = {}
@@ -144,8 +150,23 @@ class RefinerModel:
             offsets.zero_()
         return eng.tta_merge(eng.forward(bgr2, depth2, offsets))
 
-    def frame_dict(self, eng, logits_b, post, b, k, masks_b):
-        """The reference's output dict of one frame (model.py:304-356) from the device-side results."""
+    def decode(self, eng, logits, d_masks=None):
+        """decode_errors: enqueue, per enabled error head, the class map and histogram of `logits` [B,planes,H,W] and - given the
+        initial masks u8 [B,N,H,W] on the device - the per-mask class counts.  -> {head: (classes, hist, mask_hist | None)} or None."""
+        if not self.decode_errors:
+            return None
+        err = {}
+        for head, (_, ncls) in eng.error_heads().items():
+            cls, hist = eng.error_decode(logits, head)
+            mh = None
+            if d_masks is not None:
+                mh = eng.error_mask_hist(cls, d_masks, ncls)
+            err[head] = (cls, hist, mh)
+        return err
+
+    def frame_dict(self, eng, logits_b, post, b, k, masks_b, err=None, n_masks=None):
+        """The reference's output dict of one frame (model.py:304-356) from the device-side results.  err: what decode() returned
+        for the batch; n_masks: the frame's own initial masks (the leading rows of its mask histogram)."""
         qc = eng.qcfg
         ncls, o = qc.error_classes, 4
         r = {"sem_seg": logits_b[0:1], "panoptic_seg": (post["panoptic"][b], None)}
@@ -154,6 +175,10 @@ class RefinerModel:
             o += ncls
         if qc.eee_mask_on:
             r["eee_mask"] = logits_b[o:o + ncls]
+        for head, (cls, hist, mh) in (err or {}).items():
+            r[head + "_classes"], r[head + "_hist"] = cls[b], hist[b]
+            if mh is not None:
+                r[head + "_mask_hist"] = mh[b] if n_masks is None else mh[b, :n_masks]
         if k > 0:
             labels = post["labels"][b, :k]
             inst = Instances((eng.H, eng.W))
@@ -164,13 +189,16 @@ class RefinerModel:
             r["instances"] = inst
         return r
 
-    def results(self, eng, logits, post):
-        """One D2H of the small per-frame tables, then mask extraction for exactly max(count) slots."""
+    def results(self, eng, logits, post, d_masks=None, n_masks=None):
+        """One D2H of the small per-frame tables, then mask extraction for exactly max(count) slots.  d_masks / n_masks (decode_errors):
+        the initial masks on the device and how many of them are each frame's own."""
         B = logits.shape[0]
+        err = self.decode(eng, logits, d_masks)
         count = post["count"].cpu().numpy()
         kmax = int(count.max()) if B else 0
         masks = eng.extract_masks(post, kmax) if kmax > 0 else None
-        return [self.frame_dict(eng, logits[b], post, b, int(count[b]), masks[b, :int(count[b])].bool() if count[b] > 0 else None)
+        return [self.frame_dict(eng, logits[b], post, b, int(count[b]), masks[b, :int(count[b])].bool() if count[b] > 0 else None,
+                                err, None if n_masks is None else n_masks[b])
                 for b in range(B)]
 
     def predict_one(self, bgr, depth, masks):
@@ -219,6 +247,7 @@ class RefinerModel:
                 stg.offsets.zero_()
             logits = eng.forward(d_bgr, d_dep, stg.offsets)        # fresh tensor: owned by the caller through the dict
         post = eng.postprocess(logits, stg.post)
+        err = self.decode(eng, logits, d_masks[:1])
         stg.pin_count.copy_(post["count"], non_blocking=True)
         torch.cuda.current_stream().synchronize()
         k = int(stg.pin_count[0])
@@ -229,7 +258,7 @@ class RefinerModel:
             masks_b = eng.extract_masks(post, k)[0].view(torch.bool)      # the kernel writes 0 / 1 bytes
         # (the caller's ``.to('cpu')`` of the masks is a plain D2H copy into fresh pageable memory: 0.17 ms for 5 MB, which a
         # prefetch into a pinned buffer plus the copy out of it does not beat - tools/predict_profile.py)
-        return self.frame_dict(eng, logits[0], post_out, 0, k, masks_b)
+        return self.frame_dict(eng, logits[0], post_out, 0, k, masks_b, err)
 
     # -- batched form on device-resident frames, split into "enqueue" and "collect" so that a caller can keep one batch in flight --
     def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False):
@@ -256,11 +285,13 @@ class RefinerModel:
         post = eng.postprocess(logits)
         slots = min(max(1, slots), eng.cap)
         masks = eng.extract_masks(post, slots)
+        err = self.decode(eng, logits, d_masks[:B])
         count = torch.empty((B,), dtype=torch.int32).pin_memory()
         count.copy_(post["count"], non_blocking=True)
         e1.record()
         eng._in_flight = getattr(eng, "_in_flight", 0) + 1
-        return {"eng": eng, "logits": logits, "post": post, "masks": masks, "slots": slots, "count": count, "e0": e0, "e1": e1}
+        return {"eng": eng, "logits": logits, "post": post, "masks": masks, "slots": slots, "count": count, "e0": e0, "e1": e1,
+                "err": err}
 
     def collect_batch(self, hd, host_masks=False):
         """-> (list of the reference's per-frame output dicts, device milliseconds of the whole batch[, per-frame numpy masks]).
@@ -276,7 +307,8 @@ class RefinerModel:
             masks = eng.extract_masks(post, kmax)
             ready = torch.cuda.Event()
             ready.record()
-        outs = [self.frame_dict(eng, hd["logits"][b], post, b, int(count[b]), masks[b, :int(count[b])].view(torch.bool) if count[b] > 0 else None)
+        outs = [self.frame_dict(eng, hd["logits"][b], post, b, int(count[b]), masks[b, :int(count[b])].view(torch.bool) if count[b] > 0 else None,
+                                hd.get("err"))
                 for b in range(len(count))]
         ms = hd["e0"].elapsed_time(hd["e1"])
         eng._in_flight = max(0, getattr(eng, "_in_flight", 1) - 1)
@@ -343,7 +375,7 @@ class RefinerModel:
 
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
-                 seed=0, state_dict=None, tta=False):
+                 seed=0, state_dict=None, tta=False, decode_errors=False):
         if config_file is None:
             self.cfg = qconfig.canonical_cfg()
         else:
@@ -369,7 +401,9 @@ class MaskRefinerPredictor:
             sd = arch.init_state_dict(seed=seed, **kw)
         self.cfg.MODEL.WEIGHTS = path or "<synthetic seed %d>" % seed
         self.tta = bool(tta)          # horizontal-flip test-time augmentation in predict() / predict_batch()
-        self.model = RefinerModel(self.cfg, sd, device, tta=self.tta)
+        # the error heads decoded on the device: `<head>_classes`, `<head>_hist`, `<head>_mask_hist` beside the logits in every dict
+        self.decode_errors = bool(decode_errors)
+        self.model = RefinerModel(self.cfg, sd, device, tta=self.tta, decode_errors=self.decode_errors)
         self.device = torch.device(device)
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
@@ -416,4 +450,4 @@ class MaskRefinerPredictor:
             offsets = eng.encode(d_masks)
             logits = eng.forward(bgr, depth, offsets)
         post = eng.postprocess(logits)
-        return self.model.results(eng, logits, post)
+        return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list])
