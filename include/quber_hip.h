@@ -218,6 +218,37 @@ int quber_error_score(quber_ctx* ctx, const uint8_t* dev_classes, const uint8_t*
 int quber_error_overlay(quber_ctx* ctx, const uint8_t* dev_bgr, const uint8_t* dev_classes, int32_t batch, uint32_t color0,
                         uint32_t color1, uint32_t color2, uint32_t color3, uint8_t* dev_out, void* stream);
 
+/* Iterative refinement (csrc/iterate.hip): the refined label map of one pass fed back as the initial masks of the next without
+ * leaving the device, and what the refinement did to the caller's masks.  No reference counterpart: the reference refines once
+ * (maskrefiner/predictor.py:287-359).  All three work on a context created with with_network = 0, take any H, W and pointer
+ * alignment (4 bytes for the 32-bit maps), use integer arithmetic only (exact, order-independent) and overwrite their outputs
+ * (the call clears what it accumulates into, on `stream`).
+ *
+ * The label map of quber_postprocess as the input of quber_encode_label_map:
+ *   dev_panoptic f32 [B][H][W], dev_labels f32 [B][top_k] (ascending), dev_count i32 [B] (read on the device; above top_k: top_k)
+ *   -> dev_ids i32 [B][H][W]: 1 + j where j < count[b] is the first position of the pixel's value in labels[b][0 .. count[b]),
+ *      0 when the value is not in that list (-1, or anything else).  The value is looked up, not offset: the list need not be
+ *      consecutive and may hold `label_divisor` itself (the K = 0 "stuff blob" of post_processing.py:110-162).
+ *   mirror != 0: dev_ids is [2B][H][W] and frame B + b receives the W-mirror, ids[B + b][y][x] = ids[b][y][W - 1 - x] (the
+ *      test-time-augmentation pass: quber_encode_label_map then runs on all 2B frames); 2 * batch <= max_batch. */
+int quber_relabel_panoptic(quber_ctx* ctx, const float* dev_panoptic, const float* dev_labels, const int32_t* dev_count,
+                           int32_t batch, int32_t mirror, int32_t* dev_ids, void* stream);
+/* Initial masks against a compact label map: which refined instance came from which initial mask, what was dropped.
+ *   dev_masks u8 [B][n_masks][H][W] (non-zero = inside), n_masks 0..max_instances (0: only dev_area); dev_ids i32 [B][H][W],
+ *   n_ids 0..254
+ *   -> dev_table u32 [B][n_masks][n_ids + 1]: pixels of mask n whose id is j; dev_area u32 [B][n_ids + 1] (may be NULL): pixels
+ *      whose id is j.  Overlapping masks each count their own pixels; a pixel whose id lies outside 0..n_ids is counted nowhere. */
+int quber_overlap_masks(quber_ctx* ctx, const uint8_t* dev_masks, const int32_t* dev_ids, int32_t batch, int32_t n_masks,
+                        int32_t n_ids, uint32_t* dev_table, uint32_t* dev_area, void* stream);
+/* Two compact label maps against each other (successive passes):
+ *   dev_a, dev_b i32 [B][H][W], n_a, n_b 0..254
+ *   -> dev_table u32 [B][n_a + 1][n_b + 1]: pixels with a == i and b == j; out-of-range ids are counted nowhere.
+ * The two maps describe the same segmentation iff every row and every column holds at most one non-zero cell and row 0 and
+ * column 0 hold none besides [0][0].  (quber_label_contingency below is one frame per call, compacts arbitrary 16-bit labels and
+ * needs a workspace; this one takes compact ids and a batch.) */
+int quber_overlap_ids(quber_ctx* ctx, const int32_t* dev_a, const int32_t* dev_b, int32_t batch, int32_t n_a, int32_t n_b,
+                      uint32_t* dev_table, void* stream);
+
 /* evaluation support - all pairwise overlap counts of two label maps in one pass.  Replaces the per-pair
  * np.count_nonzero loops of eval/evaluation.py:180-199 (multilabel_metrics).
  *   dev_pred, dev_gt i32 [n_pixels], label values in 0..65535, at most `cap` (<= 1024) distinct values per map

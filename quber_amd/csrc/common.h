@@ -303,6 +303,13 @@ int launch_error_score(const uint8_t* cls, const uint8_t* expl, int kind, int er
                        unsigned long long* table, hipStream_t st);
 int launch_error_overlay(const uint8_t* bgr, const uint8_t* cls, int B, int H, int W, const unsigned* colors, uint8_t* out,
                          hipStream_t st);
+// iterative refinement (iterate.hip): postprocess label map -> compact ids [+ their W-mirrors behind the batch]; pixels of every initial
+// mask per id (+ area per id); contingency table of two compact id maps
+int launch_relabel_panoptic(const float* pan, const float* labels, const int* count, int B, int top_k, int mirror, int H, int W,
+                            int* ids, hipStream_t st);
+int launch_overlap_masks(const uint8_t* masks, const int* ids, int B, int N, int n_ids, int H, int W, unsigned* table, unsigned* area,
+                         hipStream_t st);
+int launch_overlap_ids(const int* a, const int* b, int B, int n_a, int n_b, int H, int W, unsigned* table, hipStream_t st);
 int launch_group_pixels(const float* logits, int nch, int B, int H, int W, int cap, const int* centers, const int* ncenters,
                         uint8_t* idmap, unsigned* area, hipStream_t st);
 

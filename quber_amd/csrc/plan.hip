@@ -1755,6 +1755,32 @@ int quber_error_overlay(quber_ctx* c, const uint8_t* bgr, const uint8_t* classes
     return launch_error_overlay(bgr, classes_map, batch, c->cfg.height, c->cfg.width, colors, out, (hipStream_t)stream);
 }
 
+// ---- iterative refinement (iterate.hip); usable on a context without a network ----
+int quber_relabel_panoptic(quber_ctx* c, const float* panoptic, const float* labels, const int32_t* count, int32_t batch, int32_t mirror,
+                           int32_t* ids, void* stream) {
+    if (mirror ? check_tta_batch(c, batch) : check_batch(c, batch)) return -1;
+    if (!panoptic || !labels || !count || !ids) return fail("null tensor");
+    return launch_relabel_panoptic(panoptic, labels, count, batch, c->cfg.top_k, mirror != 0, c->cfg.height, c->cfg.width, ids,
+                                   (hipStream_t)stream);
+}
+
+int quber_overlap_masks(quber_ctx* c, const uint8_t* masks, const int32_t* ids, int32_t batch, int32_t n_masks, int32_t n_ids,
+                        uint32_t* table, uint32_t* area, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_masks < 0 || n_masks > c->cfg.max_instances) return fail("initial masks outside 0..max_instances");
+    if (n_ids < 0 || n_ids > 254) return fail("n_ids outside 0..254");
+    if (!ids || (n_masks > 0 && (!masks || !table))) return fail("null tensor");
+    return launch_overlap_masks(masks, ids, batch, n_masks, n_ids, c->cfg.height, c->cfg.width, table, area, (hipStream_t)stream);
+}
+
+int quber_overlap_ids(quber_ctx* c, const int32_t* a, const int32_t* b, int32_t batch, int32_t n_a, int32_t n_b, uint32_t* table,
+                      void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_a < 0 || n_a > 254 || n_b < 0 || n_b > 254) return fail("n_a / n_b outside 0..254");
+    if (!a || !b || !table) return fail("null tensor");
+    return launch_overlap_ids(a, b, batch, n_a, n_b, c->cfg.height, c->cfg.width, table, (hipStream_t)stream);
+}
+
 int64_t quber_contingency_workspace_bytes(int32_t cap) { return (int64_t)contingency_ws_bytes(cap); }
 
 int quber_label_contingency(const int32_t* pred, const int32_t* gt, int64_t n_pixels, int32_t cap, void* workspace,

@@ -406,6 +406,50 @@ class Engine:
         _lib.check(self.lib.quber_error_overlay(self.h, _ptr(bgr), _ptr(classes_map), B, *cols, _ptr(out), _stream()))
         return out
 
+    # ---- iterative refinement on the device (csrc/iterate.hip; INTEGRATION.md "Iterative refinement") ----
+    def relabel_panoptic(self, post, mirror=False, out=None):
+        """post: the dict of postprocess() -> compact ids i32 [B,H,W] (0 = no instance, 1 + j = the frame's j-th label), the input of
+        encode_label_map().  mirror: [2B,H,W], frames [B,2B) holding the W-mirrors of frames [0,B)."""
+        pan = post["panoptic"]
+        B = pan.shape[0]
+        assert pan.dtype == torch.float32 and pan.is_contiguous() and pan.shape == (B, self.H, self.W)
+        assert post["labels"].dtype == torch.float32 and post["labels"].is_contiguous() and post["labels"].shape == (B, self.cap)
+        assert post["count"].dtype == torch.int32 and post["count"].shape == (B,)
+        shape = ((2 * B) if mirror else B, self.H, self.W)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == shape
+        _lib.check(self.lib.quber_relabel_panoptic(self.h, _ptr(pan), _ptr(post["labels"]), _ptr(post["count"]), B, int(bool(mirror)),
+                                                   _ptr(out), _stream()))
+        return out
+
+    def overlap_masks(self, masks, ids, n_ids, out=None):
+        """masks u8 [B,N,H,W] (non-zero = inside), ids i32 [B,H,W] in 0..n_ids -> (table i32 [B,N,n_ids+1]: pixels of mask n with
+        id j, area i32 [B,n_ids+1]: pixels with id j).  out: a (table, area) pair to write into."""
+        B, N = masks.shape[:2]
+        assert masks.dtype == torch.uint8 and masks.is_contiguous() and masks.shape[2:] == (self.H, self.W)
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.shape == (B, self.H, self.W)
+        table, area = out if out is not None else (None, None)
+        if table is None:
+            table = torch.empty((B, N, n_ids + 1), dtype=torch.int32, device=self.device)
+        if area is None:
+            area = torch.empty((B, n_ids + 1), dtype=torch.int32, device=self.device)
+        assert table.dtype == torch.int32 and table.is_contiguous() and table.shape == (B, N, n_ids + 1)
+        assert area.dtype == torch.int32 and area.is_contiguous() and area.shape == (B, n_ids + 1)
+        _lib.check(self.lib.quber_overlap_masks(self.h, _ptr(masks), _ptr(ids), B, N, n_ids, _ptr(table), _ptr(area), _stream()))
+        return table, area
+
+    def overlap_ids(self, a, b, n_a, n_b, out=None):
+        """a, b i32 [B,H,W] with ids in 0..n_a / 0..n_b -> i32 [B,n_a+1,n_b+1]: pixels with a == i and b == j."""
+        B = a.shape[0]
+        for t in (a, b):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.shape == (B, self.H, self.W)
+        if out is None:
+            out = torch.empty((B, n_a + 1, n_b + 1), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == (B, n_a + 1, n_b + 1)
+        _lib.check(self.lib.quber_overlap_ids(self.h, _ptr(a), _ptr(b), B, n_a, n_b, _ptr(out), _stream()))
+        return out
+
     def extract_masks(self, post, max_inst, out=None):
         B = post["panoptic"].shape[0]
         if out is None:

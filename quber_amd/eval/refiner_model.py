@@ -78,11 +78,15 @@ def resize_shortest_edge_shape(oldh, oldw, short_edge_length=800, max_size=1333)
 class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
                  lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
-                 decode_errors=False):
+                 decode_errors=False, iterations=1, until_converged=False, track_initial=False):
         # tta: every frame and its W-mirror in one forward, logits merged on the device (MaskRefinerPredictor(tta=True))
         # decode_errors: the error heads' class maps, histograms and per-mask class counts in every output dict
+        # iterations / until_converged / track_initial: the refined masks fed back for further passes on the device, early stop at a
+        # fixed point (predict() only: the stream always runs the fixed count), initial_overlap / initial_index / initial_iou in every
+        # output dict (INTEGRATION.md "Iterative refinement")
         self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, tta=tta,
-                                                      decode_errors=decode_errors)
+                                                      decode_errors=decode_errors, iterations=iterations,
+                                                      until_converged=until_converged, track_initial=track_initial)
         self.dataset = dataset
         self.lmffnet = None
         # "host" / True (default): csrc/inpaint.hip on the calling (worker) thread; "device": csrc/inpaint_dev.hip, bit-equal, for hosts
@@ -267,6 +271,7 @@ class MaskRefiner:
                 torch.cuda.current_stream().wait_event(f["ready"])
             two = self.refiner_predictor.depth_on and self.refiner_predictor.rgb_on
             B_ = len(frs)
+            own = [f["d_masks"].shape[0] for f in frs]      # each frame's own masks among the n rows of the batch
             if model.tta:
                 # test-time augmentation: the frames go straight into the first halves of 2B-frame buffers (the flip fills the rest)
                 d_rgb, d_depth, d_masks = model.tta_alloc(B_, H_, W_, n, two)
@@ -281,10 +286,10 @@ class MaskRefiner:
                 torch.stack(img, out=d_rgb[:B_])
                 if two:
                     torch.stack([f["d_depth"] for f in frs], out=d_depth[:B_])
-                return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, halves=True)
+                return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, halves=True, n_masks=own)
             d_rgb = torch.stack(img)
             d_depth = torch.stack([f["d_depth"] for f in frs]) if two else None
-            return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k)
+            return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, n_masks=own)
 
         def collect(frs, hd):
             outs, ms, host = self.refiner_predictor.model.collect_batch(hd, host_masks=True)

@@ -15,6 +15,9 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
   * ``decode_errors=True``: every dict also carries, per error head, the class map (``eee_boundary_classes`` u8 [H,W] = the argmax
     of the logits), its histogram and the class counts inside every initial mask, all computed on the device (csrc/errhead.hip;
     INTEGRATION.md "Predicted error maps").  Off by default: the dicts then have the reference's keys only.
+  * ``iterations=k``: the refined masks are fed back as the initial masks of a further pass, k passes in all, without leaving the
+    device (csrc/iterate.hip; INTEGRATION.md "Iterative refinement"); ``until_converged=True`` stops as soon as a pass reproduces its
+    input; ``track_initial=True`` reports which refined instance came from which initial mask.  Defaults: one pass, today's keys.
 There is no CPU fallback: construction fails if the HIP library or a GPU is missing.
 """
 import os
@@ -39,13 +42,40 @@ def load_checkpoint(path):
     return {k: (v.numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in sd.items()}
 
 
+def same_segmentation(table):
+    """table int [B,n+1,m+1] of Engine.overlap_ids (row / column 0 = no instance) -> bool [B]: the two label maps describe the same
+    segmentation, i.e. every row and every column holds at most one non-zero cell and row 0 / column 0 none besides [0][0].  The next
+    pass's encoding depends on the masks as sets only, so a frame for which this holds has reached a fixed point."""
+    nz = table != 0
+    ok = (nz.sum(2) <= 1).all(1) & (nz.sum(1) <= 1).all(1)
+    return ok & ~nz[:, 0, 1:].any(1) & ~nz[:, 1:, 0].any(1)
+
+
+def match_initial(table, area, n, k):
+    """table int [N,K+1] / area int [K+1] of Engine.overlap_masks for one frame, its n initial masks and k instances ->
+    (initial_overlap i64 [n,k+1], initial_index i64 [k], initial_iou f32 [k]): per instance the initial mask of the largest IoU
+    (inter / (|mask| + area - inter) in float64, the first index wins ties; -1 / 0 when no initial mask touches it)."""
+    tab = table[:n, :k + 1].to(torch.int64)
+    if n == 0 or k == 0:
+        return tab, torch.full((k,), -1, dtype=torch.int64, device=tab.device), torch.zeros((k,), dtype=torch.float32, device=tab.device)
+    inter = tab[:, 1:].to(torch.float64)
+    size = table[:n].sum(1, dtype=torch.int64).to(torch.float64)          # every pixel of a mask has some id: the row sum is |mask|
+    union = size[:, None] + area[1:k + 1].to(torch.float64)[None] - inter
+    iou = torch.where(union > 0, inter / union.clamp(min=1.0), torch.zeros_like(union))
+    best = iou.max(0).values
+    down = torch.arange(n, 0, -1, device=tab.device)[:, None]             # the first index among equals (argmax promises no order)
+    first = n - ((iou == best[None]) * down).max(0).values
+    touched = best > 0
+    return tab, torch.where(touched, first, torch.full_like(first, -1)), torch.where(touched, best, torch.zeros_like(best)).to(torch.float32)
+
+
 class _FrameStaging:
     """Buffers of the batch-1 call path for one frame size, allocated once: ONE pinned host block and ONE device block for the
     frame's inputs (bgr | depth | initial masks, uploaded in a few pipelined pieces), the device-side intermediates, and pinned
     word for the instance count.  frames = 2 (test-time augmentation): the device block holds every input for two frames - the
     uploaded frame in slot 0, its mirror in slot 1 (bgr [2,H,W,3] | depth [2,H,W,3] | masks [2,N,H,W]); the host block one."""
 
-    def __init__(self, eng, n_cap, frames=1):
+    def __init__(self, eng, n_cap, frames=1, iterate=False, track=False):
         H, W, dev = eng.H, eng.W, eng.device
         hw = H * W
         self.n_cap = n_cap
@@ -55,15 +85,34 @@ class _FrameStaging:
         self.dev_in = torch.empty(frames * (6 * hw + n_cap * hw), dtype=torch.uint8, device=dev)
         self.offsets = torch.empty((frames, 3, H, W), dtype=torch.float32, device=dev)
         self.post = eng.alloc_post(1)
-        self.pin_count = torch.empty((1,), dtype=torch.int32).pin_memory()
+        self.pin_count = torch.empty((2,), dtype=torch.int32).pin_memory()     # instance count, refine_converged_at
         self.done = torch.cuda.Event()
+        self.iterate, self.track = iterate, track
+        # iterations > 1: the two id maps (this pass's input, its refined map) and their overlap table; track_initial: the tables
+        self.iter_bufs = _iter_buffers(eng, 1, frames, self.offsets) if iterate else None
+        k1 = eng.cap + 1
+        self.overlap = (torch.empty((1, n_cap, k1), dtype=torch.int32, device=dev),
+                        torch.empty((1, k1), dtype=torch.int32, device=dev)) if track else None
+
+
+def _iter_buffers(eng, B, frames, offsets=None):
+    """(ids in, ids out, overlap table, offsets) of the passes >= 2 for B frames (frames = 2: and their mirrors)."""
+    dev, k1 = eng.device, eng.cap + 1
+    if offsets is None:
+        offsets = torch.empty((frames * B, 3, eng.H, eng.W), dtype=torch.float32, device=dev)
+    return (torch.empty((frames * B, eng.H, eng.W), dtype=torch.int32, device=dev),
+            torch.empty((frames * B, eng.H, eng.W), dtype=torch.int32, device=dev),
+            torch.empty((B, k1, k1), dtype=torch.int32, device=dev), offsets)
 
 
 class RefinerModel:
     """The ``predictor.model`` object: ``model(list[dict]) -> list[dict]`` in the detectron2 convention
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
-    def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False):
+    def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False, iterations=1, until_converged=False,
+                 track_initial=False):
+        if int(iterations) < 1:
+            raise ValueError("iterations must be >= 1")
         self.cfg = cfg
         self.state_dict = state_dict
         self.device = torch.device(device)
@@ -71,6 +120,14 @@ class RefinerModel:
         # every frame dict also carries, per error head, the class map, its histogram and (where the initial masks are on the device)
         # the per-mask class counts (INTEGRATION.md "Predicted error maps"); off: today's keys, no extra kernel
         self.decode_errors = bool(decode_errors)
+        # iterative refinement: passes per call, early stop at a fixed point (predict_one / predict_batch only),
+        # initial_overlap / initial_index / initial_iou in every dict
+        self.iterations = int(iterations)
+        self.until_converged = bool(until_converged)
+        self.track_initial = bool(track_initial)
+        self.top_k = 200 if cfg is None else int(cfg.MODEL.PANOPTIC_DEEPLAB.TOP_K_INSTANCE)
+        assert 1 <= self.top_k <= 254, "the label-map encoding holds at most 254 instances per frame"
+        self.debug_passes = None  # tests: a list that receives, per pass, its input ids, logits, post tables and refined ids
         self._engines = {}
         self._retired = {}        # (H, W) -> the engine a larger one replaced last; see engine_for
         self._staging = {}
@@ -81,6 +138,8 @@ class RefinerModel:
 
     def engine_for(self, h, w, batch, n_masks=64):
         key = (h, w)
+        if self.iterations > 1:
+            n_masks = max(n_masks, self.top_k)       # a pass >= 2 encodes a label map of up to top_k instances
         eng = self._engines.get(key)
         if eng is None or eng.qcfg.max_batch < batch or eng.qcfg.max_instances < n_masks:
             # grow, never shrink: alternating workloads must not trigger repeated multi-GB rebuilds
@@ -105,8 +164,9 @@ class RefinerModel:
         key = (eng.H, eng.W)
         stg = self._staging.get(key)
         frames = 2 if self.tta else 1
-        if stg is None or stg.n_cap < n_masks or stg.frames != frames:
-            stg = _FrameStaging(eng, max(64, n_masks), frames)
+        it, tr = self.iterations > 1, self.track_initial
+        if stg is None or stg.n_cap < n_masks or stg.frames != frames or stg.iterate != it or stg.track != tr:
+            stg = _FrameStaging(eng, max(64, n_masks), frames, it, tr)
             self._staging[key] = stg
         return stg
 
@@ -136,10 +196,13 @@ class RefinerModel:
                 buf[:B].copy_(t)
         return bufs
 
-    def tta_logits(self, eng, bgr2, depth2, masks2, offsets=None):
+    def tta_logits(self, eng, bgr2, depth2, masks2, offsets=None, ready=False):
         """The augmented forward on 2B-frame buffers whose first halves hold the frames, all on the current stream: mirror the
         inputs into the second halves, a1 on all 2B frames (the mirrored frames' own encoding), one forward of 2B frames, merge
-        -> logits f32 [B,planes,H,W] of the B frames.  `offsets`: an optional [2B,3,H,W] buffer for a1."""
+        -> logits f32 [B,planes,H,W] of the B frames.  `offsets`: an optional [2B,3,H,W] buffer for a1.  ready=True (a pass >= 2 of
+        the iterative refinement): the images are mirrored already and `offsets` holds a1 of all 2B frames."""
+        if ready:
+            return eng.tta_merge(eng.forward(bgr2, depth2, offsets))
         n = 0 if masks2 is None else masks2.shape[1]
         eng.tta_flip_inputs(bgr2, depth2, masks2 if n else None)
         if n:
@@ -164,9 +227,51 @@ class RefinerModel:
             err[head] = (cls, hist, mh)
         return err
 
-    def frame_dict(self, eng, logits_b, post, b, k, masks_b, err=None, n_masks=None):
+    # -- iterative refinement (INTEGRATION.md "Iterative refinement") --
+    def refine(self, eng, bgr, depth, logits, post, B, may_stop=False, bufs=None):
+        """Passes 2 .. iterations on frames whose pass 1 has just been enqueued: relabel_panoptic(post) -> encode_label_map -> forward
+        -> postprocess (into the same `post` tables), all on the current stream, nothing copied to the host unless may_stop and
+        until_converged (the flags are then read after every pass).  bgr / depth: the buffers pass 1 ran on (test-time augmentation:
+        2B frames, mirrors filled).  -> (logits, post, it) of the last pass; it: None for iterations == 1, else the passes run, the
+        per-frame refine_converged_at (device, i32 [B]) and the last pass's refined map as compact ids."""
+        if self.iterations == 1:
+            return logits, post, None
+        K = eng.cap
+        ids_in, ids_out, table, offsets = bufs if bufs is not None else _iter_buffers(eng, B, 2 if self.tta else 1)
+        conv = torch.zeros((B,), dtype=torch.int32, device=self.device)
+        dbg = self.debug_passes
+        snap = lambda d: {k: v.clone() for k, v in d.items()}
+        eng.relabel_panoptic(post, mirror=self.tta, out=ids_in)
+        if dbg is not None:
+            dbg.append({"ids_in": None, "logits": logits, "post": snap(post), "ids_out": ids_in[:B].clone()})
+        passes = 1
+        for p in range(2, self.iterations + 1):
+            eng.encode_label_map(ids_in, K, offsets)
+            logits = self.tta_logits(eng, bgr, depth, None, offsets, ready=True) if self.tta else eng.forward(bgr, depth, offsets)
+            eng.postprocess(logits, post)
+            eng.relabel_panoptic(post, mirror=self.tta, out=ids_out)
+            eng.overlap_ids(ids_in[:B], ids_out[:B], K, K, out=table)
+            conv = torch.where((conv == 0) & same_segmentation(table), torch.full_like(conv, p), conv)
+            passes = p
+            if dbg is not None:
+                dbg.append({"ids_in": ids_in[:B].clone(), "logits": logits, "post": snap(post), "ids_out": ids_out[:B].clone()})
+            ids_in, ids_out = ids_out, ids_in
+            if may_stop and self.until_converged and p < self.iterations and bool((conv > 0).all()):
+                break
+        return logits, post, {"passes": passes, "conv": conv, "ids": ids_in[:B]}
+
+    def track(self, eng, d_masks, post, it, out=None):
+        """track_initial: enqueue the overlap of the initial masks u8 [B,N,H,W] with the last pass's refined map -> (table, area) or None."""
+        if not self.track_initial:
+            return None
+        ids = it["ids"] if it is not None else eng.relabel_panoptic(post)
+        return eng.overlap_masks(d_masks, ids, eng.cap, out=out)
+
+    def frame_dict(self, eng, logits_b, post, b, k, masks_b, err=None, n_masks=None, it=None, conv=0, ov=None, n_own=None):
         """The reference's output dict of one frame (model.py:304-356) from the device-side results.  err: what decode() returned
-        for the batch; n_masks: the frame's own initial masks (the leading rows of its mask histogram)."""
+        for the batch; n_masks: the frame's own initial masks (the leading rows of its mask histogram and of initial_overlap);
+        it / conv: what refine() returned and the frame's refine_converged_at on the host; ov: what track() returned; n_own: per frame
+        of the batch, the rows of initial_overlap where n_masks is not given (collect_batch: the mask histogram keeps all N rows)."""
         qc = eng.qcfg
         ncls, o = qc.error_classes, 4
         r = {"sem_seg": logits_b[0:1], "panoptic_seg": (post["panoptic"][b], None)}
@@ -179,6 +284,11 @@ class RefinerModel:
             r[head + "_classes"], r[head + "_hist"] = cls[b], hist[b]
             if mh is not None:
                 r[head + "_mask_hist"] = mh[b] if n_masks is None else mh[b, :n_masks]
+        if it is not None:
+            r["refine_passes"], r["refine_converged_at"] = it["passes"], int(conv)
+        if ov is not None:
+            r["initial_overlap"], first, iou = match_initial(
+                ov[0][b], ov[1][b], n_masks if n_masks is not None else int(n_own[b]) if n_own is not None else ov[0].shape[1], k)
         if k > 0:
             labels = post["labels"][b, :k]
             inst = Instances((eng.H, eng.W))
@@ -186,19 +296,22 @@ class RefinerModel:
             inst.scores = post["scores"][b, :k]
             inst.pred_boxes = Boxes(post["boxes"][b, :k])
             inst.pred_classes = (torch.div(labels, LABEL_DIVISOR, rounding_mode="floor") - 1).to(torch.int64)
+            if ov is not None:
+                inst.initial_index, inst.initial_iou = first, iou
             r["instances"] = inst
         return r
 
-    def results(self, eng, logits, post, d_masks=None, n_masks=None):
+    def results(self, eng, logits, post, d_masks=None, n_masks=None, it=None, ov=None):
         """One D2H of the small per-frame tables, then mask extraction for exactly max(count) slots.  d_masks / n_masks (decode_errors):
-        the initial masks on the device and how many of them are each frame's own."""
+        the initial masks on the device and how many of them are each frame's own.  it / ov: what refine() / track() returned."""
         B = logits.shape[0]
-        err = self.decode(eng, logits, d_masks)
+        err = self.decode(eng, logits, d_masks if it is None else None)       # (a pass >= 2 has no initial masks to attribute to)
         count = post["count"].cpu().numpy()
+        conv = it["conv"].cpu().numpy() if it is not None else np.zeros((B,), np.int32)
         kmax = int(count.max()) if B else 0
         masks = eng.extract_masks(post, kmax) if kmax > 0 else None
         return [self.frame_dict(eng, logits[b], post, b, int(count[b]), masks[b, :int(count[b])].bool() if count[b] > 0 else None,
-                                err, None if n_masks is None else n_masks[b])
+                                err, None if n_masks is None else n_masks[b], it, conv[b], ov)
                 for b in range(B)]
 
     def predict_one(self, bgr, depth, masks):
@@ -247,8 +360,14 @@ class RefinerModel:
                 stg.offsets.zero_()
             logits = eng.forward(d_bgr, d_dep, stg.offsets)        # fresh tensor: owned by the caller through the dict
         post = eng.postprocess(logits, stg.post)
-        err = self.decode(eng, logits, d_masks[:1])
-        stg.pin_count.copy_(post["count"], non_blocking=True)
+        logits, post, it = self.refine(eng, d_bgr, d_dep, logits, post, 1, True, stg.iter_bufs)
+        ov = None
+        if self.track_initial:
+            ov = self.track(eng, d_masks[:1], post, it, (stg.overlap[0][:, :n], stg.overlap[1]))
+        err = self.decode(eng, logits, d_masks[:1] if it is None else None)
+        stg.pin_count[:1].copy_(post["count"], non_blocking=True)
+        if it is not None:
+            stg.pin_count[1:].copy_(it["conv"], non_blocking=True)
         torch.cuda.current_stream().synchronize()
         k = int(stg.pin_count[0])
         post_out = {"panoptic": post["panoptic"].clone(), "labels": post["labels"].clone(), "scores": post["scores"].clone(),
@@ -258,14 +377,15 @@ class RefinerModel:
             masks_b = eng.extract_masks(post, k)[0].view(torch.bool)      # the kernel writes 0 / 1 bytes
         # (the caller's ``.to('cpu')`` of the masks is a plain D2H copy into fresh pageable memory: 0.17 ms for 5 MB, which a
         # prefetch into a pinned buffer plus the copy out of it does not beat - tools/predict_profile.py)
-        return self.frame_dict(eng, logits[0], post_out, 0, k, masks_b, err)
+        return self.frame_dict(eng, logits[0], post_out, 0, k, masks_b, err, None, it, int(stg.pin_count[1]) if it is not None else 0, ov)
 
     # -- batched form on device-resident frames, split into "enqueue" and "collect" so that a caller can keep one batch in flight --
-    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False):
+    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None):
         """d_bgr / d_depth: u8 [B,H,W,3] (depth None for single-stream configs), d_masks: u8 [B,N,H,W] on the device.  Enqueues a1 ...
         a11 and the extraction of the first `slots` instance masks of every frame on the current stream WITHOUT synchronising;
         returns a handle for collect_batch().  halves=True (test-time augmentation only): the tensors are 2B-frame buffers
-        (tta_alloc) whose first halves hold the B frames."""
+        (tta_alloc) whose first halves hold the B frames.  n_masks: how many of the N masks are each frame's own (the rows of
+        `initial_overlap` under track_initial; default: all N)."""
         if halves:
             assert self.tta and d_bgr.shape[0] % 2 == 0
         B, H, W = d_bgr.shape[:3]
@@ -275,7 +395,9 @@ class RefinerModel:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         if self.tta:
-            logits = self.tta_logits(eng, *((d_bgr, d_depth, d_masks) if halves else self.tta_buffers(d_bgr, d_depth, d_masks)))
+            if not halves:
+                d_bgr, d_depth, d_masks = self.tta_buffers(d_bgr, d_depth, d_masks)
+            logits = self.tta_logits(eng, d_bgr, d_depth, d_masks)
         else:
             if d_masks.shape[1]:
                 offsets = eng.encode(d_masks)
@@ -283,15 +405,21 @@ class RefinerModel:
                 offsets = torch.zeros((B, 3, H, W), dtype=torch.float32, device=self.device)
             logits = eng.forward(d_bgr, d_depth, offsets)
         post = eng.postprocess(logits)
+        logits, post, it = self.refine(eng, d_bgr, d_depth, logits, post, B)           # always the fixed count: nothing is read back here
+        ov = self.track(eng, d_masks[:B], post, it)
         slots = min(max(1, slots), eng.cap)
         masks = eng.extract_masks(post, slots)
-        err = self.decode(eng, logits, d_masks[:B])
-        count = torch.empty((B,), dtype=torch.int32).pin_memory()
+        err = self.decode(eng, logits, d_masks[:B] if it is None else None)
+        pinned = torch.zeros((2, B), dtype=torch.int32).pin_memory()                   # instance counts, refine_converged_at
+        count = pinned[0]
         count.copy_(post["count"], non_blocking=True)
+        if it is not None:
+            pinned[1].copy_(it["conv"], non_blocking=True)
         e1.record()
         eng._in_flight = getattr(eng, "_in_flight", 0) + 1
         return {"eng": eng, "logits": logits, "post": post, "masks": masks, "slots": slots, "count": count, "e0": e0, "e1": e1,
-                "err": err}
+                "err": err, "it": it, "conv": pinned[1], "ov": ov,
+                "n_masks": n_masks}
 
     def collect_batch(self, hd, host_masks=False):
         """-> (list of the reference's per-frame output dicts, device milliseconds of the whole batch[, per-frame numpy masks]).
@@ -299,7 +427,7 @@ class RefinerModel:
         output['instances'].to('cpu').pred_masks.numpy() - through ONE device-to-host copy for the whole batch (the arrays of a
         batch are views of one host block)."""
         hd["e1"].synchronize()
-        eng, post, count = hd["eng"], hd["post"], hd["count"].numpy()
+        eng, post, count, conv = hd["eng"], hd["post"], hd["count"].numpy(), hd["conv"].numpy()
         kmax = int(count.max()) if len(count) else 0
         ready = hd["e1"]
         masks = hd["masks"]
@@ -308,7 +436,7 @@ class RefinerModel:
             ready = torch.cuda.Event()
             ready.record()
         outs = [self.frame_dict(eng, hd["logits"][b], post, b, int(count[b]), masks[b, :int(count[b])].view(torch.bool) if count[b] > 0 else None,
-                                hd.get("err"))
+                                hd.get("err"), None, hd.get("it"), conv[b], hd.get("ov"), hd.get("n_masks"))
                 for b in range(len(count))]
         ms = hd["e0"].elapsed_time(hd["e1"])
         eng._in_flight = max(0, getattr(eng, "_in_flight", 1) - 1)
@@ -375,7 +503,9 @@ class RefinerModel:
 
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
-                 seed=0, state_dict=None, tta=False, decode_errors=False):
+                 seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False):
+        if int(iterations) < 1:
+            raise ValueError("iterations must be >= 1")
         if config_file is None:
             self.cfg = qconfig.canonical_cfg()
         else:
@@ -403,7 +533,11 @@ class MaskRefinerPredictor:
         self.tta = bool(tta)          # horizontal-flip test-time augmentation in predict() / predict_batch()
         # the error heads decoded on the device: `<head>_classes`, `<head>_hist`, `<head>_mask_hist` beside the logits in every dict
         self.decode_errors = bool(decode_errors)
-        self.model = RefinerModel(self.cfg, sd, device, tta=self.tta, decode_errors=self.decode_errors)
+        # iterative refinement: `iterations` passes per call, the refined masks fed back on the device; until_converged:
+        # predict() / predict_batch() stop at a fixed point; track_initial: initial_overlap / initial_index / initial_iou in every dict
+        self.iterations, self.until_converged, self.track_initial = int(iterations), bool(until_converged), bool(track_initial)
+        self.model = RefinerModel(self.cfg, sd, device, tta=self.tta, decode_errors=self.decode_errors, iterations=self.iterations,
+                                  until_converged=self.until_converged, track_initial=self.track_initial)
         self.device = torch.device(device)
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
@@ -450,4 +584,6 @@ class MaskRefinerPredictor:
             offsets = eng.encode(d_masks)
             logits = eng.forward(bgr, depth, offsets)
         post = eng.postprocess(logits)
-        return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list])
+        logits, post, it = self.model.refine(eng, bgr, depth, logits, post, B, True)
+        ov = self.model.track(eng, d_masks[:B], post, it)
+        return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list], it, ov)
