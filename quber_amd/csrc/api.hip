@@ -1,0 +1,547 @@
+// The C ABI of libquber_hip.so: contexts, weight ingestion, the forward pass and the context-free adapter / metrics / in-painting entries.
+// (The stand-alone test ops quber_op_* are in api_ops.hip.)
+#include "plan.h"
+
+#include <optional>
+
+using namespace quber;
+
+// the time-stamp readers of the diagnostic builds (wino_fused.hip WF_STAMPS, conv_h8.hip H8_STAMPS, conv_x8.hip X8_STAMPS)
+namespace quber { int wf_read_stamps(unsigned long long* dst, int n), h8_read_stamps(unsigned long long* dst, int n), x8_read_stamps(unsigned long long* dst, int n); }
+
+int quber::check_cfg(const quber_config& c) {
+    if (c.height <= 0 || c.width <= 0) return fail("height and width must be positive");
+    if (c.with_network && (c.height < 16 || c.width < 16)) return fail("frames smaller than 16 x 16 are not supported");
+    if (c.with_network == 2) {
+        if (c.height % 8 || c.width % 8) return fail("LMFFNet needs height and width to be multiples of 8");
+        return c.max_batch >= 1 ? 0 : fail("max_batch must be >= 1");
+    }
+    if (c.max_batch < 1) return fail("max_batch must be >= 1");
+    if (c.max_instances < 1) return fail("max_instances must be >= 1");
+    if (c.resnet_depth != 50 && c.resnet_depth != 101 && c.resnet_depth != 152) return fail("resnet_depth must be 50, 101 or 152");
+    if (c.res5_dilation != 1 && c.res5_dilation != 2 && c.res5_dilation != 4) return fail("res5_dilation must be 1, 2 or 4");
+    if (c.res5_dilation == 1) return fail("res5_dilation 1 (output stride 32) is not supported by this build");
+    if (c.error_classes < 2 || c.error_classes > 4) return fail("error_classes must be 2..4");
+    if (c.streams != 1 && c.streams != 2) return fail("streams must be 1 or 2");
+    if (c.with_network == 1 && c.convs_dim != 128 && c.convs_dim != 256) return fail("convs_dim must be 128 or 256");
+    if (c.with_network == 1 && c.head_channels != 32 && c.head_channels != 64) return fail("head_channels must be 32 or 64");
+    if (c.compute_dtype < 0 || c.compute_dtype > 3)
+        return fail("compute_dtype must be 0 (fp32 MFMA), 1 (bf16 operands), 2 (fp16 operands) or 3 (fp32 operands as 3 bf16 terms)");
+    if (c.with_network && c.hierarchical) {
+        if (c.n_levels < 1 || c.n_levels > 5) return fail("n_levels must be 1..5");
+        int seen[5] = {0, 0, 0, 0, 0};
+        for (int i = 0; i < c.n_levels; ++i) {
+            if (c.level_heads[i][0] < 0) return fail("empty hierarchy level");
+            for (int j = 0; j < 5 && c.level_heads[i][j] >= 0; ++j) {
+                const int k = c.level_heads[i][j];
+                if (k > 4) return fail("hierarchy head id out of range");
+                seen[k]++;
+            }
+        }
+        const int want[5] = {1, 1, 1, c.eee_mask_on ? 1 : 0, c.eee_boundary_on ? 1 : 0};
+        for (int k = 0; k < 5; ++k)
+            if (seen[k] != want[k]) return fail("the hierarchy must list every enabled head exactly once");
+    }
+    if (c.top_k < 1 || c.top_k > 254) return fail("top_k must be in 1..254");
+    if (c.gaussian_sigma < 1 || c.gaussian_sigma > 40) return fail("gaussian_sigma out of range");
+    return 0;
+}
+
+extern "C" {
+
+const char* quber_version(void) { return "quber-hip 0.1 (gfx950, fp32 MFMA)"; }
+
+void quber_default_config(quber_config* c) {
+    memset(c, 0, sizeof(*c));
+    c->height = 480; c->width = 640; c->max_batch = 1; c->max_instances = 64;
+    c->resnet_depth = 50; c->res5_dilation = 2; c->backbone_fusion_layers = 2; c->head_fusion_layers = 3;
+    c->error_classes = 4; c->gaussian_sigma = 10; c->nms_kernel = 7; c->top_k = 200; c->stuff_area = 2048;
+    c->min_instance_area = 512; c->label_divisor = 1000; c->with_network = 1;
+    c->eee_mask_on = 0; c->eee_boundary_on = 1; c->hierarchical = 1; c->fusion_feat = 1; c->fusion_pred = 1;
+    c->n_levels = 2;
+    c->streams = 2;
+    c->fusion_add = 0;
+    c->convs_dim = 128; c->head_channels = 32;
+    for (int i = 0; i < 5; ++i)
+        for (int j = 0; j < 5; ++j) c->level_heads[i][j] = -1;
+    c->level_heads[0][0] = 4;                                   // [[eee_boundary], [foreground, center, offset]]
+    c->level_heads[1][0] = 0; c->level_heads[1][1] = 1; c->level_heads[1][2] = 2;
+    c->center_threshold = 0.3f; c->boundary_ratio = 0.01f;
+    const float mean[6] = {103.53f, 116.28f, 123.675f, 127.5f, 127.5f, 127.5f};
+    for (int i = 0; i < 6; ++i) { c->pixel_mean[i] = mean[i]; c->pixel_std[i] = 1.f; }
+}
+
+int quber_create(const quber_config* cfg, quber_ctx** out) {
+    if (!cfg || !out) return fail("null argument");
+    if (check_cfg(*cfg)) return -1;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device available");
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return fail("hipGetDevice failed");
+    quber_ctx* c = new quber_ctx();
+    c->cfg = *cfg;
+    c->tune = quber::g_tune;          // the process defaults of this moment; quber_set_option changes this context only
+    c->device = device;
+    const int B = cfg->max_batch, H = cfg->height, W = cfg->width;
+    // Gaussian template (predictor.py:246-251): float64 exp rounded to f32
+    const int sg = cfg->gaussian_sigma, side = 6 * sg + 3, c0 = 3 * sg + 1;
+    std::vector<float> g((size_t)side * side);
+    for (int y = 0; y < side; ++y)
+        for (int x = 0; x < side; ++x)
+            g[(size_t)y * side + x] = (float)exp(-((double)((x - c0) * (x - c0)) + (double)((y - c0) * (y - c0))) / (2.0 * sg * sg));
+    Builder b(c, false);
+    c->gauss = b.upload(g);
+    c->enc_ws = b.dalloc_bytes(encode_ws_bytes(B, cfg->max_instances, H, W));
+    c->enc_bad = (int*)b.dalloc_bytes(16);
+    c->err_ws = (uint8_t*)b.dalloc_bytes(errmaps_ws_bytes(B, cfg->max_instances > 0 ? cfg->max_instances : 1, H, W));
+    c->post_ws = b.dalloc_bytes(postprocess_ws_bytes(B, H, W, cfg->top_k));
+    if (!b.err.empty()) {
+        std::string e = b.err;
+        quber_destroy(c);
+        return fail(e);
+    }
+    if (cfg->with_network) {      // the weights the plan will ask for
+        Builder dry(c, true);
+        if (cfg->with_network == 2) build_lmff(dry); else dry.build();
+    }
+    *out = c;
+    return 0;
+}
+
+void quber_destroy(quber_ctx* c) {
+    if (!c) return;
+    if (c->prof && quber::g_prof == c->prof.get()) quber::g_prof = nullptr;
+    for (hipEvent_t e : c->prof_events) (void)hipEventDestroy(e);   // nothing useful to do with a failure while tearing down
+    for (int l = 1; l < LANES; ++l) {
+        if (c->lane_fork[l]) (void)hipEventDestroy(c->lane_fork[l]);
+        if (c->lane_join[l]) (void)hipEventDestroy(c->lane_join[l]);
+        if (c->lane_stream[l]) (void)hipStreamDestroy(c->lane_stream[l]);
+    }
+    for (void* p : c->allocs) (void)hipFree(p);
+    delete c;
+}
+
+int quber_num_weights(quber_ctx* c) { return c ? (int)c->specs.size() : 0; }
+int quber_weight_spec(quber_ctx* c, int i, const char** name, int64_t* numel) {
+    if (!c || i < 0 || i >= (int)c->specs.size()) return fail("weight index out of range");
+    *name = c->specs[i].first.c_str();
+    *numel = c->specs[i].second;
+    return 0;
+}
+
+int quber_set_weight(quber_ctx* c, const char* name, const float* host, int64_t numel) {
+    if (!c || !name || !host || numel <= 0) return fail("bad argument to quber_set_weight");
+    if (c->finalized) return fail("weights already finalized");
+    c->hostw[name].assign(host, host + numel);
+    return 0;
+}
+
+int quber_finalize_weights(quber_ctx* c) {
+    if (!c) return fail("null context");
+    if (!c->cfg.with_network) return fail("context was created with with_network = 0");
+    if (c->finalized) return fail("weights already finalized");
+    quber::TuneScope tscope(&c->tune);          // the plan is shaped by THIS context's options
+    Builder b(c, false);
+    c->flops = c->wino_flops = c->wino_saved = c->wino_pad = 0.0;
+    if (c->cfg.with_network == 2) {
+        c->splitk_floats = (size_t)4 << 20;
+        c->splitk_ws = (float*)b.dalloc_bytes(sizeof(float) * c->splitk_floats);
+        build_lmff(b);
+    } else {
+        b.build();
+    }
+    if (c->wino_floats) c->wino_ws = (float*)b.dalloc_bytes(sizeof(float) * c->wino_floats);
+    if (c->lanes_built) {          // side lanes: streams, fork / join events, workspaces sized for LANE_BATCH frames
+        c->lane_splitk_floats = c->splitk_floats;       // as large as the caller's stream's (160 MiB): a launch picks the same split on a lane as off it
+        for (int l = 1; l < LANES; ++l) {
+            QB_CHECK(hipStreamCreateWithFlags(&c->lane_stream[l], hipStreamNonBlocking));
+            QB_CHECK(hipEventCreateWithFlags(&c->lane_fork[l], hipEventDisableTiming));
+            QB_CHECK(hipEventCreateWithFlags(&c->lane_join[l], hipEventDisableTiming));
+            c->lane_splitk_ws[l] = (float*)b.dalloc_bytes(sizeof(float) * c->lane_splitk_floats);
+            if (c->lane_wino_floats[l]) c->lane_wino_ws[l] = (float*)b.dalloc_bytes(sizeof(float) * c->lane_wino_floats[l]);
+        }
+    }
+    if (!b.err.empty()) {
+        c->ops.clear();
+        return fail(b.err);
+    }
+    QB_CHECK(hipDeviceSynchronize());
+    c->hostw.clear();
+    c->finalized = true;
+    return 0;
+}
+
+double quber_forward_flops(quber_ctx* c) { return c ? c->flops : 0.0; }
+double quber_forward_flops_executed(quber_ctx* c) {
+    if (!c) return 0.0;
+    // a layer planned as Winograd F(m x m,3x3) multiplies (m+2)^2 times per m x m output tile and channel pair (padded tiles included) instead of 9 m^2
+    return c->flops - c->wino_saved;
+}
+double quber_forward_flops_padding(quber_ctx* c) { return c ? c->wino_pad : 0.0; }
+void quber_set_tuning(int32_t key, int32_t value) {
+    // process defaults: copied by every context created afterwards (quber_create) and used by the stand-alone quber_op_* ops; contexts that already exist keep theirs (quber_set_option)
+    if (op_set_tuning(key, value)) return;       // keys 2, 11, 12, 26: state of the stand-alone ops
+    (void)quber::tuning_set(quber::g_tune, key, value);
+}
+
+int quber_set_option(quber_ctx* c, int32_t key, int32_t value) {
+    if (!c) return fail("null context");
+    if (quber::tuning_plan_time(key) && c->finalized) return fail("option " + std::to_string(key) + " shapes the plan: set it before quber_finalize_weights");
+    if (!quber::tuning_set(c->tune, key, value)) return fail("unknown option key " + std::to_string(key));
+    return 0;
+}
+
+int quber_get_option(quber_ctx* c, int32_t key, int32_t* value) {
+    if (!c || !value) return fail("null argument");
+    int* f = quber::tuning_field(c->tune, key);
+    if (!f) return fail("unknown option key " + std::to_string(key));
+    *value = *f;
+    return 0;
+}
+
+#ifdef WF_STAMPS
+int quber_wf_read_stamps(unsigned long long* dst, int n) { return quber::wf_read_stamps(dst, n); }
+#endif
+#ifdef H8_STAMPS
+int quber_h8_read_stamps(unsigned long long* dst, int n) { return quber::h8_read_stamps(dst, n); }
+#endif
+#ifdef X8_STAMPS
+int quber_x8_read_stamps(unsigned long long* dst, int n) { return quber::x8_read_stamps(dst, n); }
+#endif
+#ifdef PK_STAMPS
+int quber_pk_read_stamps(unsigned long long* dst, int n) { return quber::pk_read_stamps(dst, n); }
+int quber_pk_read_span(unsigned long long* dst, int n) { return quber::pk_read_span(dst, n); }
+#endif
+
+int32_t quber_debug_persistent_segments(int32_t tiles, int32_t blocks, int32_t k_slices, int32_t min_share, int32_t block, int32_t* out4, int32_t cap) {
+    return quber::conv_persistent_segments(tiles, blocks, k_slices, min_share, block, out4, cap);
+}
+int32_t quber_debug_persistent_fixup(int32_t tiles, int32_t blocks, int32_t k_slices, int32_t min_share, int32_t xcd, int32_t j, int32_t* tile, int32_t* slots, int32_t cap) {
+    return quber::conv_persistent_fixup(tiles, blocks, k_slices, min_share, xcd, j, tile, slots, cap);
+}
+
+int quber_profile_begin(quber_ctx* c) {
+    if (!c) return fail("null context");
+    if (!c->prof) c->prof.reset(new quber::Profiler());
+    c->prof->recs.clear(); c->prof->sums.clear(); c->prof->used = 0;
+    quber::g_prof = c->prof.get();
+    return 0;
+}
+
+int quber_profile_end(quber_ctx* c, void* stream) {
+    if (!c || !c->prof || quber::g_prof != c->prof.get()) return fail("quber_profile_end without quber_profile_begin");
+    quber::g_prof = nullptr;
+    QB_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    quber::Profiler& p = *c->prof;
+    p.sums.assign(p.tags.size(), quber::StageSum());
+    for (size_t i = 0; i < p.tags.size(); ++i) p.sums[i].name = p.tags[i];
+    for (const quber::ProfRec& r : p.recs) {
+        float ms = 0.f;
+        QB_CHECK(hipEventElapsedTime(&ms, r.e0, r.e1));
+        quber::StageSum& s = p.sums[r.tag];
+        s.ms += ms; s.bytes += r.bytes; s.flops += r.flops; s.launches += 1;
+    }
+    return 0;
+}
+
+int quber_profile_num_stages(quber_ctx* c) { return (c && c->prof) ? (int)c->prof->sums.size() : 0; }
+
+int quber_profile_stage(quber_ctx* c, int i, const char** name, double* ms, double* bytes, double* flops, int32_t* launches) {
+    if (!c || !c->prof || i < 0 || i >= (int)c->prof->sums.size()) return fail("stage index out of range");
+    const quber::StageSum& s = c->prof->sums[i];
+    *name = s.name.c_str(); *ms = s.ms; *bytes = s.bytes; *flops = s.flops; *launches = s.launches;
+    return 0;
+}
+
+int quber_num_ops(quber_ctx* c) { return c ? (int)c->ops.size() : 0; }
+int quber_op_info(quber_ctx* c, int i, const char** name, int32_t* kind, double* flops, int32_t* launches) {
+    if (!c || i < 0 || i >= (int)c->ops.size()) return fail("op index out of range");
+    const Op& o = c->ops[i];
+    *name = o.name.c_str(); *kind = o.kind; *flops = o.flops; *launches = o.launches;
+    return 0;
+}
+
+int quber_encode_initial_masks(quber_ctx* c, const uint8_t* masks, int32_t batch, int32_t n, float* out, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n > c->cfg.max_instances) return fail("more initial masks than max_instances");
+    if (!masks && n > 0) return fail("null masks");
+    return launch_encode(masks, batch, n, c->cfg.height, c->cfg.width, c->gauss, c->cfg.gaussian_sigma, c->cfg.encode_legacy_f32, c->enc_ws, out, (hipStream_t)stream);
+}
+
+int quber_encode_label_map(quber_ctx* c, const int32_t* labels, int32_t batch, int32_t n, float* out, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n > c->cfg.max_instances) return fail("more instances than max_instances");
+    if (!labels && n > 0) return fail("null label map");
+    return launch_encode_labels(labels, batch, n, c->cfg.height, c->cfg.width, c->gauss, c->cfg.gaussian_sigma, c->cfg.encode_legacy_f32, c->enc_ws, out, c->enc_bad, (hipStream_t)stream);
+}
+
+int64_t quber_workspace_bytes(quber_ctx* c) { return c ? (int64_t)c->alloc_bytes : 0; }
+
+int quber_explicit_error_maps(quber_ctx* c, const uint8_t* init, int32_t n_init, const uint8_t* gt, int32_t n_gt, int32_t batch, uint8_t* out, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    const int H = c->cfg.height, W = c->cfg.width;
+    // util.py:80-83: dilation = max(1, int(round(ratio * diag)))   (Python round = half to even)
+    int d = (int)rint((double)c->cfg.boundary_ratio * sqrt((double)H * H + (double)W * W));
+    if (d < 1) d = 1;
+    return launch_errmaps(init, n_init, gt, n_gt, batch, c->cfg.max_instances > 0 ? c->cfg.max_instances : 1, H, W, d, c->err_ws, out, (hipStream_t)stream);
+}
+
+// The shared preamble of quber_forward / quber_forward_profiled: checks, this context's options for every launcher (`scope`, until the caller returns), the pointers
+// the plan's ops read, the preprocess kernel.  0 = go on, < 0 = error, 1 = an LMFFNet context that the caller runs itself (lmff_own; nothing stored or launched).
+static int forward_begin(quber_ctx* c, const char* who, std::optional<quber::TuneScope>& scope, const uint8_t* bgr, const uint8_t* depth,
+                         const float* offs, int batch, float* logits, bool lmff_own, bool rest_ok, const char* null_msg, hipStream_t st) {
+    if (check_batch(c, batch)) return -1;
+    if (!c->finalized) return fail(std::string(who) + " before quber_finalize_weights");
+    scope.emplace(&c->tune);
+    if (lmff_own && c->cfg.with_network == 2) return 1;
+    if (!bgr || (!depth && c->cfg.streams == 2) || !offs || !logits || !rest_ok) return fail(null_msg);
+    c->cur_out = logits;
+    c->cur_bgr = bgr; c->cur_depth = depth; c->cur_off = offs;
+    return c->stem_fused ? 0 : launch_preprocess(bgr, depth, offs, c->X, batch, c->cfg.max_batch, c->cfg.height, c->cfg.width,
+                                                 c->cfg.pixel_mean, c->cfg.pixel_std, c->cfg.streams, st);
+}
+
+int quber_forward(quber_ctx* c, const uint8_t* bgr, const uint8_t* depth, const float* offs, int32_t batch, float* logits, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    std::optional<quber::TuneScope> tscope;
+    int rc = forward_begin(c, "quber_forward", tscope, bgr, depth, offs, batch, logits, true, true, "null tensor", st);
+    if (rc == 1) {   // LMFFNet: (bgr, depth) -> 3 class planes; `offs` is unused
+        if (!bgr || !depth || !logits) return fail("null tensor");
+        c->cur_out = logits;
+        int r2 = launch_lmff_preprocess(bgr, depth, (long)batch * c->cfg.height * c->cfg.width, c->X.p, st);
+        for (size_t i = 0; !r2 && i < c->ops.size(); ++i)
+            if (!c->ops[i].ctl) r2 = c->ops[i].run(batch, st);
+        return r2;
+    }
+    if (rc) return rc;
+    // side lanes: at small batches the independent branches of the plan (Builder::fork / join) run on streams of the context
+    c->lanes_on = c->lanes_built && tune().lanes && batch <= (c->cfg.compute_dtype == 0 || c->cfg.compute_dtype == 3 ? LANE_BATCH_F32 : LANE_BATCH) && c->lane_stream[1] != nullptr &&
+                  quber::g_prof == nullptr;
+    auto lane_used = [&](int l) { return c->lanes_on && l > 0; };
+    for (auto& op : c->ops) {
+        if (op.ctl == 1) {
+            if (lane_used(op.lane)) {
+                QB_CHECK(hipEventRecord(c->lane_fork[op.lane], st));
+                QB_CHECK(hipStreamWaitEvent(c->lane_stream[op.lane], c->lane_fork[op.lane], 0));
+            }
+            continue;
+        }
+        if (op.ctl == 2) {
+            if (lane_used(op.lane)) {
+                QB_CHECK(hipEventRecord(c->lane_join[op.lane], c->lane_stream[op.lane]));
+                QB_CHECK(hipStreamWaitEvent(st, c->lane_join[op.lane], 0));
+            }
+            continue;
+        }
+        c->lane_now = lane_used(op.lane) ? op.lane : 0;
+        rc = op.run(batch, c->lane_now ? c->lane_stream[op.lane] : st);
+        if (rc) return rc;
+    }
+    c->lane_now = 0;
+    c->lanes_on = false;
+    return 0;
+}
+
+int quber_forward_profiled(quber_ctx* c, const uint8_t* bgr, const uint8_t* depth, const float* offs, int32_t batch,
+                           float* logits, void* stream, double* kind_ms, int32_t* kind_launches) {
+    hipStream_t st = (hipStream_t)stream;
+    std::optional<quber::TuneScope> tscope;
+    int rc = forward_begin(c, "quber_forward_profiled", tscope, bgr, depth, offs, batch, logits, false, kind_ms && kind_launches, "null argument", st);
+    if (rc) return rc;
+    const size_t n = c->ops.size();
+    if (c->prof_events.size() < 2 * n) {
+        const size_t old = c->prof_events.size();
+        c->prof_events.resize(2 * n);
+        for (size_t i = old; i < 2 * n; ++i) QB_CHECK(hipEventCreate(&c->prof_events[i]));
+    }
+    c->lanes_on = false;          // one stream: every op in plan order
+    for (size_t i = 0; i < n; ++i) {
+        QB_CHECK(hipEventRecord(c->prof_events[2 * i], st));
+        if (!c->ops[i].ctl) {
+            rc = c->ops[i].run(batch, st);
+            if (rc) return rc;
+        }
+        QB_CHECK(hipEventRecord(c->prof_events[2 * i + 1], st));
+    }
+    QB_CHECK(hipStreamSynchronize(st));
+    for (int k = 0; k < OP_KINDS; ++k) { kind_ms[k] = 0.0; kind_launches[k] = 0; }
+    for (size_t i = 0; i < n; ++i) {
+        float ms = 0.f;
+        QB_CHECK(hipEventElapsedTime(&ms, c->prof_events[2 * i], c->prof_events[2 * i + 1]));
+        kind_ms[c->ops[i].kind] += ms;
+        kind_launches[c->ops[i].kind] += 1;
+    }
+    return 0;
+}
+
+int quber_postprocess(quber_ctx* c, const float* logits, int32_t n_planes, int32_t batch, float* pan, int32_t* count,
+                      float* labels, float* scores, float* boxes, int32_t* centers, int32_t* ncenters, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    PostCfg pc;
+    pc.threshold = c->cfg.center_threshold; pc.nms_kernel = c->cfg.nms_kernel; pc.top_k = c->cfg.top_k;
+    pc.stuff_area = c->cfg.stuff_area; pc.min_area = c->cfg.min_instance_area; pc.label_divisor = c->cfg.label_divisor;
+    pc.cap = c->cfg.top_k;
+    return launch_postprocess(logits, n_planes, batch, c->cfg.height, c->cfg.width, pc, c->post_ws, pan, count, labels,
+                              scores, boxes, centers, ncenters, (hipStream_t)stream);
+}
+
+int quber_extract_masks(quber_ctx* c, const float* pan, const float* labels, int32_t batch, int32_t max_inst,
+                        uint8_t* masks, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    return launch_extract_masks(pan, labels, batch, c->cfg.height, c->cfg.width, c->cfg.top_k, max_inst, masks,
+                                (hipStream_t)stream);
+}
+
+int quber_tta_flip_inputs(quber_ctx* c, uint8_t* bgr, uint8_t* depth, uint8_t* masks, int32_t batch, int32_t n, void* stream) {
+    if (check_tta_batch(c, batch)) return -1;
+    if (n < 0 || n > c->cfg.max_instances) return fail("initial masks outside 0..max_instances");
+    if (!bgr || (!masks && n > 0)) return fail("null tensor");
+    const int H = c->cfg.height, W = c->cfg.width;
+    const long hw = (long)H * W;
+    hipStream_t st = (hipStream_t)stream;
+    if (launch_tta_flip_u8(bgr, bgr + batch * hw * 3, batch, H, W, 3, st)) return -1;
+    if (depth && launch_tta_flip_u8(depth, depth + batch * hw * 3, batch, H, W, 3, st)) return -1;
+    if (n > 0 && launch_tta_flip_u8(masks, masks + (long)batch * n * hw, (long)batch * n, H, W, 1, st)) return -1;
+    return 0;
+}
+
+int quber_tta_merge(quber_ctx* c, const float* logits2, int32_t n_planes, int32_t batch, float* out, void* stream) {
+    if (check_tta_batch(c, batch)) return -1;
+    if (n_planes < 4) return fail("test-time augmentation: fewer than 4 logit planes");
+    if (!logits2 || !out) return fail("null tensor");
+    return launch_tta_merge(logits2, n_planes, batch, c->cfg.height, c->cfg.width, out, (hipStream_t)stream);
+}
+
+// ---- the predicted error maps (errhead.hip); usable on a context without a network ----
+int quber_error_decode(quber_ctx* c, const float* logits, int32_t n_planes, int32_t first_plane, int32_t classes, int32_t batch,
+                       uint8_t* classes_out, uint32_t* hist, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (!logits || !classes_out) return fail("null tensor");
+    return launch_error_decode(logits, n_planes, first_plane, classes, batch, c->cfg.height, c->cfg.width, classes_out, hist,
+                               (hipStream_t)stream);
+}
+
+int quber_error_mask_hist(quber_ctx* c, const uint8_t* classes_map, const uint8_t* masks, int32_t batch, int32_t n, int32_t classes,
+                          uint32_t* out, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n < 0 || n > c->cfg.max_instances) return fail("initial masks outside 0..max_instances");
+    if (n == 0) return 0;
+    if (!classes_map || !masks || !out) return fail("null tensor");
+    return launch_error_mask_hist(classes_map, masks, batch, n, classes, c->cfg.height, c->cfg.width, out, (hipStream_t)stream);
+}
+
+int quber_error_score(quber_ctx* c, const uint8_t* classes_map, const uint8_t* explicit_maps, int32_t kind, int32_t error_type,
+                      int32_t classes, int32_t batch, uint64_t* table, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (!classes_map || !explicit_maps || !table) return fail("null tensor");
+    return launch_error_score(classes_map, explicit_maps, kind, error_type, classes, batch, c->cfg.height, c->cfg.width,
+                              (unsigned long long*)table, (hipStream_t)stream);
+}
+
+int quber_error_overlay(quber_ctx* c, const uint8_t* bgr, const uint8_t* classes_map, int32_t batch, uint32_t color0, uint32_t color1,
+                        uint32_t color2, uint32_t color3, uint8_t* out, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (!bgr || !classes_map || !out) return fail("null tensor");
+    const unsigned colors[4] = {color0, color1, color2, color3};
+    return launch_error_overlay(bgr, classes_map, batch, c->cfg.height, c->cfg.width, colors, out, (hipStream_t)stream);
+}
+
+// ---- iterative refinement (iterate.hip); usable on a context without a network ----
+int quber_relabel_panoptic(quber_ctx* c, const float* panoptic, const float* labels, const int32_t* count, int32_t batch, int32_t mirror,
+                           int32_t* ids, void* stream) {
+    if (mirror ? check_tta_batch(c, batch) : check_batch(c, batch)) return -1;
+    if (!panoptic || !labels || !count || !ids) return fail("null tensor");
+    return launch_relabel_panoptic(panoptic, labels, count, batch, c->cfg.top_k, mirror != 0, c->cfg.height, c->cfg.width, ids,
+                                   (hipStream_t)stream);
+}
+
+int quber_overlap_masks(quber_ctx* c, const uint8_t* masks, const int32_t* ids, int32_t batch, int32_t n_masks, int32_t n_ids,
+                        uint32_t* table, uint32_t* area, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_masks < 0 || n_masks > c->cfg.max_instances) return fail("initial masks outside 0..max_instances");
+    if (n_ids < 0 || n_ids > 254) return fail("n_ids outside 0..254");
+    if (!ids || (n_masks > 0 && (!masks || !table))) return fail("null tensor");
+    return launch_overlap_masks(masks, ids, batch, n_masks, n_ids, c->cfg.height, c->cfg.width, table, area, (hipStream_t)stream);
+}
+
+int quber_overlap_ids(quber_ctx* c, const int32_t* a, const int32_t* b, int32_t batch, int32_t n_a, int32_t n_b, uint32_t* table,
+                      void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_a < 0 || n_a > 254 || n_b < 0 || n_b > 254) return fail("n_a / n_b outside 0..254");
+    if (!a || !b || !table) return fail("null tensor");
+    return launch_overlap_ids(a, b, batch, n_a, n_b, c->cfg.height, c->cfg.width, table, (hipStream_t)stream);
+}
+
+int64_t quber_contingency_workspace_bytes(int32_t cap) { return (int64_t)contingency_ws_bytes(cap); }
+
+int quber_label_contingency(const int32_t* pred, const int32_t* gt, int64_t n_pixels, int32_t cap, void* workspace,
+                            void* stream) {
+    if (!pred || !gt || !workspace || n_pixels < 1 || cap < 1 || cap > 1024) return fail("bad argument to quber_label_contingency");
+    return launch_contingency(pred, gt, n_pixels, cap, workspace, (hipStream_t)stream);
+}
+
+int64_t quber_boundary_workspace_bytes(int32_t h, int32_t w, int32_t n_masks) {
+    return (int64_t)boundary_ws_bytes(h, w, n_masks);
+}
+
+int quber_boundary_overlap(const int32_t* pred, const int32_t* gt, int32_t h, int32_t w, const int32_t* labels, int32_t n_pred,
+                           int32_t n_gt, int32_t bound_pix, void* workspace, uint32_t* out, void* stream) {
+    if (!pred || !gt || !labels || !workspace || !out || h < 1 || w < 1) return fail("bad argument to quber_boundary_overlap");
+    return launch_boundary_overlap(pred, gt, h, w, labels, n_pred, n_gt, bound_pix, workspace, out, (hipStream_t)stream);
+}
+
+int quber_foreground_filter(const float* fg_logits, int32_t n_classes, int32_t fg_class, const uint8_t* masks,
+                            int32_t batch, int32_t n_masks, int64_t hw, uint8_t* fg_mask, uint64_t* counts, void* stream) {
+    if (!fg_logits || !fg_mask || batch < 1 || hw < 1 || n_classes < 2) return fail("bad argument to quber_foreground_filter");
+    hipStream_t st = (hipStream_t)stream;
+    int rc = launch_argmax_fg(fg_logits, batch, hw, n_classes, fg_class, fg_mask, st);
+    if (rc || n_masks == 0) return rc;
+    if (!masks || !counts) return fail("null masks / counts");
+    return launch_mask_overlap(masks, fg_mask, batch, n_masks, hw, (unsigned long long*)counts, st);
+}
+
+int quber_normalize_depth(const void* depth, int32_t is_float32, int64_t n_pixels, double min_val, double max_val,
+                          uint8_t* out3, uint8_t* zero, void* stream) {
+    if (!depth || !out3 || n_pixels <= 0) return fail("bad argument to quber_normalize_depth");
+    if (!(max_val > min_val)) return fail("normalize_depth: max_val must exceed min_val");
+    return launch_normalize_depth(depth, is_float32, n_pixels, min_val, max_val, out3, zero, (hipStream_t)stream);
+}
+
+int quber_inpaint_telea_u8(const uint8_t* host_img, const uint8_t* host_mask, int32_t h, int32_t w, int32_t radius,
+                           uint8_t* host_out) {
+    return inpaint_telea_u8_host(host_img, host_mask, h, w, radius, host_out);
+}
+
+int quber_inpaint_depth_u8(const uint8_t* host_depth3, int32_t h, int32_t w, int32_t kernel, uint8_t* host_out3) {
+    return inpaint_depth_u8_host(host_depth3, h, w, kernel, host_out3);
+}
+
+int64_t quber_inpaint_depth_workspace_bytes(int32_t batch, int32_t h, int32_t w) { return (int64_t)inpaint_depth_ws_bytes(batch, h, w); }
+
+int quber_inpaint_depth_device(const uint8_t* dev_depth3, int32_t batch, int32_t h, int32_t w, int32_t kernel, void* dev_workspace,
+                               int64_t workspace_bytes, uint8_t* dev_out3, void* stream) {
+    return launch_inpaint_depth(dev_depth3, batch, h, w, kernel, dev_workspace, (size_t)workspace_bytes, dev_out3, (hipStream_t)stream);
+}
+
+int quber_resize_u8(const uint8_t* src, int32_t src_h, int32_t src_w, int32_t channels, uint8_t* dst, int32_t dst_h,
+                    int32_t dst_w, int32_t linear, void* stream) {
+    if (!src || !dst) return fail("bad argument to quber_resize_u8");
+    return launch_resize_u8(src, src_h, src_w, channels, dst, dst_h, dst_w, linear, (hipStream_t)stream);
+}
+
+int quber_debug_tensor(quber_ctx* c, const char* name, float** ptr, int32_t* dims4, int32_t* cs) {
+    if (!c || !name) return fail("null argument");
+    auto it = c->taps.find(name);
+    if (it == c->taps.end()) return fail(std::string("no intermediate named '") + name + "'");
+    *ptr = it->second.p;
+    dims4[0] = it->second.B; dims4[1] = it->second.H; dims4[2] = it->second.W; dims4[3] = it->second.C;
+    *cs = it->second.cs;
+    return 0;
+}
+int32_t quber_debug_tensor_elem_size(quber_ctx* c, const char* name) {
+    if (!c || !name) return 0;
+    auto it = c->taps.find(name);
+    return it == c->taps.end() ? 0 : it->second.es;
+}
+
+}  // extern "C"

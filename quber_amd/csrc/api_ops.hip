@@ -1,0 +1,215 @@
+// Stand-alone ops of the C ABI (tests / micro-benchmarks): single launches without a context, on the process defaults of the options.
+#include "plan.h"
+
+using namespace quber;
+
+static float* g_op_ws = nullptr;
+static int g_op_skip_rows = 0;
+static int g_op_bf16 = 0;
+static const size_t g_op_ws_floats = (size_t)256 << 20;   // 1 GiB, test harness only
+static int g_op_wino_reuse = 0;   // key 26
+
+bool quber::op_set_tuning(int key, int value) {
+    if (key == 2) {   // stand-alone conv op: allocate (value != 0) or drop the split-K workspace
+        if (value && !g_op_ws) {
+            if (hipMalloc((void**)&g_op_ws, sizeof(float) * g_op_ws_floats) != hipSuccess) g_op_ws = nullptr;
+        } else if (!value && g_op_ws) {
+            (void)hipFree(g_op_ws);
+            g_op_ws = nullptr;
+        }
+        return true;
+    }
+    if (key == 26) { g_op_wino_reuse = value; return true; }   // timing harness: quber_op_conv3x3_winograd reuses the transformed filters its previous call left in u / ws
+    if (key == 12) { g_op_bf16 = value; return true; }         // stand-alone conv ops: 1 = bf16, 2 = fp16 operands, 3 = fp32 as 3 bf16 terms; fp32 accumulation
+    if (key == 11) { g_op_skip_rows = value; return true; }    // stand-alone conv op: tap-major K order with padded filter rows skipped (dilated 3x3)
+    return false;
+}
+
+// the geometry fields of a dense single-group launch on unsliced tensors (K = k * k * cin; the callers pad it)
+static void conv_geometry(ConvP& p, int B, int h, int w, int cin, int cout, int k, int stride, int pad, int dil) {
+    p.B = B; p.H = h; p.W = w; p.Cin = cin; p.in_cs = cin;
+    p.OH = (h + 2 * pad - dil * (k - 1) - 1) / stride + 1;
+    p.OW = (w + 2 * pad - dil * (k - 1) - 1) / stride + 1;
+    p.Cout = cout; p.out_cs = cout; p.K = k * k * cin;
+    p.kh = k; p.kw = k; p.stride = stride; p.pad = pad; p.dil = dil;
+    p.M = B * p.OH * p.OW; p.ohw = p.OH * p.OW;
+}
+
+// bf16x3 mode: the pre-split weight planes conv_x8.hip reads - a grow-only scratch of the process (test harness), one per op
+struct PlaneScratch {
+    void* planes = nullptr;
+    size_t cap = 0;
+    int split(const float* w, long n, ConvP& p, const char* who, hipStream_t st) {
+        const size_t need = (size_t)n * 3 * sizeof(unsigned short);
+        if (need > cap) {
+            if (planes) (void)hipFree(planes);
+            planes = nullptr; cap = 0;
+            if (hipMalloc(&planes, need) != hipSuccess) return fail(std::string(who) + ": cannot allocate the bf16x3 weight planes");
+            cap = need;
+        }
+        const int rc = launch_split_bf16x3(w, n, planes, st);
+        if (rc) return rc;
+        p.w3 = planes; p.w3_plane = n;
+        return 0;
+    }
+};
+
+static View mkview(const float* p, int B, int h, int w, int c) {
+    View v;
+    v.p = const_cast<float*>(p); v.B = B; v.H = h; v.W = w; v.C = c; v.cs = c; v.gs = 0;
+    return v;
+}
+
+extern "C" {
+
+__global__ void pack_oihw_kernel(const float* __restrict__ w, int O, int I, int k, int Kpad, int kmode, float* __restrict__ out) {
+    const long total = (long)O * Kpad;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int o = i / Kpad, kk = i % Kpad;
+        float v = 0.f;
+        if (kk < k * k * I) {
+            int tap, ci;
+            if (kmode) {
+                const int cb = kk / (k * k * 32), rem = kk % (k * k * 32);
+                tap = rem / 32;
+                ci = cb * 32 + rem % 32;
+            } else {
+                tap = kk / I;
+                ci = kk % I;
+            }
+            v = w[((long)o * I + ci) * k * k + tap];
+        }
+        out[i] = v;
+    }
+}
+
+int quber_op_conv2d(const float* x, int32_t B, int32_t h, int32_t w, int32_t cin, const float* w_oihw, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t dil,
+                    const float* scale, const float* shift, const float* residual, int32_t relu, float* packed, float* y, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const int Kpad = (k * k * cin + 31) / 32 * 32;
+    const bool skip_rows = g_op_skip_rows && k == 3 && stride == 1 && dil > 1 && cin % 32 == 0;
+    const int kmode = (k > 1 && cin % 32 == 0 && !skip_rows) ? 1 : 0;
+    hipLaunchKernelGGL(pack_oihw_kernel, dim3(256), dim3(256), 0, st, w_oihw, cout, cin, k, Kpad, kmode, packed);
+    ConvP p{};
+    p.in = x; p.w = packed; p.scale = scale; p.shift = shift; p.res = residual; p.out = y;
+    conv_geometry(p, B, h, w, cin, cout, k, stride, pad, dil);
+    p.res_cs = cout; p.Kpad = Kpad; p.relu = relu;
+    p.kmode = kmode; p.skip_rows = skip_rows;
+    p.bf16 = g_op_bf16; p.w_gs = 0; p.ss_gs = 0;
+    // the stand-alone op splits K only when the test harness asked for a workspace (tuning key 2)
+    p.ws = g_op_ws; p.ws_floats = g_op_ws ? g_op_ws_floats : 0;
+    if (g_op_bf16 == 3 && k == 1 && tune().x8) {
+        static PlaneScratch scratch;
+        const int rc = scratch.split(packed, (long)cout * Kpad, p, "conv2d", st);
+        if (rc) return rc;
+    }
+    return launch_conv(p, 1, st);
+}
+
+// the fp16 data path's 1x1 convolution on fp16 tensors (x, w [cout][cin], residual, y: fp16 in HBM; scale / shift fp32)
+int quber_op_conv1x1_f16(const void* x, int32_t B, int32_t h, int32_t w, int32_t cin, const void* w_oi, int32_t cout,
+                         const float* scale, const float* shift, const void* residual, int32_t relu, void* y, void* stream) {
+    if (cin % 64) return fail("conv1x1_f16: cin must be a multiple of 64");
+    ConvP p{};
+    p.in = (const float*)x; p.w = (const float*)w_oi; p.scale = scale; p.shift = shift; p.res = (const float*)residual; p.out = (float*)y;
+    conv_geometry(p, B, h, w, cin, cout, 1, 1, 0, 1);
+    p.res_cs = cout; p.Kpad = cin; p.relu = relu;
+    p.bf16 = 2; p.es = 2;
+    return launch_conv(p, 1, (hipStream_t)stream);
+}
+
+int quber_op_conv2d_f16(const void* x, int32_t B, int32_t h, int32_t w, int32_t cin, const void* w_packed, int32_t cout, int32_t ksize, int32_t stride, int32_t pad, int32_t dil,
+                        int32_t kmode, const float* scale, const float* shift, const void* residual, int32_t relu, double* gn_sums, int32_t gn_groups, void* y, void* stream) {
+    if (cin % 8 || (kmode && cin % 64)) return fail("conv2d_f16: cin must be a multiple of 8 (slice-major K order: of 64)");
+    if (ksize < 1 || stride < 1 || dil < 1 || pad < 0) return fail("conv2d_f16: bad geometry");
+    ConvP p{};
+    p.in = (const float*)x; p.w = (const float*)w_packed; p.scale = scale; p.shift = shift; p.res = (const float*)residual; p.out = (float*)y;
+    conv_geometry(p, B, h, w, cin, cout, ksize, stride, pad, dil);
+    if (p.OH < 1 || p.OW < 1) return fail("conv2d_f16: empty output");
+    p.res_cs = cout; p.Kpad = (p.K + 63) / 64 * 64; p.relu = relu;      // (filter rows zero-filled up to Kpad)
+    p.kmode = kmode; p.bf16 = 2; p.es = 2;
+    p.w_gs = (long)cout * p.Kpad; p.ss_gs = cout;
+    if (gn_sums) {
+        if (gn_groups < 1 || cout % gn_groups) return fail("conv2d_f16: channels must divide into the norm groups");
+        p.gn_sum = gn_sums; p.gn_groups = gn_groups; p.gn_cpg = cout / gn_groups;
+    }
+    return launch_conv(p, 1, (hipStream_t)stream);
+}
+
+// y: [B][oh][ow][mid], x: [B][h2][w2][cin] (sampled at `stride`), w: [cout][mid + cin] (BN scales already folded in),
+// out = relu?(y . w[:, :mid] + x[::stride, ::stride] . w[:, mid:] + shift)
+int quber_op_conv1x1_dual(const float* y, const float* x, int32_t B, int32_t oh, int32_t ow, int32_t mid, int32_t h2, int32_t w2, int32_t cin, int32_t stride,
+                          const float* w, const float* shift, const float* ones, int32_t cout, int32_t relu, float* out, void* stream) {
+    ConvP p{};
+    p.in = y; p.in2 = x; p.w = w; p.scale = ones; p.shift = shift; p.out = out;
+    conv_geometry(p, B, oh, ow, mid, cout, 1, 1, 0, 1);
+    p.H2 = h2; p.W2 = w2; p.in2_cs = cin; p.stride2 = stride; p.K1 = mid;
+    p.K = mid + cin; p.Kpad = mid + cin; p.relu = relu;
+    p.bf16 = g_op_bf16; p.ss_gs = 0;
+    p.ws = g_op_ws; p.ws_floats = g_op_ws ? g_op_ws_floats : 0;
+    if (g_op_bf16 == 3 && tune().x8) {
+        static PlaneScratch scratch;
+        const int rs = scratch.split(w, (long)cout * p.Kpad, p, "conv1x1_dual", (hipStream_t)stream);
+        if (rs) return rs;
+    }
+    const int rc = launch_conv_dual(p, 1, (hipStream_t)stream);
+    if (rc == 1) return fail("conv1x1_dual: launch not covered by the dual kernel (workspace: tuning key 2)");
+    return rc;
+}
+
+int quber_op_conv3x3_winograd(const float* x, int32_t B, int32_t h, int32_t w, int32_t cin, const float* w_oihw, int32_t cout, int32_t dil, int32_t m,
+                              const float* scale, const float* shift, int32_t relu, float* u, float* ws, int64_t ws_floats, float* y, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!winograd_eligible(3, 1, dil, dil, cin, cout)) return fail("winograd: unsupported channel counts");
+    if ((scale == nullptr) != (shift == nullptr)) return fail("winograd: scale and shift go together");
+    if (m != 2 && m != 4 && m != 6) return fail("winograd: the output tile edge is 2, 4 or 6");
+    int rc = g_op_wino_reuse ? 0 : launch_winograd_weights(w_oihw, cout, cin, m, u, st);
+    if (rc) return rc;
+    WinoP q{};
+    q.in = mkview(x, B, h, w, cin); q.out = mkview(y, B, h, w, cout);
+    q.u = u; q.scale = scale; q.shift = shift; q.ss_gs = 0; q.relu = relu; q.dil = dil; q.m = m;
+    q.dtype = g_op_bf16;
+    q.ws = ws; q.ws_floats = (size_t)ws_floats;
+    // the single-kernel form where it applies and the workspace also holds its filter order (36 * cout * cin floats)
+    if (m == 4 && tune().wino_fused && cout % 32 == 0 && (size_t)ws_floats >= (size_t)36 * cout * cin) {
+        q.uf = ws;
+        if (winograd_fused_ok(q, B, 1)) {
+            rc = winograd_fused_prepare();
+            if (rc) return rc;
+            rc = g_op_wino_reuse ? 0 : launch_winograd_fused_pack(u, cout, cin, ws, st);
+            if (rc) return rc;
+            q.ws = ws + (size_t)36 * cout * cin; q.ws_floats = (size_t)ws_floats - (size_t)36 * cout * cin;
+        } else {
+            q.uf = nullptr;
+        }
+    }
+    q.splitk_ws = g_op_ws; q.splitk_floats = g_op_ws ? g_op_ws_floats : 0;
+    return launch_conv_winograd(q, B, 1, st);
+}
+
+int quber_op_groupnorm(const float* x, int32_t B, int32_t h, int32_t w, int32_t c, int32_t groups, const float* gamma,
+                       const float* beta, float eps, int32_t relu, double* stats, float* y, void* stream) {
+    View in = mkview(x, B, h, w, c), out = mkview(y, B, h, w, c);
+    int rc = launch_gn_stats(in, B, 1, groups, stats, (hipStream_t)stream);
+    if (rc) return rc;
+    return launch_gn_apply(in, out, B, 1, groups, stats, gamma, beta, 0, eps, relu, (hipStream_t)stream);
+}
+
+int quber_op_bilinear(const float* x, int32_t B, int32_t h, int32_t w, int32_t c, int32_t oh, int32_t ow, float* y,
+                      void* stream) {
+    if (c % 4) return fail("bilinear: channels must be a multiple of 4");
+    return launch_bilinear(mkview(x, B, h, w, c), mkview(y, B, oh, ow, c), B, (hipStream_t)stream);
+}
+
+int quber_op_group_pixels(const float* logits, int32_t n_planes, int32_t batch, int32_t h, int32_t w, int32_t cap,
+                          const int32_t* centers, const int32_t* ncenters, uint8_t* ids, uint32_t* area, void* stream) {
+    if (!logits || !centers || !ncenters || !ids || !area || batch < 1 || h < 1 || w < 1) return fail("bad argument to quber_op_group_pixels");
+    return launch_group_pixels(logits, n_planes, batch, h, w, cap, centers, ncenters, ids, area, (hipStream_t)stream);
+}
+
+int quber_op_maxpool3x3s2(const float* x, int32_t B, int32_t h, int32_t w, int32_t c, float* y, void* stream) {
+    if (c % 4) return fail("maxpool: channels must be a multiple of 4");
+    return launch_maxpool3x3s2(mkview(x, B, h, w, c), mkview(y, B, (h + 1) / 2, (w + 1) / 2, c), B, 1, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -77,7 +77,7 @@ struct ConvP {
     int zones, zx1, zx2;
 };
 
-int device_cus();         // compute units of the CURRENT device (cached per device id; plan.hip), <= 0: the query failed
+int device_cus();         // compute units of the CURRENT device (cached per device id; runtime.hip), <= 0: the query failed
 void set_error(const std::string& msg);
 int fail(const std::string& msg);
 

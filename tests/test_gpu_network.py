@@ -493,7 +493,7 @@ def test_config2_1280x720_hipgraph_steady_state():
 def test_hipgraph_replay_with_side_lanes_at_larger_batches(dtype, b):
     """Since round 6's last pass the side lanes run up to 16 frames (fp32-class modes: 12): a step captured at such a batch holds the lanes'
     fork / join events inside the hipGraph (bench.py captures the step at N > 1; predict_stream users may).  The replay on NEW inputs must
-    equal the eager step bit for bit, twice over (csrc/plan.hip: event record / wait on the context's own streams are capturable)."""
+    equal the eager step bit for bit, twice over (csrc/api.hip quber_forward: event record / wait on the context's own streams are capturable)."""
     h, w, n = 240, 320, 6
     sd = arch.init_state_dict(seed=3, loud_heads=True, center_bias=-1.6)
     qc = engine.make_config(h, w, max_batch=b, max_instances=n)

@@ -4,8 +4,8 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=${1:-rXX}; O=$R/gpurun_out
 D=/tmp/quber_diag_lanes16
 rm -rf $D && mkdir -p $D/quber_amd/csrc $D/include && cp $R/include/*.h $D/include/ && cp $R/quber_amd/csrc/*.hip $R/quber_amd/csrc/*.h $R/quber_amd/csrc/Makefile $D/quber_amd/csrc/ || exit 1
-sed -i 's/constexpr int LANE_BATCH = [0-9]*;/constexpr int LANE_BATCH = 16;/' $D/quber_amd/csrc/plan.hip
-grep -q "LANE_BATCH = 16" $D/quber_amd/csrc/plan.hip || exit 1
+sed -i 's/constexpr int LANE_BATCH = [0-9]*;/constexpr int LANE_BATCH = 16;/' $D/quber_amd/csrc/plan.h
+grep -q "LANE_BATCH = 16" $D/quber_amd/csrc/plan.h || exit 1
 make -C $D/quber_amd/csrc -j16 > $D/build.log 2>&1 || { tail -20 $D/build.log; exit 1; }
 cd $R
 Q="--cpu-frames 0 --predict-calls 0 --no-split-mode --no-configs --steps 20 --warmup 5"
