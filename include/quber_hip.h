@@ -249,6 +249,39 @@ int quber_overlap_masks(quber_ctx* ctx, const uint8_t* dev_masks, const int32_t*
 int quber_overlap_ids(quber_ctx* ctx, const int32_t* dev_a, const int32_t* dev_b, int32_t batch, int32_t n_a, int32_t n_b,
                       uint32_t* dev_table, void* stream);
 
+/* Connected-component clean-up of the refined instances (csrc/cleanup.hip).  Nearest-centre grouping does not make an instance
+ * connected: stray votes leave detached specks, a dip of the foreground logit leaves a void hole.  The competing refiners of the
+ * reference clean their masks on the host - largest_connected_component(mask, connectivity=4) (eval/utilities.py:726-748, the UOIS
+ * path) and remove_small_regions(mask, 300, "holes") (eval/refiner_model.py:526-549, the SAM path); these two do it on the device.
+ * Both work on a context created with with_network = 0, take any H, W and 4-byte alignment, allocate nothing (the workspace is part of
+ * the context, sized for max_batch), use integer arithmetic for the maps (exact, order-independent) and overwrite their outputs.
+ *
+ *   dev_ids i32 [B][H][W], in place: 0 = void, 1..n_ids = instance (n_ids 0..254); a value outside 0..n_ids counts as 0 and is
+ *   written back as 0.  Frames never interact.  connectivity c = 4 or 8; keep_largest 0 or 1; the two areas >= 0.
+ *   Step 1, islands.  For every i >= 1 the c-connected components of {ids == i}, ordered by their first pixel in raster order; the
+ *     largest has the most pixels, the earlier one among equals.  keep_largest: every other component becomes 0.  Otherwise every
+ *     component of fewer than min_island_area pixels becomes 0, except that the largest always stays (min_island_area = 0: nothing
+ *     is removed).
+ *   Step 2, holes, only if max_hole_area > 0, on the map step 1 left.  A c-connected component of {ids == 0} takes the id i iff it
+ *     has fewer than max_hole_area pixels and its c-neighbours outside itself (inside the frame) all carry i.  One that touches the
+ *     frame edge can be filled; one that borders two instances, or none, cannot.  A removed speck of j inside i ends up as i.
+ *   Every instance keeps at least one pixel; the operation is idempotent.
+ *   -> dev_report u32 [B][n_ids + 1][4] (may be NULL), row i >= 1: components found in step 1, pixels removed, pixels gained by
+ *      filling, final area; row 0: void components examined in step 2, 0, pixels filled in all, final void area. */
+int quber_cleanup_ids(quber_ctx* ctx, int32_t* dev_ids, int32_t batch, int32_t n_ids, int32_t connectivity, int32_t keep_largest,
+                      int32_t min_island_area, int32_t max_hole_area, uint32_t* dev_report, void* stream);
+/* The same on the outputs of quber_postprocess, with no host read and no synchronisation: the label map is compacted on the device
+ * (the lookup of quber_relabel_panoptic, dev_count read there), cleaned with n_ids = top_k and written back - a removed pixel becomes
+ * -1, a filled one takes the instance's label - and scores and boxes are recomputed over the cleaned masks exactly as quber_postprocess
+ * defines them (mean of sigmoid(fg) over the mask in float64, times the centre plane at the truncated centre of mass; box = min /
+ * max + 1).  Labels, count and the centre list do not change (every instance keeps a pixel); the 512-px filter is not applied again.
+ *   dev_logits f32 [B][n_planes][H][W] (planes 0, 1 used); dev_panoptic f32 [B][H][W] in / out; dev_labels f32 [B][top_k], dev_count
+ *   i32 [B] in; dev_scores f32 [B][top_k], dev_boxes f32 [B][top_k][4] out; dev_report u32 [B][top_k + 1][4] (may be NULL). */
+int quber_cleanup_postprocess(quber_ctx* ctx, const float* dev_logits, int32_t n_planes, int32_t batch, float* dev_panoptic,
+                              const float* dev_labels, const int32_t* dev_count, float* dev_scores, float* dev_boxes,
+                              int32_t connectivity, int32_t keep_largest, int32_t min_island_area, int32_t max_hole_area,
+                              uint32_t* dev_report, void* stream);
+
 /* evaluation support - all pairwise overlap counts of two label maps in one pass.  Replaces the per-pair
  * np.count_nonzero loops of eval/evaluation.py:180-199 (multilabel_metrics).
  *   dev_pred, dev_gt i32 [n_pixels], label values in 0..65535, at most `cap` (<= 1024) distinct values per map

@@ -95,6 +95,7 @@ int quber_create(const quber_config* cfg, quber_ctx** out) {
     c->enc_bad = (int*)b.dalloc_bytes(16);
     c->err_ws = (uint8_t*)b.dalloc_bytes(errmaps_ws_bytes(B, cfg->max_instances > 0 ? cfg->max_instances : 1, H, W));
     c->post_ws = b.dalloc_bytes(postprocess_ws_bytes(B, H, W, cfg->top_k));
+    c->cleanup_ws = b.dalloc_bytes(cleanup_ws_bytes(B, H, W, cfg->top_k));
     if (!b.err.empty()) {
         std::string e = b.err;
         quber_destroy(c);
@@ -470,6 +471,25 @@ int quber_overlap_ids(quber_ctx* c, const int32_t* a, const int32_t* b, int32_t 
     if (n_a < 0 || n_a > 254 || n_b < 0 || n_b > 254) return fail("n_a / n_b outside 0..254");
     if (!a || !b || !table) return fail("null tensor");
     return launch_overlap_ids(a, b, batch, n_a, n_b, c->cfg.height, c->cfg.width, table, (hipStream_t)stream);
+}
+
+// ---- connected-component clean-up (cleanup.hip); usable on a context without a network ----
+int quber_cleanup_ids(quber_ctx* c, int32_t* ids, int32_t batch, int32_t n_ids, int32_t connectivity, int32_t keep_largest,
+                      int32_t min_island_area, int32_t max_hole_area, uint32_t* report, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (!ids) return fail("null tensor");
+    return launch_cleanup_ids(ids, batch, c->cfg.height, c->cfg.width, n_ids, connectivity, keep_largest, min_island_area, max_hole_area,
+                              c->cleanup_ws, report, (hipStream_t)stream);
+}
+
+int quber_cleanup_postprocess(quber_ctx* c, const float* logits, int32_t n_planes, int32_t batch, float* panoptic, const float* labels,
+                              const int32_t* count, float* scores, float* boxes, int32_t connectivity, int32_t keep_largest,
+                              int32_t min_island_area, int32_t max_hole_area, uint32_t* report, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (!logits || !panoptic || !labels || !count || !scores || !boxes) return fail("null tensor");
+    return launch_cleanup_postprocess(logits, n_planes, batch, c->cfg.height, c->cfg.width, c->cfg.top_k, c->cfg.label_divisor, panoptic, labels, count, scores,
+                                      boxes, connectivity, keep_largest, min_island_area, max_hole_area, c->cleanup_ws, report,
+                                      (hipStream_t)stream);
 }
 
 int64_t quber_contingency_workspace_bytes(int32_t cap) { return (int64_t)contingency_ws_bytes(cap); }

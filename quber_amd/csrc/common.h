@@ -279,6 +279,18 @@ int launch_errmaps(const uint8_t* init, int N, const uint8_t* gt, int Ng, int B,
                    uint8_t* ws, uint8_t* out, hipStream_t st);
 size_t errmaps_ws_bytes(int B, int Nmax, int H, int W);
 
+// per-instance sums of the post-processor (postproc.hip P4-P6): foreground probability, centre of mass, pixel count, bounding box
+struct InstStat {
+    double prob;
+    unsigned long long sy, sx;
+    unsigned cnt;
+    int xmin, ymin, xmax, ymax;
+    int pad;
+};
+int launch_post_finalize(const float* logits, int nch, int B, int H, int W, int cap, const int* count, const InstStat* stats, float* scores,
+                         float* boxes, hipStream_t st);
+int launch_post_paint_finalize(const float* logits, int nch, int B, int H, int W, int cap, int label_divisor, const int* ids, const float* lut,
+                               const int* count, float* pan, InstStat* stats, float* scores, float* boxes, hipStream_t st);
 struct PostCfg {
     float threshold;
     int nms_kernel, top_k, stuff_area, min_area, label_divisor, cap;
@@ -310,6 +322,14 @@ int launch_relabel_panoptic(const float* pan, const float* labels, const int* co
 int launch_overlap_masks(const uint8_t* masks, const int* ids, int B, int N, int n_ids, int H, int W, unsigned* table, unsigned* area,
                          hipStream_t st);
 int launch_overlap_ids(const int* a, const int* b, int B, int n_a, int n_b, int H, int W, unsigned* table, hipStream_t st);
+// connected-component clean-up (cleanup.hip): islands and holes of a compact id map, in place; the same on the label map of
+// launch_postprocess, with scores and boxes recomputed over the cleaned masks.  `ws`: cleanup_ws_bytes for a batch >= B
+int launch_cleanup_ids(int* ids, int B, int H, int W, int n_ids, int conn, int keep_largest, int min_island, int max_hole, void* ws,
+                       unsigned* report, hipStream_t st);
+int launch_cleanup_postprocess(const float* logits, int nch, int B, int H, int W, int cap, int label_divisor, float* pan, const float* labels, const int* count,
+                               float* scores, float* boxes, int conn, int keep_largest, int min_island, int max_hole, void* ws,
+                               unsigned* report, hipStream_t st);
+size_t cleanup_ws_bytes(int B, int H, int W, int cap);
 int launch_group_pixels(const float* logits, int nch, int B, int H, int W, int cap, const int* centers, const int* ncenters,
                         uint8_t* idmap, unsigned* area, hipStream_t st);
 

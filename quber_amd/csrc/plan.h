@@ -74,6 +74,7 @@ struct quber_ctx {
     void* enc_ws = nullptr;
     uint8_t* err_ws = nullptr;
     void* post_ws = nullptr;
+    void* cleanup_ws = nullptr;   // parent map, per-root tables, per-instance keys of the connected-component clean-up (cleanup.hip)
     double* gn_stats = nullptr;   // [GN_SLOTS][launch group <= 4][max_batch][32 groups][sum, sum of squares]
     int gn_slots = 0;
     float* splitk_ws = nullptr;

@@ -311,14 +311,6 @@ __global__ __launch_bounds__(256) void group_kernel(const float* __restrict__ lo
     if (harea[threadIdx.x]) atomicAdd(&area[(long)b * 256 + threadIdx.x], harea[threadIdx.x]);
 }
 
-struct InstStat {
-    double prob;
-    unsigned long long sy, sx;
-    unsigned cnt;
-    int xmin, ymin, xmax, ymax;
-    int pad;
-};
-
 // ---- P4: 512-px filter + running relabel; one block per frame ----
 __global__ void relabel_kernel(const unsigned* __restrict__ area, const int* __restrict__ ncenters, int min_area,
                                int stuff_area, int label_divisor, int cap, float* __restrict__ lut,
@@ -362,8 +354,10 @@ __global__ void relabel_kernel(const unsigned* __restrict__ area, const int* __r
 // instead of eight per foreground pixel.
 constexpr int PS_PIX = 4096;
 
+// ID: the id map's element type - uint8_t here, int for the compact ids of the clean-up (cleanup.hip), whose lut maps id -> label
+template <typename ID>
 __global__ __launch_bounds__(256) void paint_stats_kernel(const float* __restrict__ logits, int nch, int H, int W,
-                                                          int cap, int label_divisor, const uint8_t* __restrict__ idmap,
+                                                          int cap, int label_divisor, const ID* __restrict__ idmap,
                                                           const float* __restrict__ lut, float* __restrict__ pan,
                                                           InstStat* __restrict__ stats) {
     __shared__ float slut[256];
@@ -379,7 +373,7 @@ __global__ __launch_bounds__(256) void paint_stats_kernel(const float* __restric
     const long base = (long)blockIdx.x * PS_PIX;
     // the block's instance ids and foreground logits are requested up front (16 + 16 loads in flight per thread): 2048 blocks
     // walking 16 dependent load pairs each left the launch latency-bound at 6 % of the HBM rate
-    uint8_t ids[PS_PIX / 256];
+    ID ids[PS_PIX / 256];
     float lgs[PS_PIX / 256];
 #pragma unroll
     for (int it = 0; it < PS_PIX / 256; ++it) {
@@ -393,7 +387,9 @@ __global__ __launch_bounds__(256) void paint_stats_kernel(const float* __restric
         int slot = -1, y = 0, x = 0;
         double pr = 0.0;
         if (p < HW) {
-            const float lab = slut[ids[it]];
+            // (a no-op on a byte.  ID = int: an id outside 0..255 would wrap instead of mapping to -1 - the clean-up has rewritten every pixel
+            //  to 0..n_ids, n_ids <= 254, before this kernel reads its map: cc_islands_kernel in cleanup.hip)
+            const float lab = slut[(unsigned)ids[it] & 255u];
             pan[(long)b * HW + p] = lab;
             if (lab >= 0.f) {
                 slot = (int)lab - label_divisor;     // 1000 -> 0 (centre-less blob), 1001.. -> 0..
@@ -544,7 +540,7 @@ int launch_postprocess(const float* logits, int nch, int B, int H, int W, const 
     }
     {   // a10 / a11: id map + fg plane in, label map out, per-instance sums
         ProfScope prof("post_paint_stats", 9.0 * px, 0.0, st);
-        hipLaunchKernelGGL(paint_stats_kernel, dim3((int)((HW + PS_PIX - 1) / PS_PIX), B), dim3(256), 0, st, logits, nch, H, W, c.cap,
+        hipLaunchKernelGGL(paint_stats_kernel<uint8_t>, dim3((int)((HW + PS_PIX - 1) / PS_PIX), B), dim3(256), 0, st, logits, nch, H, W, c.cap,
                            c.label_divisor, idmap, lut, pan, stats);
     }
     {
@@ -552,6 +548,22 @@ int launch_postprocess(const float* logits, int nch, int B, int H, int W, const 
         hipLaunchKernelGGL(finalize_kernel, dim3(B), dim3(256), 0, st, logits, nch, H, W, c.cap, count, stats, scores,
                            boxes);
     }
+    QB_CHECK(hipGetLastError());
+    return 0;
+}
+
+// P5 + P6 alone on a compact id map (cleanup.hip: label map, scores and boxes of the cleaned masks).  lut f32 [B][256]: id -> label
+// (divisor, divisor + 1 ...: the slot is derived from it as in launch_postprocess) or -1; stats [B][cap] initialised as relabel_kernel does
+int launch_post_paint_finalize(const float* logits, int nch, int B, int H, int W, int cap, int label_divisor, const int* ids, const float* lut,
+                               const int* count, float* pan, InstStat* stats, float* scores, float* boxes, hipStream_t st) {
+    const size_t HW = (size_t)H * W;
+    hipLaunchKernelGGL(paint_stats_kernel<int>, dim3((int)((HW + PS_PIX - 1) / PS_PIX), B), dim3(256), 0, st, logits, nch, H, W, cap,
+                       label_divisor, ids, lut, pan, stats);
+    return launch_post_finalize(logits, nch, B, H, W, cap, count, stats, scores, boxes, st);
+}
+int launch_post_finalize(const float* logits, int nch, int B, int H, int W, int cap, const int* count, const InstStat* stats, float* scores,
+                         float* boxes, hipStream_t st) {
+    hipLaunchKernelGGL(finalize_kernel, dim3(B), dim3(256), 0, st, logits, nch, H, W, cap, count, stats, scores, boxes);
     QB_CHECK(hipGetLastError());
     return 0;
 }

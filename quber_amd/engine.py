@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from . import arch
+from .cleanup import Cleanup
 from .config import arch_kwargs
 
 
@@ -448,6 +449,43 @@ class Engine:
             out = torch.empty((B, n_a + 1, n_b + 1), dtype=torch.int32, device=self.device)
         assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == (B, n_a + 1, n_b + 1)
         _lib.check(self.lib.quber_overlap_ids(self.h, _ptr(a), _ptr(b), B, n_a, n_b, _ptr(out), _stream()))
+        return out
+
+    # ---- connected-component clean-up on the device (csrc/cleanup.hip; INTEGRATION.md "Connected-component clean-up") ----
+    def cleanup_ids(self, ids, n_ids, opts, report=None):
+        """ids i32 [B,H,W] in 0..n_ids (device), cleaned IN PLACE under `opts` (a Cleanup, "largest" or "holes") -> (ids, report i32
+        [B,n_ids+1,4]: per id the components found, pixels removed, pixels gained, final area; row 0: void components examined, 0,
+        pixels filled, final void area)."""
+        opts = Cleanup.parse(opts)
+        if opts is None:
+            raise ValueError("cleanup_ids needs clean-up options")
+        B = ids.shape[0]
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.shape == (B, self.H, self.W)
+        if report is None:
+            report = torch.empty((B, n_ids + 1, 4), dtype=torch.int32, device=self.device)
+        assert report.dtype == torch.int32 and report.is_contiguous() and report.shape == (B, n_ids + 1, 4)
+        _lib.check(self.lib.quber_cleanup_ids(self.h, _ptr(ids), B, n_ids, *opts.args(), _ptr(report), _stream()))
+        return ids, report
+
+    def cleanup_post(self, logits, post, opts, out=None):
+        """The clean-up on the tables of postprocess(), in place: post["panoptic"] loses the removed pixels (-1) and gains the filled
+        ones, post["scores"] / post["boxes"] are recomputed over the cleaned masks; labels, count and centres stay.  No host read.
+        -> report i32 [B,cap+1,4] (row 1 + j: the frame's j-th label); out: a tensor to write it into."""
+        opts = Cleanup.parse(opts)
+        if opts is None:
+            raise ValueError("cleanup_post needs clean-up options")
+        B, planes = logits.shape[:2]
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape[2:] == (self.H, self.W)
+        pan = post["panoptic"]
+        assert pan.dtype == torch.float32 and pan.is_contiguous() and pan.shape == (B, self.H, self.W)
+        for key, shape in (("labels", (B, self.cap)), ("scores", (B, self.cap)), ("boxes", (B, self.cap, 4))):
+            assert post[key].dtype == torch.float32 and post[key].is_contiguous() and post[key].shape == shape, key
+        assert post["count"].dtype == torch.int32 and post["count"].shape == (B,)
+        if out is None:
+            out = torch.empty((B, self.cap + 1, 4), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == (B, self.cap + 1, 4)
+        _lib.check(self.lib.quber_cleanup_postprocess(self.h, _ptr(logits), planes, B, _ptr(pan), _ptr(post["labels"]), _ptr(post["count"]),
+                                                      _ptr(post["scores"]), _ptr(post["boxes"]), *opts.args(), _ptr(out), _stream()))
         return out
 
     def extract_masks(self, post, max_inst, out=None):

@@ -78,15 +78,17 @@ def resize_shortest_edge_shape(oldh, oldw, short_edge_length=800, max_size=1333)
 class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
                  lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
-                 decode_errors=False, iterations=1, until_converged=False, track_initial=False):
+                 decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None):
         # tta: every frame and its W-mirror in one forward, logits merged on the device (MaskRefinerPredictor(tta=True))
         # decode_errors: the error heads' class maps, histograms and per-mask class counts in every output dict
         # iterations / until_converged / track_initial: the refined masks fed back for further passes on the device, early stop at a
         # fixed point (predict() only: the stream always runs the fixed count), initial_overlap / initial_index / initial_iou in every
         # output dict (INTEGRATION.md "Iterative refinement")
+        # cleanup: None, a quber_amd.cleanup.Cleanup, "largest" (the UOIS path's largest_connected_component, 4-connected) or "holes"
+        # (the SAM refiner's remove_small_regions(mask, 300, "holes")), applied on the device after post-processing
         self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, tta=tta,
                                                       decode_errors=decode_errors, iterations=iterations,
-                                                      until_converged=until_converged, track_initial=track_initial)
+                                                      until_converged=until_converged, track_initial=track_initial, cleanup=cleanup)
         self.dataset = dataset
         self.lmffnet = None
         # "host" / True (default): csrc/inpaint.hip on the calling (worker) thread; "device": csrc/inpaint_dev.hip, bit-equal, for hosts
@@ -340,5 +342,5 @@ class MaskRefinerTTA(MaskRefiner):
     """``MaskRefinerTTA(config_file, weights_file=..., dataset=...)`` of eval/un_eval_utils.py:79-81: MaskRefiner with horizontal-flip
     test-time augmentation.  predict() and predict_stream(batch=k) work as on MaskRefiner; the engine runs 2k frames."""
 
-    def __init__(self, config_file=None, weights_file=None, dataset="OSD", decode_errors=False, **kw):
-        super().__init__(config_file, weights_file=weights_file, dataset=dataset, tta=True, decode_errors=decode_errors, **kw)
+    def __init__(self, config_file=None, weights_file=None, dataset="OSD", decode_errors=False, cleanup=None, **kw):
+        super().__init__(config_file, weights_file=weights_file, dataset=dataset, tta=True, decode_errors=decode_errors, cleanup=cleanup, **kw)

@@ -18,6 +18,9 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
   * ``iterations=k``: the refined masks are fed back as the initial masks of a further pass, k passes in all, without leaving the
     device (csrc/iterate.hip; INTEGRATION.md "Iterative refinement"); ``until_converged=True`` stops as soon as a pass reproduces its
     input; ``track_initial=True`` reports which refined instance came from which initial mask.  Defaults: one pass, today's keys.
+  * ``cleanup=Cleanup(...)`` / ``"largest"`` / ``"holes"``: the connected-component clean-up the reference's competing refiners run on
+    the host (largest component, small holes), on the device right after post-processing (csrc/cleanup.hip; INTEGRATION.md
+    "Connected-component clean-up"); ``instances`` gains ``cc_components`` / ``cc_removed`` / ``cc_filled``.  Default: none, today's keys.
 There is no CPU fallback: construction fails if the HIP library or a GPU is missing.
 """
 import os
@@ -27,6 +30,7 @@ import numpy as np
 import torch
 
 from .. import arch, config as qconfig, engine as qengine
+from ..cleanup import Cleanup
 from ..structures import Boxes, Instances
 
 LABEL_DIVISOR = 1000  # maskrefiner/data/datasets/register_uoais_sim_panoptic.py:177-186
@@ -110,9 +114,12 @@ class RefinerModel:
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
     def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False, iterations=1, until_converged=False,
-                 track_initial=False):
+                 track_initial=False, cleanup=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
+        # connected-component clean-up of the instances right after every post-processing pass (INTEGRATION.md): None, a Cleanup,
+        # "largest" or "holes"; everything downstream - masks, the feed-back of a further pass, tracking - sees the cleaned instances
+        self.cleanup = Cleanup.parse(cleanup)
         self.cfg = cfg
         self.state_dict = state_dict
         self.device = torch.device(device)
@@ -170,12 +177,19 @@ class RefinerModel:
             self._staging[key] = stg
         return stg
 
+    def postprocess(self, eng, logits, out=None):
+        """a8-a11 and, with `cleanup` set, the connected-component clean-up of their result (its report kept beside the tables)."""
+        post = eng.postprocess(logits, out)
+        if self.cleanup is not None:
+            post["cc_report"] = eng.cleanup_post(logits, post, self.cleanup, post.get("cc_report"))
+        return post
+
     # -- device-side pipeline on already-resident tensors --
     def run(self, bgr, depth, offsets):
         B, H, W = bgr.shape[:3]
         eng = self.engine_for(H, W, B)
         logits = eng.forward(bgr, depth, offsets)
-        post = eng.postprocess(logits)
+        post = self.postprocess(eng, logits)
         return eng, logits, post
 
     # -- horizontal-flip test-time augmentation (INTEGRATION.md) --
@@ -248,7 +262,7 @@ class RefinerModel:
         for p in range(2, self.iterations + 1):
             eng.encode_label_map(ids_in, K, offsets)
             logits = self.tta_logits(eng, bgr, depth, None, offsets, ready=True) if self.tta else eng.forward(bgr, depth, offsets)
-            eng.postprocess(logits, post)
+            self.postprocess(eng, logits, post)
             eng.relabel_panoptic(post, mirror=self.tta, out=ids_out)
             eng.overlap_ids(ids_in[:B], ids_out[:B], K, K, out=table)
             conv = torch.where((conv == 0) & same_segmentation(table), torch.full_like(conv, p), conv)
@@ -298,6 +312,9 @@ class RefinerModel:
             inst.pred_classes = (torch.div(labels, LABEL_DIVISOR, rounding_mode="floor") - 1).to(torch.int64)
             if ov is not None:
                 inst.initial_index, inst.initial_iou = first, iou
+            if "cc_report" in post:                  # row 1 + j of the frame's report: its j-th instance
+                cc = post["cc_report"][b, 1:k + 1].to(torch.int64)
+                inst.cc_components, inst.cc_removed, inst.cc_filled = cc[:, 0], cc[:, 1], cc[:, 2]
             r["instances"] = inst
         return r
 
@@ -359,7 +376,7 @@ class RefinerModel:
             else:
                 stg.offsets.zero_()
             logits = eng.forward(d_bgr, d_dep, stg.offsets)        # fresh tensor: owned by the caller through the dict
-        post = eng.postprocess(logits, stg.post)
+        post = self.postprocess(eng, logits, stg.post)
         logits, post, it = self.refine(eng, d_bgr, d_dep, logits, post, 1, True, stg.iter_bufs)
         ov = None
         if self.track_initial:
@@ -372,6 +389,8 @@ class RefinerModel:
         k = int(stg.pin_count[0])
         post_out = {"panoptic": post["panoptic"].clone(), "labels": post["labels"].clone(), "scores": post["scores"].clone(),
                     "boxes": post["boxes"].clone()}
+        if "cc_report" in post:
+            post_out["cc_report"] = post["cc_report"].clone()
         masks_b = None
         if k > 0:
             masks_b = eng.extract_masks(post, k)[0].view(torch.bool)      # the kernel writes 0 / 1 bytes
@@ -404,7 +423,7 @@ class RefinerModel:
             else:
                 offsets = torch.zeros((B, 3, H, W), dtype=torch.float32, device=self.device)
             logits = eng.forward(d_bgr, d_depth, offsets)
-        post = eng.postprocess(logits)
+        post = self.postprocess(eng, logits)
         logits, post, it = self.refine(eng, d_bgr, d_depth, logits, post, B)           # always the fixed count: nothing is read back here
         ov = self.track(eng, d_masks[:B], post, it)
         slots = min(max(1, slots), eng.cap)
@@ -503,9 +522,11 @@ class RefinerModel:
 
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
-                 seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False):
+                 seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False,
+                 cleanup=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
+        self.cleanup = Cleanup.parse(cleanup)         # the connected-component clean-up after post-processing; None: none
         if config_file is None:
             self.cfg = qconfig.canonical_cfg()
         else:
@@ -537,7 +558,7 @@ class MaskRefinerPredictor:
         # predict() / predict_batch() stop at a fixed point; track_initial: initial_overlap / initial_index / initial_iou in every dict
         self.iterations, self.until_converged, self.track_initial = int(iterations), bool(until_converged), bool(track_initial)
         self.model = RefinerModel(self.cfg, sd, device, tta=self.tta, decode_errors=self.decode_errors, iterations=self.iterations,
-                                  until_converged=self.until_converged, track_initial=self.track_initial)
+                                  until_converged=self.until_converged, track_initial=self.track_initial, cleanup=self.cleanup)
         self.device = torch.device(device)
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
@@ -583,7 +604,7 @@ class MaskRefinerPredictor:
             depth = None if depth_imgs is None else torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)).to(dev)
             offsets = eng.encode(d_masks)
             logits = eng.forward(bgr, depth, offsets)
-        post = eng.postprocess(logits)
+        post = self.model.postprocess(eng, logits)
         logits, post, it = self.model.refine(eng, bgr, depth, logits, post, B, True)
         ov = self.model.track(eng, d_masks[:B], post, it)
         return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list], it, ov)
