@@ -444,6 +444,11 @@ double quber_forward_flops_padding(quber_ctx* ctx);
  *         64-row tiles) skip the padded filter COLUMNS as well: the GEMM rows of an image run through three column zones (left tap padded |
  *         both taps inside or both padded | right tap padded) as a serpentine, a tile multiplies only the filter columns its zones meet.
  *         The skipped taps multiply zeros: same bits unless the launch is split over K (then a re-association); 0 = rows only.
+ * key 51 (1; plan - the stand-alone quber_op_conv3x3_winograd reads the process default per call) dilated layers of the three-kernel Winograd
+ *         pipeline: the d phases of an axis share tiles, one zero slot between two phases, where that needs fewer tiles than a tiling of every
+ *         phase on its own (rows and columns decide independently; 640x480: res5.1/.2 conv2 and ASPP d = 6 / 12 run 88 / 96 / 108 / 132 tiles per
+ *         image instead of 96 / 128 / 144 / 144).  Which layers take Winograd, and with which tile, is not affected.  The same arithmetic per
+ *         tile; a pixel falls into another tile, so the last bits move as on a ragged frame; 0 = per phase everywhere, the bits before the key.
  * Process-only keys (quber_set_tuning): key 2 = give the stand-alone conv ops a split-K workspace (value != 0) or drop it (0);
  * key 11 = stand-alone conv op: dilated 3x3 layers in tap-major K order with the zero-padding filter rows skipped;
  * key 12 = stand-alone conv ops: quber_config.compute_dtype of the launch (1 = bf16 / 2 = fp16 operands, 3 = bf16x3);

@@ -169,6 +169,7 @@ int quber_op_conv3x3_winograd(const float* x, int32_t B, int32_t h, int32_t w, i
     q.in = mkview(x, B, h, w, cin); q.out = mkview(y, B, h, w, cout);
     q.u = u; q.scale = scale; q.shift = shift; q.ss_gs = 0; q.relu = relu; q.dil = dil; q.m = m;
     q.dtype = g_op_bf16;
+    q.pack = tune().wino_pack;           // key 51, read per call
     q.ws = ws; q.ws_floats = (size_t)ws_floats;
     // the single-kernel form where it applies and the workspace also holds its filter order (36 * cout * cin floats)
     if (m == 4 && tune().wino_fused && cout % 32 == 0 && (size_t)ws_floats >= (size_t)36 * cout * cin) {

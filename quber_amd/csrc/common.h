@@ -119,6 +119,8 @@ struct WinoP {
     int ss_gs, relu;
     int dil;                 // dilation (= padding)
     int m;                   // output tile edge: 2 = F(2x2,3x3), 4 = F(4x4,3x3)
+    int pack;                // three-kernel pipeline, dilated layers: 1 = an axis whose phases need fewer tiles packed into shared tiles takes that
+                             //   tiling (option key 51: the plan's value for an engine's layers, the process default for the stand-alone op), 0 = per phase
     int dtype;               // arithmetic of the P GEMMs (ConvP::bf16): 0 = fp32 MFMA, 3 = fp32 operands as 3 bf16 terms
     double* gn_sum;          // GroupNorm sums of the output to accumulate ([G][B][gn_groups][2]) or null
     int gn_groups;
@@ -138,6 +140,7 @@ bool winograd_eligible(int k, int stride, int pad, int dil, int Cin, int Cout);
 bool winograd_m6_channels_ok(int Cin, int Cout);
 size_t winograd_ws_floats(int B, int H, int W, int Cin, int Cout, int G, int dil, int m);
 double winograd_mac_ratio(int H, int W, int dil, int m);
+double winograd_mac_ratio_run(int H, int W, int dil, int m, bool pack);     // ... of the tiles the three-kernel pipeline runs (key 51)
 // single-kernel F(4x4,3x3) (wino_fused.hip)
 bool winograd_fused_ok(const WinoP& q, int B, int G);
 int launch_conv_winograd_fused(const WinoP& q, int B, int G, hipStream_t st);
@@ -159,6 +162,8 @@ struct Tuning {
     int wino_min_cout = 32;      // key 10 (plan): smallest output width routed to the Winograd path
     int wino_pairs = 0;          // key 17 (launch): F(4x4) transforms on channel pairs (8-byte accesses) instead of quads
     int wino_chunk_mb = 0;       // key 20 (launch): largest V | M footprint (MiB) of one pass over a pipeline layer; 0 = the whole batch at once
+    int wino_pack = 1;           // key 51 (plan): three-kernel pipeline, dilated layers: the d phases of an axis share tiles (one zero slot between two phases) where that needs
+                                 //   fewer tiles than a tiling per phase (winograd_xf.h: Axis); 0 = per phase everywhere (the arithmetic before the key existed)
     int wino_fused = 1;          // key 25 (plan): the eligible F(4x4) layers of the exact fp32 / bf16x3 modes as ONE kernel (wino_fused.hip); 0 = the three-kernel pipeline
     int wino_fused_max_cin = 160;  // key 27 (plan): widest input (channels) the single-kernel form takes.  Its two accumulation chains are Cin / 2 long: 80
                                  //   channels at the default - the float64-anchor ratios stay 0.64-1.11 (0.67-0.98 on the final plan); admitting 256 / 320

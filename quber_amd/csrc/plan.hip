@@ -39,6 +39,11 @@ BnFold frozen_bn(Builder& b, const std::string& n, int C) {
 // still executes <= tune().wino_max_ratio % of the direct multiplies.  The choice is the best of m = 4 / 2 (F(4x4) measures the
 // direct kernel's error against float64, profiles/r02a_parity_report.txt).  The 6x6 variant is OPT-IN
 // (quber_set_tuning key 9 = 6 / QUBER_WINOGRAD=f6): 2.5x the error at tap level, +4.5 % throughput at batch 16.
+// The decision - which layers, which m - is taken from the PER-PHASE ratio of a dilated layer, whatever option key 51 says: packing the
+// phases of an axis into shared tiles (winograd_xf.h: Axis) makes the layers that take the pipeline cheaper, it does not change which
+// layers do, so every configuration keeps its plan.  In particular ASPP d = 18 on the 30x40 map stays on its zone-skipping direct
+// launch: packed it would run 180 tiles, a ratio of 180 * 36 / (9 * 1200) = 0.60 and under key 8's 67 %, but 180 tiles cost about
+// 1.1 ms at 16 frames against the 0.85 ms of that launch, which already executes only 0.42 of the direct multiplies.
 // take it or not; m = the output tile edge; ratio = executed / direct multiplies of that variant on this map; one_kernel = eligible for the single-kernel
 // form (wino_fused.hip): its filter order is uploaded too.  plain = every input channel is real, no residual, no PReLU
 struct WinoChoice { bool take = false; int m = 0; double ratio = 0.0; bool one_kernel = false; };
@@ -202,9 +207,6 @@ void Builder::emit_conv(const std::string& name, const std::vector<const float*>
     if (wino) {
         const int m = wc.m, P = (m + 2) * (m + 2);
         c->wino_flops += fl;
-        c->wino_saved += fl * (1.0 - wc.ratio);
-        // exactly tiled, F(m x m) executes (m + 2)^2 / (9 m^2) of the direct multiplies: what it executes beyond that is tile padding
-        c->wino_pad += fl * (wc.ratio - (double)((m + 2) * (m + 2)) / (9.0 * m * m));
         std::vector<float> u((size_t)G * P * Cout * Cin);
         for (int g = 0; g < G; ++g) winograd_weights_host(w[g], Cout, Cin, m, &u[(size_t)g * P * Cout * Cin]);
         wq.in = in; wq.out = out; wq.u = upload(u);
@@ -216,6 +218,7 @@ void Builder::emit_conv(const std::string& name, const std::vector<const float*>
         }
         wq.scale = p.scale; wq.shift = p.shift; wq.ss_gs = Cout; wq.relu = relu; wq.dil = dil; wq.m = m;
         wq.dtype = c->cfg.compute_dtype;
+        wq.pack = tune().wino_pack;
     }
     std::shared_ptr<DeferredNorm> norm, norm16;
     if (wino && pending_norm && pending_norm->out.p == in.p && pending_norm->C == Cin && pending_norm->G == G) {
@@ -238,6 +241,11 @@ void Builder::emit_conv(const std::string& name, const std::vector<const float*>
         if (norm) probe.in = norm->in;           // what the layer will read (in place -> the pipeline)
         const bool fusedk = wq.uf && winograd_fused_ok(probe, Bmax, G);
         wq.algo = fusedk ? 2 : 1;            // decided once, here, for max_batch: every smaller launch takes the same kernels
+        // executed multiplies over the direct kernel's, of the tiles the layer really runs: the single kernel tiles per phase, the pipeline per key 51
+        const double ratio = fusedk ? wc.ratio : winograd_mac_ratio_run(in.H, in.W, dil, wq.m, wq.pack != 0);
+        c->wino_saved += fl * (1.0 - ratio);
+        // exactly tiled, F(m x m) executes (m + 2)^2 / (9 m^2) of the direct multiplies: what it executes beyond that is tile padding
+        c->wino_pad += fl * (ratio - (double)((wq.m + 2) * (wq.m + 2)) / (9.0 * wq.m * wq.m));
         if (wq.uf && winograd_fused_prepare() && err.empty()) err = "winograd (fused): cannot raise the kernels' LDS limit";
         const size_t need = fusedk ? winograd_fused_ws_floats(Bmax, Cin, G) : winograd_ws_floats(Bmax, in.H, in.W, Cin, Cout, G, dil, wq.m);
         if (need > c->wino_floats) c->wino_floats = need;

@@ -17,8 +17,11 @@
 // (tests/test_gpu_parity.py::test_conv3x3_winograd_vs_float64 bounds it); see DESIGN.md section 4 for where each is used.
 // m = 6 (points 0, +-1, +-2, +-1/2, inf): 64 GEMMs per layer, about a decimal digit less accurate than the direct
 // kernel; taken only where the 6x6 tiles fit the map with little padding.
-// With dilation d the layer is d*d independent dense convolutions on the phase sub-images in[d*Y + py][d*X + px]
-// (TH x TW tiles each, the same for every phase; tiles beyond a shorter phase read zeros and store nothing).
+// With dilation d (= padding) the layer is d*d independent dense convolutions, zero padding 1, on the phase sub-images
+// in[d*Y + py][d*X + px].  Per axis the d phases are tiled either each on its own (ceil(ceil(n/d)/m) tiles per phase, slots beyond a
+// shorter phase read zeros and store nothing) or, where that needs fewer tiles, PACKED: one after the other with a single zero slot
+// between two phases - the padding both read - and tiled as one image (winograd_xf.h: Axis; option key 51).  Rows and columns decide
+// independently, from (H, W, d, m) alone; the output at a zero slot is computed and dropped: it reaches neither `out` nor the GroupNorm sums.
 #include "common.h"
 #include "winograd_xf.h"
 
@@ -43,10 +46,12 @@ namespace {
 constexpr int wino_in_waves(int O, int V) { return O == 4 ? (V == 4 ? QB_WINO_IN_WAVES44 : 5) : O == 2 ? 4 : 2; }
 constexpr int wino_out_waves(int O, int V) { return O == 4 ? (V == 4 ? 2 : 3) : O == 2 ? 4 : 1; }
 
-template <int O, int V, bool NORM>
+// PK: at least one axis of a dilated layer is packed (winograd_xf.h: Axis) - TH x TW are then the tiles of the two axes over all
+// phases and a tile's pixels come from the axis maps ay / ax; !PK: d*d phases of TH x TW tiles each (every undilated layer)
+template <int O, int V, bool NORM, bool PK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wino_in_waves(O, V)))) void wino_input_kernel(const float* __restrict__ in, int B, int H, int W, int CV, int in_cs,
                                                          long in_gs, int TH, int TW, int d, float* __restrict__ v, long v_gs,
-                                                         const WinoNorm np, int Ball, int boff) {
+                                                         const WinoNorm np, int Ball, int boff, const Axis ay, const Axis ax) {
     constexpr int T = O + 2;
     using VT = Vec<V>;
     const int g = blockIdx.z;
@@ -54,7 +59,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wino_in_wav
     v += g * v_gs;
     const int tpb = 256 / CV;
     const int cv = tpb ? threadIdx.x % CV : blockIdx.y * 256 + threadIdx.x;
-    const long tiles = (long)B * d * d * TH * TW;
+    const long tiles = PK ? (long)B * TH * TW : (long)B * d * d * TH * TW;
     // XCD-aware order: blocks b and b + 8 share an XCD (and its L2).  Every input pixel is read by up to (T/O)^2 = 2.25
     // tiles (the 2-pixel halo); with consecutive blocks on consecutive tiles the neighbours sit on other XCDs and every
     // halo read misses L2 (rocprofv3: 1.9x the input fetched from HBM).  Each XCD gets one contiguous run of tiles instead.
@@ -62,7 +67,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wino_in_wav
     const int vb = (xcd < br ? xcd * (bq + 1) : br * (bq + 1) + (xcd - br) * bq) + (blockIdx.x >> 3);
     const long tile = tpb ? (long)vb * tpb + threadIdx.x / CV : vb;
     if (tile >= tiles || cv >= CV || (tpb && (int)(threadIdx.x / CV) >= tpb)) return;
-    const TileAt ta = locate(tile, TH, TW, d);
+    TileAt ta;
+    int yy[T];                                       // PK: the rows of the patch (-1: a zero slot)
+    AxisPos sx{0, 0};
+    if constexpr (PK) {
+        const long per_img = (long)TH * TW;
+        ta.b = (int)(tile / per_img);
+        const int local = (int)(tile - ta.b * per_img), aty = local / TW;
+        AxisPos sy = axis_begin(ay, aty);
+#pragma unroll
+        for (int i = 0; i < T; ++i) {
+            yy[i] = axis_coord(ay, sy);
+            sy = axis_next(ay, sy);
+        }
+        sx = axis_begin(ax, local - aty * TW);
+    } else {
+        ta = locate(tile, TH, TW, d);
+    }
     const int c = cv * V;
     const float* base = in + (long)ta.b * H * W * in_cs + c;
     VT nsc, nbi;
@@ -83,7 +104,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wino_in_wav
     VT t[T][T];                                      // t = B^T d, one input column at a time
 #pragma unroll
     for (int j = 0; j < T; ++j) {
-        const int x = d * (O * ta.tx - 1 + j) + ta.px;
+        int x;
+        if constexpr (PK) {
+            x = axis_coord(ax, sx);
+            sx = axis_next(ax, sx);
+        } else {
+            x = d * (O * ta.tx - 1 + j) + ta.px;
+        }
         VT col[T], tc[T];
         // No branch around a load: a pixel of the zero padding is read from the nearest pixel of the map (a line its neighbours read
         // anyway) and replaced by zero afterwards, and the six loads of a column are requested before the first is used.  With
@@ -93,12 +120,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wino_in_wav
         const bool xin = (unsigned)x < (unsigned)W;
 #pragma unroll
         for (int i = 0; i < T; ++i) {
-            const int y = d * (O * ta.ty - 1 + i) + ta.py;
+            int y;
+            if constexpr (PK) y = yy[i]; else y = d * (O * ta.ty - 1 + i) + ta.py;
             col[i] = vload<V>(base + ((long)min(max(y, 0), H - 1) * W + xc) * in_cs);
         }
 #pragma unroll
         for (int i = 0; i < T; ++i) {
-            const int y = d * (O * ta.ty - 1 + i) + ta.py;
+            int y;
+            if constexpr (PK) y = yy[i]; else y = d * (O * ta.ty - 1 + i) + ta.py;
             const bool inside = xin && (unsigned)y < (unsigned)H;
 #pragma unroll
             for (int e = 0; e < V; ++e) {
@@ -127,12 +156,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wino_in_wav
 // sums of what it stores (fp64, LDS per block, one global atomic per (image, group) per block - as the direct kernel's
 // epilogue does).
 constexpr int OUT_ITERS = 4;
-template <int O, int V>
+template <int O, int V, bool PK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wino_out_waves(O, V)))) void wino_output_kernel(const float* __restrict__ m, long m_gs, int B, int OH, int OW, int CV,
                                                           int TH, int TW, int d, const float* __restrict__ scale,
                                                           const float* __restrict__ shift, int ss_gs, int relu,
                                                           float* __restrict__ out, int out_cs, long out_gs,
-                                                          double* __restrict__ gn_sum, int gn_groups, int gn_cpg, int Ball, int boff, int iters) {
+                                                          double* __restrict__ gn_sum, int gn_groups, int gn_cpg, int Ball, int boff, int iters,
+                                                          const Axis ay, const Axis ax) {
     constexpr int T = O + 2;
     using VT = Vec<V>;
     const int g = blockIdx.z;
@@ -141,7 +171,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wino_out_wa
     const int tpb = 256 / CV;
     const int cv = tpb ? threadIdx.x % CV : blockIdx.y * 256 + threadIdx.x;
     const int c = cv * V;
-    const long per_img = (long)d * d * TH * TW;
+    const long per_img = PK ? (long)TH * TW : (long)d * d * TH * TW;
     const long tiles = (long)B * per_img;
     const int step = tpb ? tpb : 1;                  // tiles per iteration
     const long tile0 = (long)blockIdx.x * step * iters;
@@ -162,7 +192,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wino_out_wa
     for (int it = 0; it < iters; ++it) {
         const long tile = tile0 + (long)it * step + (tpb ? threadIdx.x / CV : 0);
         if (!lane_ok || tile >= tiles) continue;
-        const TileAt ta = locate(tile, TH, TW, d);
+        TileAt ta;
+        int oys[O], oxs[O];                          // PK: the pixels the tile owns (-1: a zero slot - nothing stored, nothing summed)
+        if constexpr (PK) {
+            ta.b = (int)(tile / per_img);
+            const int local = (int)(tile - ta.b * per_img), aty = local / TW;
+            AxisPos sy = axis_next(ay, axis_begin(ay, aty)), sx = axis_next(ax, axis_begin(ax, local - aty * TW));
+#pragma unroll
+            for (int i = 0; i < O; ++i) {
+                oys[i] = axis_coord(ay, sy);
+                oxs[i] = axis_coord(ax, sx);
+                sy = axis_next(ay, sy);
+                sx = axis_next(ax, sx);
+            }
+        } else {
+            ta = locate(tile, TH, TW, d);
+        }
         const float* src = m + tile * (long)(CV * V) + c;
         VT s[O][T];                                  // s = A^T M, one column of positions at a time
 #pragma unroll
@@ -177,14 +222,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(wino_out_wa
         double a = 0.0, q = 0.0;
 #pragma unroll
         for (int i = 0; i < O; ++i) {
-            const int oy = d * (O * ta.ty + i) + ta.py;
+            int oy;
+            if constexpr (PK) oy = oys[i]; else oy = d * (O * ta.ty + i) + ta.py;
             VT row[O];
             at<O>(s[i], row);                        // (A^T M) A
-            if (oy >= OH) continue;
+            if (oy >= OH || (PK && oy < 0)) continue;
 #pragma unroll
             for (int j = 0; j < O; ++j) {
-                const int ox = d * (O * ta.tx + j) + ta.px;
-                if (ox >= OW) continue;
+                int ox;
+                if constexpr (PK) ox = oxs[j]; else ox = d * (O * ta.tx + j) + ta.px;
+                if (ox >= OW || (PK && ox < 0)) continue;
                 VT y = row[j];
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
@@ -311,6 +358,10 @@ size_t winograd_ws_floats(int B, int H, int W, int Cin, int Cout, int G, int dil
 double winograd_mac_ratio(int H, int W, int dil, int m) {
     return (double)((m + 2) * (m + 2)) * wino_tiles(H, W, dil, m) / (9.0 * H * W);
 }
+// the same for the tiles the three-kernel pipeline really runs (pack: option key 51 - the axes of a dilated layer packed where that needs fewer tiles)
+double winograd_mac_ratio_run(int H, int W, int dil, int m, bool pack) {
+    return (double)((m + 2) * (m + 2)) * wino_tiles_run(H, W, dil, m, pack) / (9.0 * H * W);
+}
 
 
 template <int O, int V>     // V: channels per thread in the transforms
@@ -319,8 +370,12 @@ static int run_winograd(const WinoP& q, int Ball, int G, hipStream_t st) {
     const View& in = q.in;
     const View& out = q.out;
     const int H = in.H, W = in.W, Cin = in.C, Cout = out.C, d = q.dil;
-    const int TH = tiles_1d(H, d, O), TW = tiles_1d(W, d, O);
-    const long tiles_pf = wino_tiles(H, W, d, O);
+    // the tile map: per axis, packed where that needs fewer tiles (a function of H, W, d, m alone - never of the batch); with no axis
+    // packed - every undilated layer - the per-phase kernels
+    const Axis ay = make_axis(H, d, O, q.pack != 0), ax = make_axis(W, d, O, q.pack != 0);
+    const bool pk = ay.packed || ax.packed;
+    const int TH = pk ? ay.T : tiles_1d(H, d, O), TW = pk ? ax.T : tiles_1d(W, d, O);
+    const long tiles_pf = (long)ay.T * ax.T;             // (not packed: d * d * TH * TW = wino_tiles)
     if ((long)Ball * tiles_pf * P >= (1L << 31) / 2) return fail("winograd: too many tiles");
     // Frames per pass.  The intermediates V | M of a pass are rewritten in place by the next one; kept below the Infinity
     // Cache (256 MiB) they are written and re-read on the die instead of through HBM (tools/wino_subbatch_probe.py).
@@ -368,12 +423,12 @@ static int run_winograd(const WinoP& q, int Ball, int G, hipStream_t st) {
         };
         {   // activations in once, V = P / m^2 times their size out
             ProfScope prof("wino_input", 4.0 * Gv * Cin * ((double)B * H * W + (double)P * tiles), 0.0, st);
-            if (np.stats)
-                hipLaunchKernelGGL((wino_input_kernel<O, V, true>), grid_v(Cin / V), dim3(256), 0, st, in_p, B, H, W, Cin / V, in.cs, in.gs, TH,
-                                   TW, d, v, (long)P * tiles * Cin, np, Ball, b0);
-            else
-                hipLaunchKernelGGL((wino_input_kernel<O, V, false>), grid_v(Cin / V), dim3(256), 0, st, in_p, B, H, W, Cin / V, in.cs, in.gs, TH,
-                                   TW, d, v, (long)P * tiles * Cin, np, Ball, b0);
+            auto launch_in = [&](auto kern) {
+                hipLaunchKernelGGL(kern, grid_v(Cin / V), dim3(256), 0, st, in_p, B, H, W, Cin / V, in.cs, in.gs, TH, TW, d, v, (long)P * tiles * Cin, np,
+                                   Ball, b0, ay, ax);
+            };
+            if (np.stats) pk ? launch_in(wino_input_kernel<O, V, true, true>) : launch_in(wino_input_kernel<O, V, true, false>);
+            else pk ? launch_in(wino_input_kernel<O, V, false, true>) : launch_in(wino_input_kernel<O, V, false, false>);
         }
         QB_CHECK(hipGetLastError());
         ConvP p{};
@@ -404,9 +459,11 @@ static int run_winograd(const WinoP& q, int Ball, int G, hipStream_t st) {
         og.x = (og.x + iters - 1) / iters;
         {   // M in once, the layer's output out once
             ProfScope prof("wino_output", 4.0 * G * Cout * ((double)P * tiles + (double)B * H * W), 0.0, st);
-            hipLaunchKernelGGL((wino_output_kernel<O, V>), og, dim3(256), 0, st, m, (long)P * tiles * Cout, B, H, W, CVo, TH, TW, d,
-                               q.scale, q.shift, q.ss_gs, q.relu, out_p, out.cs, out.gs, gn_here ? q.gn_sum : nullptr, q.gn_groups,
-                               q.gn_groups ? Cout / q.gn_groups : 1, Ball, b0, iters);
+            auto launch_out = [&](auto kern) {
+                hipLaunchKernelGGL(kern, og, dim3(256), 0, st, m, (long)P * tiles * Cout, B, H, W, CVo, TH, TW, d, q.scale, q.shift, q.ss_gs, q.relu, out_p,
+                                   out.cs, out.gs, gn_here ? q.gn_sum : nullptr, q.gn_groups, q.gn_groups ? Cout / q.gn_groups : 1, Ball, b0, iters, ay, ax);
+            };
+            pk ? launch_out(wino_output_kernel<O, V, true>) : launch_out(wino_output_kernel<O, V, false>);
         }
         QB_CHECK(hipGetLastError());
     }

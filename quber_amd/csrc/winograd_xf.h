@@ -123,5 +123,68 @@ __device__ inline TileAt locate32(unsigned tile, unsigned TH, unsigned TW, unsig
 inline int tiles_1d(int n, int d, int m) { return ((n + d - 1) / d + m - 1) / m; }
 inline long wino_tiles(int H, int W, int d, int m) { return (long)d * d * tiles_1d(H, d, m) * tiles_1d(W, d, m); }
 
+// ---- the tile map of one axis (three-kernel pipeline; host and device) ----
+// With dilation d (= padding) an axis of n pixels is d phases, phase p = the pixels d*r + p, r < n_p = ceil((n - p) / d); in
+// phase coordinates the layer is a dense 3-tap convolution with zero padding 1.  Two tilings of the axis into tiles of m slots:
+//   per phase: every phase gets ceil(ceil(n/d)/m) tiles of its own, d * that in all (what wino_fused.hip keeps);
+//   packed:    the non-empty phases one after the other with ONE zero slot between neighbours - the slot both read as their
+//              padding - tiled as if they were one image: L = n + (non-empty phases - 1) slots, ceil(L / m) tiles.
+// An axis is packed iff that needs fewer tiles (rows and columns decide independently; d = 1 never is).
+// A tile reads the slots m*t - 1 .. m*t + m and owns m*t .. m*t + m - 1; a slot is a pixel or zero (separator, slot -1, slots
+// >= L / past the phase's end): a zero slot's output is computed and dropped.
+struct Axis {
+    int n, d, m;
+    int packed;      // 1: the packed tiling
+    int T;           // tiles of the axis
+    int Tp;          // per phase: tiles of one phase
+    int q, rem;      // n / d, n % d: phases < rem have q + 1 pixels, the others q
+};
+__host__ __device__ inline int axis_tiles_phase(int n, int d, int m) { return d * (((n + d - 1) / d + m - 1) / m); }
+__host__ __device__ inline int axis_tiles_packed(int n, int d, int m) { return (n + (d < n ? d : n) - 1 + m - 1) / m; }
+__host__ __device__ inline Axis make_axis(int n, int d, int m, bool pack) {
+    Axis a;
+    a.n = n; a.d = d; a.m = m;
+    a.Tp = ((n + d - 1) / d + m - 1) / m;
+    const int tph = d * a.Tp, tpk = axis_tiles_packed(n, d, m);
+    a.packed = pack && tpk < tph;
+    a.T = a.packed ? tpk : tph;
+    a.q = n / d; a.rem = n % d;
+    return a;
+}
+// a slot of the axis: element r of phase p (r == -1: the zero slot in front of the phase)
+struct AxisPos { int p, r; };
+// slot m*t - 1, the first one tile t reads
+__host__ __device__ inline AxisPos axis_begin(const Axis& a, int t) {
+    AxisPos s;
+    if (!a.packed) {
+        s.p = t / a.Tp;
+        s.r = a.m * (t - s.p * a.Tp) - 1;
+        return s;
+    }
+    // with a zero slot in front of phase 0 as well, slot m*t - 1 has index e = m*t >= 0 in a sequence of segments
+    // [zero, the phase's pixels]: rem segments of q + 2 slots, then segments of q + 1
+    const int e = a.m * t, head = a.rem * (a.q + 2);
+    const bool lng = e < head;
+    const int seg = lng ? a.q + 2 : a.q + 1, e2 = lng ? e : e - head, k = e2 / seg;
+    s.p = (lng ? 0 : a.rem) + k;
+    s.r = e2 - k * seg - 1;
+    return s;
+}
+// the next slot
+__host__ __device__ inline AxisPos axis_next(const Axis& a, AxisPos s) {
+    ++s.r;
+    if (a.packed && s.r == a.q + (s.p < a.rem ? 1 : 0)) { ++s.p; s.r = -1; }
+    return s;
+}
+// the pixel coordinate of a slot, or -1: it reads zero and stores nothing
+__host__ __device__ inline int axis_coord(const Axis& a, AxisPos s) {
+    const int c = a.d * s.r + s.p;
+    return (s.r >= 0 && s.p < a.d && c < a.n) ? c : -1;
+}
+// tiles per image of the pipeline: each axis packed where that needs fewer tiles (pack == false: wino_tiles)
+inline long wino_tiles_run(int H, int W, int d, int m, bool pack) {
+    return (long)make_axis(H, d, m, pack).T * make_axis(W, d, m, pack).T;
+}
+
 }  // namespace wxf
 }  // namespace quber
