@@ -513,6 +513,48 @@ int quber_op_bilinear(const float* dev_x, int32_t batch, int32_t h, int32_t w, i
                       float* dev_y, void* stream);
 int quber_op_maxpool3x3s2(const float* dev_x, int32_t batch, int32_t h, int32_t w, int32_t c, float* dev_y,
                           void* stream);
+/* The glue kernels between the convolutions (csrc/elementwise.hip), each on explicit NHWC views - test hooks: the network reaches
+ * them only through quber_forward.  A view is (pointer to its first channel, cs = elements between two pixels, gs = elements between
+ * two launch groups, es = element size: 4 fp32, 2 fp16) over batch x h x w x c; a view the launcher refuses (mixed element types, c or cs
+ * no multiple of 4, a base address off the 4-element boundary) returns the launcher's error.  No op allocates or synchronises.
+ *   quber_debug_gn_pixels_per_block   pixels per block the GroupNorm statistics (stats_pass != 0) / apply pass give a tensor (host only)
+ *   quber_op_gn_stats                 dev_stats f64 [G][batch][groups][sum, sum of squares] += the sums of x; zero != 0 clears it first
+ *   quber_op_gn_apply                 y = relu?((x - mean) * rstd * gamma + beta) from those sums; gamma / beta of launch group g at g * param_gs
+ *   quber_op_maxpool_view             3x3 / stride 2 / pad 1 -> [batch][(h+1)/2][(w+1)/2][c]
+ *   quber_op_bilinear_view            F.interpolate(mode="bilinear", align_corners=False) to oh x ow
+ *   quber_op_avgpool                  mean over the pixels -> y [batch][c] at stride y_cs
+ *   quber_op_add_channels / quber_op_copy_channels    y = a + b / y = x on channel slices
+ *   quber_op_predictors               n <= 5 1x1 heads on c = 32 / 64 features in one launch: logits -> planar dev_q [batch][q_nch][h*w] from
+ *                                     plane q_ch0[j]; act[j] 1 = softmax / 2 = sigmoid of the head's cout[j] logits -> act_dst[j] (pixel stride
+ *                                     act_cs; null = none).  feat, w, bias, act_dst, cout, q_ch0, act: HOST arrays of n entries
+ *   quber_op_upsample_logits          planar bilinear x scale of dev_q [batch][nch][h][w], top-left oh x ow kept; planes whose bit of mul_mask is
+ *                                     set are multiplied by scale
+ *   quber_op_preprocess               u8 HWC bgr (+ depth, streams = 2) + f32 planar offsets -> x [streams][batch_cap][h][w][x_c];
+ *                                     mean6 / std6: HOST arrays */
+int32_t quber_debug_gn_pixels_per_block(int32_t hw, int32_t c, int32_t batch, int32_t groups_of_launch, int32_t stats_pass);
+int quber_op_gn_stats(const void* dev_x, int32_t x_cs, int64_t x_gs, int32_t es, int32_t batch, int32_t h, int32_t w, int32_t c,
+                      int32_t groups_of_launch, int32_t groups, double* dev_stats, int32_t zero, void* stream);
+int quber_op_gn_apply(const void* dev_x, int32_t x_cs, int64_t x_gs, int32_t x_es, void* dev_y, int32_t y_cs, int64_t y_gs, int32_t y_es,
+                      int32_t batch, int32_t h, int32_t w, int32_t c, int32_t groups_of_launch, int32_t groups, const double* dev_stats,
+                      const float* dev_gamma, const float* dev_beta, int32_t param_gs, float eps, int32_t relu, void* stream);
+int quber_op_maxpool_view(const void* dev_x, int32_t x_cs, int64_t x_gs, int32_t x_es, void* dev_y, int32_t y_cs, int64_t y_gs, int32_t y_es,
+                          int32_t batch, int32_t h, int32_t w, int32_t c, int32_t groups_of_launch, void* stream);
+int quber_op_bilinear_view(const void* dev_x, int32_t x_cs, int32_t x_es, void* dev_y, int32_t y_cs, int32_t y_es, int32_t batch, int32_t h,
+                           int32_t w, int32_t c, int32_t oh, int32_t ow, void* stream);
+int quber_op_avgpool(const void* dev_x, int32_t x_cs, int32_t x_es, void* dev_y, int32_t y_cs, int32_t y_es, int32_t batch, int32_t h, int32_t w,
+                     int32_t c, void* stream);
+int quber_op_add_channels(const void* dev_a, int32_t a_cs, int32_t a_es, const void* dev_b, int32_t b_cs, int32_t b_es, void* dev_y, int32_t y_cs,
+                          int32_t y_es, int32_t batch, int32_t h, int32_t w, int32_t c, void* stream);
+int quber_op_copy_channels(const void* dev_x, int32_t x_cs, int32_t x_es, void* dev_y, int32_t y_cs, int32_t y_es, int32_t batch, int32_t h,
+                           int32_t w, int32_t c, void* stream);
+int quber_op_predictors(int32_t n, const void* const* dev_feat, const float* const* dev_w, const float* const* dev_bias, void* const* dev_act_dst,
+                        const int32_t* cout, const int32_t* q_ch0, const int32_t* act, int32_t c, int32_t feat_cs, int32_t es, int32_t batch,
+                        int32_t h, int32_t w, float* dev_q, int32_t q_nch, int32_t act_cs, void* stream);
+int quber_op_upsample_logits(const float* dev_q, float* dev_out, int32_t batch, int32_t nch, int32_t h, int32_t w, int32_t scale, int32_t oh,
+                             int32_t ow, uint32_t mul_mask, void* stream);
+int quber_op_preprocess(const uint8_t* dev_bgr, const uint8_t* dev_depth, const float* dev_offsets, void* dev_x, int32_t x_c, int32_t es,
+                        int32_t batch, int32_t batch_cap, int32_t h, int32_t w, const float* mean6, const float* std6, int32_t streams,
+                        void* stream);
 /* a9 alone, on a caller-supplied centre list in ANY order - group_pixels(ctr, offsets) of post_processing.py:44-76
  * (quber_postprocess derives its centres from the centre plane, i.e. always in raster order; the reference's function takes
  * whatever list it is handed).  The grouping kernel quber_postprocess launches, unchanged.

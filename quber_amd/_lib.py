@@ -98,6 +98,18 @@ SIGNATURES = {
     "quber_op_groupnorm": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, C.c_float, _I, _P, _P, _P]),
     "quber_op_bilinear": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "quber_op_maxpool3x3s2": (C.c_int, [_P, _I, _I, _I, _I, _P, _P]),
+    # the glue kernels on explicit views (tests/test_gpu_glue.py): pointer, cs, [gs,] es per view
+    "quber_debug_gn_pixels_per_block": (C.c_int32, [_I, _I, _I, _I, _I]),
+    "quber_op_gn_stats": (C.c_int, [_P, _I, C.c_int64, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "quber_op_gn_apply": (C.c_int, [_P, _I, C.c_int64, _I, _P, _I, C.c_int64, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, C.c_float, _I, _P]),
+    "quber_op_maxpool_view": (C.c_int, [_P, _I, C.c_int64, _I, _P, _I, C.c_int64, _I, _I, _I, _I, _I, _I, _P]),
+    "quber_op_bilinear_view": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "quber_op_avgpool": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "quber_op_add_channels": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "quber_op_copy_channels": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "quber_op_predictors": (C.c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "quber_op_upsample_logits": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_uint32, _P]),
+    "quber_op_preprocess": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "quber_op_group_pixels": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 

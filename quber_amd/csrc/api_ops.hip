@@ -202,6 +202,81 @@ int quber_op_bilinear(const float* x, int32_t B, int32_t h, int32_t w, int32_t c
     return launch_bilinear(mkview(x, B, h, w, c), mkview(y, B, oh, ow, c), B, (hipStream_t)stream);
 }
 
+// ---- the glue kernels of elementwise.hip on explicit views (tests): arguments -> View -> launcher, nothing else ----
+static View opview(const void* p, int B, int h, int w, int c, int cs, long gs, int es) {
+    View v;
+    v.p = reinterpret_cast<float*>(const_cast<void*>(p)); v.B = B; v.H = h; v.W = w; v.C = c; v.cs = cs; v.gs = gs; v.es = es;
+    return v;
+}
+
+int32_t quber_debug_gn_pixels_per_block(int32_t hw, int32_t c, int32_t batch, int32_t groups_of_launch, int32_t stats_pass) {
+    return gn_pixels_per_block(hw, c, batch, groups_of_launch, stats_pass != 0);
+}
+
+int quber_op_gn_stats(const void* x, int32_t x_cs, int64_t x_gs, int32_t es, int32_t B, int32_t h, int32_t w, int32_t c, int32_t G, int32_t groups,
+                      double* stats, int32_t zero, void* stream) {
+    return launch_gn_stats(opview(x, B, h, w, c, x_cs, x_gs, es), B, G, groups, stats, (hipStream_t)stream, zero != 0);
+}
+
+int quber_op_gn_apply(const void* x, int32_t x_cs, int64_t x_gs, int32_t x_es, void* y, int32_t y_cs, int64_t y_gs, int32_t y_es, int32_t B, int32_t h,
+                      int32_t w, int32_t c, int32_t G, int32_t groups, const double* stats, const float* gamma, const float* beta, int32_t param_gs,
+                      float eps, int32_t relu, void* stream) {
+    return launch_gn_apply(opview(x, B, h, w, c, x_cs, x_gs, x_es), opview(y, B, h, w, c, y_cs, y_gs, y_es), B, G, groups, stats, gamma, beta,
+                           param_gs, eps, relu, (hipStream_t)stream);
+}
+
+int quber_op_maxpool_view(const void* x, int32_t x_cs, int64_t x_gs, int32_t x_es, void* y, int32_t y_cs, int64_t y_gs, int32_t y_es, int32_t B,
+                          int32_t h, int32_t w, int32_t c, int32_t G, void* stream) {
+    return launch_maxpool3x3s2(opview(x, B, h, w, c, x_cs, x_gs, x_es), opview(y, B, (h + 1) / 2, (w + 1) / 2, c, y_cs, y_gs, y_es), B, G,
+                               (hipStream_t)stream);
+}
+
+int quber_op_bilinear_view(const void* x, int32_t x_cs, int32_t x_es, void* y, int32_t y_cs, int32_t y_es, int32_t B, int32_t h, int32_t w, int32_t c,
+                           int32_t oh, int32_t ow, void* stream) {
+    return launch_bilinear(opview(x, B, h, w, c, x_cs, 0, x_es), opview(y, B, oh, ow, c, y_cs, 0, y_es), B, (hipStream_t)stream);
+}
+
+int quber_op_avgpool(const void* x, int32_t x_cs, int32_t x_es, void* y, int32_t y_cs, int32_t y_es, int32_t B, int32_t h, int32_t w, int32_t c,
+                     void* stream) {
+    return launch_avgpool(opview(x, B, h, w, c, x_cs, 0, x_es), opview(y, B, 1, 1, c, y_cs, 0, y_es), B, (hipStream_t)stream);
+}
+
+int quber_op_add_channels(const void* a, int32_t a_cs, int32_t a_es, const void* b, int32_t b_cs, int32_t b_es, void* y, int32_t y_cs, int32_t y_es,
+                          int32_t B, int32_t h, int32_t w, int32_t c, void* stream) {
+    return launch_add_channels(opview(a, B, h, w, c, a_cs, 0, a_es), opview(b, B, h, w, c, b_cs, 0, b_es), opview(y, B, h, w, c, y_cs, 0, y_es), B,
+                               (hipStream_t)stream);
+}
+
+int quber_op_copy_channels(const void* x, int32_t x_cs, int32_t x_es, void* y, int32_t y_cs, int32_t y_es, int32_t B, int32_t h, int32_t w, int32_t c,
+                           void* stream) {
+    return launch_copy_channels(opview(x, B, h, w, c, x_cs, 0, x_es), opview(y, B, h, w, c, y_cs, 0, y_es), B, (hipStream_t)stream);
+}
+
+// the per-head arrays are HOST arrays of n entries (device pointers / integers); a head without an activation destination passes null there
+int quber_op_predictors(int32_t n, const void* const* feat, const float* const* w, const float* const* bias, void* const* act_dst, const int32_t* cout,
+                        const int32_t* q_ch0, const int32_t* act, int32_t c, int32_t feat_cs, int32_t es, int32_t B, int32_t h, int32_t wd, float* q,
+                        int32_t q_nch, int32_t act_cs, void* stream) {
+    PredHeads hs{};
+    hs.n = n;
+    for (int j = 0; j < n && j < 5; ++j) {
+        hs.in[j] = feat[j]; hs.w[j] = w[j]; hs.bias[j] = bias[j]; hs.sm[j] = act_dst[j];
+        hs.cout[j] = cout[j]; hs.q_ch0[j] = q_ch0[j]; hs.act[j] = act[j];
+    }
+    return launch_predictors(hs, c, feat_cs, es, h, wd, q, q_nch, act_cs, B, (hipStream_t)stream);
+}
+
+int quber_op_upsample_logits(const float* q, float* out, int32_t B, int32_t nch, int32_t h, int32_t w, int32_t scale, int32_t oh, int32_t ow,
+                             uint32_t mul_mask, void* stream) {
+    return launch_upsample_logits(q, out, B, nch, h, w, scale, oh, ow, mul_mask, (hipStream_t)stream);
+}
+
+// mean6 / std6: HOST arrays; x: [streams][batch_cap][h][w][x_c]
+int quber_op_preprocess(const uint8_t* rgb, const uint8_t* depth, const float* offs, void* x, int32_t x_c, int32_t es, int32_t B, int32_t batch_cap,
+                        int32_t h, int32_t w, const float* mean6, const float* std6, int32_t streams, void* stream) {
+    return launch_preprocess(rgb, depth, offs, opview(x, batch_cap, h, w, x_c, x_c, (long)batch_cap * h * w * x_c, es), B, batch_cap, h, w, mean6,
+                             std6, streams, (hipStream_t)stream);
+}
+
 int quber_op_group_pixels(const float* logits, int32_t n_planes, int32_t batch, int32_t h, int32_t w, int32_t cap,
                           const int32_t* centers, const int32_t* ncenters, uint8_t* ids, uint32_t* area, void* stream) {
     if (!logits || !centers || !ncenters || !ids || !area || batch < 1 || h < 1 || w < 1) return fail("bad argument to quber_op_group_pixels");

@@ -231,6 +231,7 @@ int launch_stem_conv1(const uint8_t* bgr, const uint8_t* depth, const float* off
                       const void* wf16 = nullptr);
 int launch_zero(void* p, size_t bytes, hipStream_t st);
 int launch_gn_stats(const View& in, int B, int G, int groups, double* stats, hipStream_t st, bool zero = true);
+int gn_pixels_per_block(int HW, int C, int B, int G, bool stats = false);   // pixels per block of the two GroupNorm passes (elementwise.hip)
 int launch_gn_apply(const View& in, const View& out, int B, int G, int groups, const double* stats,
                     const float* gamma, const float* beta, int param_gs, float eps, int relu, hipStream_t st);
 int launch_bilinear(const View& in, const View& out, int B, hipStream_t st);

@@ -51,6 +51,15 @@ template <> struct Vec16<half_t> {
 };
 
 
+// What every kernel below assumes of a view: elements of 4 or 2 bytes, whole groups of 4 channels, and every pixel, launch group and the
+// base address on a 4-element boundary (ldv4 / stv4 move 16 or 8 bytes).  A view that breaks this is refused by the launchers - a
+// channel count that is no multiple of 4 would silently lose its last channels, a misplaced fp16 slice would be read 8 bytes at a
+// time from a 2-byte boundary.
+static inline bool quads_ok(const View& v) {
+    return (v.es == 4 || v.es == 2) && v.C > 0 && v.C % 4 == 0 && v.cs % 4 == 0 && (v.gs & 3) == 0 &&
+           ((uintptr_t)v.p & (uintptr_t)(4 * v.es - 1)) == 0;
+}
+
 static inline int cap_grid(long work, int per_block) {
     long g = (work + per_block - 1) / per_block;
     if (g < 1) g = 1;
@@ -99,6 +108,9 @@ __global__ void preprocess_kernel(const uint8_t* __restrict__ rgb, const uint8_t
 
 int launch_preprocess(const uint8_t* rgb, const uint8_t* depth, const float* offs, const View& x, int B, int Bcap,
                       int H, int W, const float* mean6, const float* std6, int streams, hipStream_t st) {
+    if ((x.es != 4 && x.es != 2) || x.C < 8 || x.C % 4 || ((uintptr_t)x.p & (uintptr_t)(4 * x.es - 1)))
+        return fail("preprocess: the stream input holds at least 8 channels, in aligned groups of 4");
+    if (streams < 1 || streams > 2 || B > Bcap) return fail("preprocess: one or two streams, batch within the capacity");
     const long total = (long)B * H * W;
     ProfScope prof("preprocess", (double)total * (3.0 * streams + 12.0 + (double)x.es * x.C * streams), 0.0, st);
     if (x.es == 2)
@@ -156,6 +168,7 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const T* __restrict__ in, 
 int launch_maxpool3x3s2(const View& in, const View& out, int B, int G, hipStream_t st) {
     ProfScope prof("maxpool", (double)in.es * G * B * in.C * ((double)in.H * in.W + (double)out.H * out.W), 0.0, st);
     if (in.es != out.es) return fail("maxpool: mixed element types");
+    if (!quads_ok(in) || !quads_ok(out) || in.C != out.C) return fail("maxpool: channels must come in aligned groups of 4");
     if (in.es == 2) {
         const bool wide = in.C % 8 == 0 && in.cs % 8 == 0 && out.cs % 8 == 0 && (in.gs & 7) == 0 && (out.gs & 7) == 0 &&
                           (((uintptr_t)in.p | (uintptr_t)out.p) & 15) == 0;      // 16-byte accesses: a channel-slice view may start 8 bytes in
@@ -237,7 +250,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ in,
     if (t < groups * 2) atomicAdd(&stats[((long)(g * B + b) * groups) * 2 + t], acc[t]);
 }
 
-static int gn_pixels_per_block(int HW, int C, int B, int G, bool stats = false) {
+int gn_pixels_per_block(int HW, int C, int B, int G, bool stats) {
     // ~64K floats per block at large batch, but never fewer than ~1000 blocks in flight at small batch.
     // stats: one block per ~8K floats at most (128 blocks at least): every block of the statistics pass ends in 2 x groups fp64 atomics on
     // the SAME addresses, and a thousand blocks of 19 pixels each (a 32-channel head tensor of one frame) spent 16-25 us queueing on them
@@ -270,7 +283,8 @@ int launch_zero(void* p, size_t bytes, hipStream_t st) {
 }
 
 int launch_gn_stats(const View& in, int B, int G, int groups, double* stats, hipStream_t st, bool zero) {
-    if (groups > 64 || in.C % groups || in.C % 4) return fail("groupnorm: unsupported channel/group count");
+    if (groups < 1 || groups > 64 || in.C % groups || in.C % 4) return fail("groupnorm: unsupported channel/group count");
+    if (!quads_ok(in)) return fail("groupnorm: channels must come in aligned groups of 4");
     const int HW = in.H * in.W;
     if (zero) {
         const int rc = launch_zero(stats, sizeof(double) * 2 * groups * B * G, st);
@@ -368,6 +382,8 @@ int launch_gn_apply(const View& in, const View& out, int B, int G, int groups, c
     const int ppb = gn_pixels_per_block(HW, in.C, B, G);
     ProfScope prof("gn_apply", 2.0 * in.es * G * B * (double)HW * in.C, 0.0, st);
     if (in.es != out.es) return fail("groupnorm: mixed element types");
+    if (groups < 1 || in.C % groups) return fail("groupnorm: unsupported channel/group count");
+    if (!quads_ok(in) || !quads_ok(out) || in.C != out.C) return fail("groupnorm: channels must come in aligned groups of 4");
     const dim3 grid((HW + ppb - 1) / ppb, B, G);
     if (in.es == 2) {
         const bool wide = in.C % 8 == 0 && in.cs % 8 == 0 && out.cs % 8 == 0 && (in.gs & 7) == 0 && (out.gs & 7) == 0 &&
@@ -430,6 +446,7 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const T* __restrict__ in,
 int launch_bilinear(const View& in, const View& out, int B, hipStream_t st) {
     ProfScope prof("bilinear", (double)in.es * B * in.C * ((double)in.H * in.W + (double)out.H * out.W), 0.0, st);
     if (in.es != out.es) return fail("bilinear: mixed element types");
+    if (!quads_ok(in) || !quads_ok(out) || in.C != out.C) return fail("bilinear: channels must come in aligned groups of 4");
     const float sy = (float)in.H / (float)out.H, sx = (float)in.W / (float)out.W;
     if (in.es == 2) {
         const bool wide = in.C % 8 == 0 && in.cs % 8 == 0 && out.cs % 8 == 0 && (((uintptr_t)in.p | (uintptr_t)out.p) & 15) == 0;
@@ -487,8 +504,8 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const T* __restrict__ in, 
 }
 
 int launch_avgpool(const View& in, const View& out, int B, hipStream_t st) {
-    if (in.C % 4 || in.cs % 4 || ((uintptr_t)in.p & 15)) return fail("avgpool: channels must come in aligned groups of 4");
     if (in.es != out.es) return fail("avgpool: mixed element types");
+    if (!quads_ok(in)) return fail("avgpool: channels must come in aligned groups of 4");      // (the means are stored one by one: any `out`)
     ProfScope prof("avgpool", (double)in.es * B * in.C * ((double)in.H * in.W + 1.0), 0.0, st);
     if (in.es == 2)
         hipLaunchKernelGGL(avgpool_kernel<half_t>, dim3((in.C + 63) / 64, B), dim3(256), 0, st, cptr<half_t>(in), (half_t*)out.p,
@@ -550,9 +567,12 @@ __global__ void predictor_kernel(const PredHeads hs, int in_cs, float* __restric
 int launch_predictors(const PredHeads& hs, int C, int in_cs, int es, int H, int W, float* q, int q_nch, int sm_cs, int B, hipStream_t st) {
     // hs.sm[j]: a channel slice of an activation buffer - same element type as the head features
     if ((C != 32 && C != 64) || hs.n < 1 || hs.n > 5) return fail("predictor: expects 32 or 64 input channels and 1..5 heads");
+    if ((es != 4 && es != 2) || in_cs % 4) return fail("predictor: features must come in aligned groups of 4");
     double couts = 0.0, acts = 0.0;
     for (int j = 0; j < hs.n; ++j) {
-        if (hs.cout[j] > 4) return fail("predictor: at most 4 outputs per head");
+        if (hs.cout[j] < 1 || hs.cout[j] > 4) return fail("predictor: 1..4 outputs per head");
+        if (hs.q_ch0[j] < 0 || hs.q_ch0[j] + hs.cout[j] > q_nch) return fail("predictor: logit planes outside q");
+        if ((uintptr_t)hs.in[j] & (uintptr_t)(4 * es - 1)) return fail("predictor: features must come in aligned groups of 4");
         couts += hs.cout[j];
         if (hs.sm[j]) acts += hs.cout[j];
     }
@@ -595,6 +615,7 @@ int launch_add_channels(const View& a, const View& b, const View& out, int B, hi
     const long pixels = (long)B * a.H * a.W;
     ProfScope prof("add_channels", 3.0 * a.es * pixels * a.C, 0.0, st);
     if (a.es != b.es || a.es != out.es) return fail("add: mixed element types");
+    if (!quads_ok(a) || !quads_ok(b) || !quads_ok(out) || a.C != b.C || a.C != out.C) return fail("add: channels must come in aligned groups of 4");
     if (a.es == 2)
         hipLaunchKernelGGL(add_channels_kernel<half_t>, dim3(cap_grid(pixels * (a.C / 4), 256)), dim3(256), 0, st, cptr<half_t>(a),
                            cptr<half_t>(b), (half_t*)out.p, pixels, a.C / 4, a.cs, b.cs, out.cs);
@@ -609,6 +630,7 @@ int launch_copy_channels(const View& in, const View& out, int B, hipStream_t st)
     const long pixels = (long)B * in.H * in.W;
     ProfScope prof("copy_channels", 2.0 * in.es * pixels * in.C, 0.0, st);
     if (in.es != out.es) return fail("copy: mixed element types");
+    if (!quads_ok(in) || !quads_ok(out) || in.C != out.C) return fail("copy: channels must come in aligned groups of 4");
     if (in.es == 2)
         hipLaunchKernelGGL(copy_channels_kernel<half_t>, dim3(cap_grid(pixels * (in.C / 4), 256)), dim3(256), 0, st, cptr<half_t>(in),
                            (half_t*)out.p, pixels, in.C / 4, in.cs, out.cs);
