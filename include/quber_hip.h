@@ -282,6 +282,34 @@ int quber_cleanup_postprocess(quber_ctx* ctx, const float* dev_logits, int32_t n
                               int32_t connectivity, int32_t keep_largest, int32_t min_island_area, int32_t max_hole_area,
                               uint32_t* dev_report, void* stream);
 
+/* Perturbed initial masks (csrc/perturb.hip): the reference's perturb_seg (tools/ours/perturbation_utils.py:39-71) - a random walk of
+ * erosions and dilations on random sub-rectangles of a mask, until its IoU with the mask it started from falls below a target - on
+ * masks that are already on the device, one workgroup per mask, the mask kept on chip for the whole walk.  The number of random draws
+ * per operation does not depend on the data: the host draws the walk (quber_amd/perturb.py: perturb_program, the reference's order of
+ * draws) and this call executes it.  The numpy statement of what it computes is tests/test_perturb_cpu.py: perturb_np.
+ *   dev_masks u8 [B][n_masks][H][W] in; seg = mask > 127 is what is perturbed, g = mask != 0 what the IoU is taken against
+ *   dev_programs i32 [B][n_masks][n_ops][8], rows (lx, ly, lw, lh, clear, dilate, size, choice); n_ops a multiple of ops_per_round
+ *     (the reference: 4 operations per round, 250 rounds).  An operation: if clear, pixel (int((ly + lh) / 2), int((lx + lw) / 2))
+ *     becomes 0; then seg[ly:lh, lx:lw] is replaced by its dilation (dilate != 0) or erosion with the structuring element
+ *     cv::getStructuringElement gives for choice 1 (rectangle size x size), 2, 3, 4 (ellipse of width x height = size x size,
+ *     size x size/2, size/2 x size), computed INSIDE the rectangle: beyond it a dilation sees 0 and an erosion 1 (OpenCV's default
+ *     border on an isolated sub-matrix); dst(x, y) = max / min over the set (i, j) of src(x + j - kw/2, y + i - kh/2).
+ *     Rectangles are clipped to the frame, sizes clamped to 1..15 (a half size to >= 1), any other choice is a rectangle: no program
+ *     can write outside its mask.
+ *   dev_iou_targets f64 [B][n_masks]: after every round iou = (|seg & g| + 1e-6) / (|seg | g| + 1e-6) in float64; the walk of a mask
+ *     stops after the first round with iou < target.  H <= 2 or W <= 2: no round (perturb_seg's "rare case").
+ *   -> dev_out u8 [B][n_masks][H][W], 0 / 255, any alignment; must not overlap dev_masks (error)
+ *   -> dev_report u32 [B][n_masks][4] (may be NULL): rounds executed, |seg & g|, |seg | g|, |seg| after the last executed round.
+ * placement: where the three bit planes (seg, scratch, g; rows padded to 32-bit words) live - 1 = LDS, an error when
+ * 12 * H * ceil(W / 32) + 512 bytes exceed the 160 KB a workgroup may declare (640 x 480: 113 KB); 2 = a per-mask workspace in device
+ * memory, any frame size; 0 = LDS when it fits.  Both compute the same bits.  The device-memory workspace (12 * H * ceil(W / 32)
+ * bytes per mask) is not part of quber_create: the first call that needs it (and one that needs a larger one) allocates it, so that
+ * call is not capturable into a graph; later calls are.  No host copy, no memset node; outputs are overwritten.  Works on a context
+ * created with with_network = 0; n_masks is not bounded by max_instances. */
+int quber_perturb_masks(quber_ctx* ctx, const uint8_t* dev_masks, int32_t batch, int32_t n_masks, const int32_t* dev_programs,
+                        int32_t n_ops, int32_t ops_per_round, const double* dev_iou_targets, uint8_t* dev_out, uint32_t* dev_report,
+                        int32_t placement, void* stream);
+
 /* evaluation support - all pairwise overlap counts of two label maps in one pass.  Replaces the per-pair
  * np.count_nonzero loops of eval/evaluation.py:180-199 (multilabel_metrics).
  *   dev_pred, dev_gt i32 [n_pixels], label values in 0..65535, at most `cap` (<= 1024) distinct values per map

@@ -119,6 +119,7 @@ void quber_destroy(quber_ctx* c) {
         if (c->lane_stream[l]) (void)hipStreamDestroy(c->lane_stream[l]);
     }
     for (void* p : c->allocs) (void)hipFree(p);
+    if (c->perturb_ws) (void)hipFree(c->perturb_ws);
     delete c;
 }
 
@@ -490,6 +491,37 @@ int quber_cleanup_postprocess(quber_ctx* c, const float* logits, int32_t n_plane
     return launch_cleanup_postprocess(logits, n_planes, batch, c->cfg.height, c->cfg.width, c->cfg.top_k, c->cfg.label_divisor, panoptic, labels, count, scores,
                                       boxes, connectivity, keep_largest, min_island_area, max_hole_area, c->cleanup_ws, report,
                                       (hipStream_t)stream);
+}
+
+// ---- perturbed initial masks (perturb.hip); usable on a context without a network ----
+int quber_perturb_masks(quber_ctx* c, const uint8_t* masks, int32_t batch, int32_t n_masks, const int32_t* programs, int32_t n_ops,
+                        int32_t ops_per_round, const double* iou_targets, uint8_t* out, uint32_t* report, int32_t placement, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_masks < 0) return fail("perturb: negative n_masks");
+    if (placement < 0 || placement > 2) return fail("perturb: placement must be 0 (auto), 1 (LDS) or 2 (device memory)");
+    if (n_masks == 0) return 0;
+    if (!masks || !out || !iou_targets || (!programs && n_ops > 0)) return fail("perturb: null tensor");
+    const int H = c->cfg.height, W = c->cfg.width;
+    const long M = (long)batch * n_masks;
+    const size_t bytes = (size_t)M * H * W;
+    if (out < masks + bytes && masks < out + bytes) return fail("perturb: dev_out overlaps dev_masks");
+    const bool fits = perturb_fits_lds(H, W);
+    if (placement == 1 && !fits) return fail("perturb: three bit planes of this frame do not fit the 160 KB of LDS a workgroup may declare");
+    const bool lds = placement == 1 || (placement == 0 && fits);
+    if (!lds) {          // the only allocation of this entry: made on first use, kept, grown when a larger batch comes
+        const size_t need = perturb_ws_bytes(M, H, W);
+        if (need > c->perturb_ws_bytes) {
+            if (c->perturb_ws) {
+                QB_CHECK(hipFree(c->perturb_ws));            // (waits for the launches that may still use it)
+                c->alloc_bytes -= c->perturb_ws_bytes;
+                c->perturb_ws = nullptr; c->perturb_ws_bytes = 0;
+            }
+            QB_CHECK(hipMalloc(&c->perturb_ws, need));
+            c->perturb_ws_bytes = need;
+            c->alloc_bytes += need;
+        }
+    }
+    return launch_perturb(masks, M, H, W, programs, n_ops, ops_per_round, iou_targets, out, report, lds ? 1 : 0, c->perturb_ws, (hipStream_t)stream);
 }
 
 int64_t quber_contingency_workspace_bytes(int32_t cap) { return (int64_t)contingency_ws_bytes(cap); }

@@ -336,6 +336,12 @@ int launch_cleanup_postprocess(const float* logits, int nch, int B, int H, int W
                                float* scores, float* boxes, int conn, int keep_largest, int min_island, int max_hole, void* ws,
                                unsigned* report, hipStream_t st);
 size_t cleanup_ws_bytes(int B, int H, int W, int cap);
+// perturbed initial masks (perturb.hip): the host-drawn walk of erosions / dilations of every mask, one workgroup per mask; lds: the
+// bit planes in LDS (perturb_fits_lds), else in `ws` (perturb_ws_bytes for >= n_masks masks)
+int launch_perturb(const uint8_t* masks, long n_masks, int H, int W, const int* programs, int n_ops, int ops_per_round, const double* targets,
+                   uint8_t* out, unsigned* report, int lds, void* ws, hipStream_t st);
+bool perturb_fits_lds(int H, int W);
+size_t perturb_ws_bytes(long n_masks, int H, int W);
 int launch_group_pixels(const float* logits, int nch, int B, int H, int W, int cap, const int* centers, const int* ncenters,
                         uint8_t* idmap, unsigned* area, hipStream_t st);
 

@@ -75,6 +75,8 @@ struct quber_ctx {
     uint8_t* err_ws = nullptr;
     void* post_ws = nullptr;
     void* cleanup_ws = nullptr;   // parent map, per-root tables, per-instance keys of the connected-component clean-up (cleanup.hip)
+    void* perturb_ws = nullptr;   // bit planes of quber_perturb_masks in its device-memory placement: allocated on first use, grown on demand
+    size_t perturb_ws_bytes = 0;
     double* gn_stats = nullptr;   // [GN_SLOTS][launch group <= 4][max_batch][32 groups][sum, sum of squares]
     int gn_slots = 0;
     float* splitk_ws = nullptr;

@@ -488,6 +488,28 @@ class Engine:
                                                       _ptr(post["scores"]), _ptr(post["boxes"]), *opts.args(), _ptr(out), _stream()))
         return out
 
+    # ---- perturbed initial masks on the device (csrc/perturb.hip; INTEGRATION.md "Perturbed initial masks") ----
+    def perturb_masks(self, masks, programs, targets, out=None, report=None, placement=0):
+        """masks u8 [B,N,H,W], programs i32 [B,N,n_ops,8] (perturb.perturb_program; four operations per round), targets f64 [B,N], all on
+        the device -> (perturbed masks u8 [B,N,H,W] of 0 / 255, report i32 [B,N,4]: rounds executed, |seg & g|, |seg | g|, |seg|).
+        `out` must not overlap `masks`.  placement: 0 auto, 1 the bit planes in LDS (an error when the frame does not fit), 2 in device
+        memory (allocated by the first call that needs it: that call cannot be captured into a graph)."""
+        from .perturb import OPS_PER_ROUND
+        B, N = masks.shape[:2]
+        assert masks.dtype == torch.uint8 and masks.is_contiguous() and masks.shape == (B, N, self.H, self.W)
+        assert programs.dtype == torch.int32 and programs.is_contiguous() and programs.dim() == 4 and programs.shape[:2] == (B, N) and programs.shape[3] == 8
+        assert targets.dtype == torch.float64 and targets.is_contiguous() and targets.shape == (B, N)
+        if out is None:
+            out = torch.empty_like(masks)
+        if report is None:
+            report = torch.empty((B, N, 4), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == masks.shape
+        assert report.dtype == torch.int32 and report.is_contiguous() and report.shape == (B, N, 4)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_perturb_masks(self.h, _ptr(masks), B, N, _ptr(programs), programs.shape[2], OPS_PER_ROUND, _ptr(targets),
+                                                    _ptr(out), _ptr(report), int(placement), _stream()))
+        return out, report
+
     def extract_masks(self, post, max_inst, out=None):
         B = post["panoptic"].shape[0]
         if out is None:

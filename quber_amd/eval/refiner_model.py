@@ -78,7 +78,7 @@ def resize_shortest_edge_shape(oldh, oldw, short_edge_length=800, max_size=1333)
 class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
                  lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
-                 decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None):
+                 decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None):
         # tta: every frame and its W-mirror in one forward, logits merged on the device (MaskRefinerPredictor(tta=True))
         # decode_errors: the error heads' class maps, histograms and per-mask class counts in every output dict
         # iterations / until_converged / track_initial: the refined masks fed back for further passes on the device, early stop at a
@@ -86,9 +86,12 @@ class MaskRefiner:
         # output dict (INTEGRATION.md "Iterative refinement")
         # cleanup: None, a quber_amd.cleanup.Cleanup, "largest" (the UOIS path's largest_connected_component, 4-connected) or "holes"
         # (the SAM refiner's remove_small_regions(mask, 300, "holes")), applied on the device after post-processing
+        # perturb: None or a quber_amd.perturb.Perturb - the initial masks degraded by the reference's perturb_seg on the device before
+        # they are encoded (INTEGRATION.md "Perturbed initial masks"); predict() and predict_stream(batch=k) alike
         self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, tta=tta,
                                                       decode_errors=decode_errors, iterations=iterations,
-                                                      until_converged=until_converged, track_initial=track_initial, cleanup=cleanup)
+                                                      until_converged=until_converged, track_initial=track_initial, cleanup=cleanup,
+                                                      perturb=perturb)
         self.dataset = dataset
         self.lmffnet = None
         # "host" / True (default): csrc/inpaint.hip on the calling (worker) thread; "device": csrc/inpaint_dev.hip, bit-equal, for hosts

@@ -21,6 +21,12 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
   * ``cleanup=Cleanup(...)`` / ``"largest"`` / ``"holes"``: the connected-component clean-up the reference's competing refiners run on
     the host (largest component, small holes), on the device right after post-processing (csrc/cleanup.hip; INTEGRATION.md
     "Connected-component clean-up"); ``instances`` gains ``cc_components`` / ``cc_removed`` / ``cc_filled``.  Default: none, today's keys.
+  * ``perturb=Perturb(iou_target, seed=...)``: the uploaded initial masks are degraded on the device by the reference's ``perturb_seg``
+    (a random walk of erosions / dilations until the IoU with the uploaded mask falls below the target: csrc/perturb.hip; INTEGRATION.md
+    "Perturbed initial masks") before anything reads them - the encoding, the mirror of ``tta``, the first pass of ``iterations=k``
+    (never the fed-back masks), ``track_initial``, the per-mask histograms.  Every dict gains ``perturbed_masks`` (u8 [n,H,W], 0 / 255)
+    and ``perturb_report`` (i64 [n,4]: rounds, |seg & g|, |seg | g|, |seg|).  uint8 masks are perturbed as their bytes stand (> 127 is
+    the mask, non-zero the ground truth), bool masks count as 0 / 255.  Default: none, today's keys.
 There is no CPU fallback: construction fails if the HIP library or a GPU is missing.
 """
 import os
@@ -31,6 +37,7 @@ import torch
 
 from .. import arch, config as qconfig, engine as qengine
 from ..cleanup import Cleanup
+from ..perturb import Perturb
 from ..structures import Boxes, Instances
 
 LABEL_DIVISOR = 1000  # maskrefiner/data/datasets/register_uoais_sim_panoptic.py:177-186
@@ -114,9 +121,14 @@ class RefinerModel:
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
     def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False, iterations=1, until_converged=False,
-                 track_initial=False, cleanup=None):
+                 track_initial=False, cleanup=None, perturb=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
+        if perturb is not None and not isinstance(perturb, Perturb):
+            raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
+        # the initial masks degraded on the device before anything reads them (INTEGRATION.md "Perturbed initial masks"); None: as uploaded
+        self.perturb = perturb
+        self._perturb_dev = {}    # (frames, masks, H, W) -> the programs and targets of such a call on the device
         # connected-component clean-up of the instances right after every post-processing pass (INTEGRATION.md): None, a Cleanup,
         # "largest" or "holes"; everything downstream - masks, the feed-back of a further pass, tracking - sees the cleaned instances
         self.cleanup = Cleanup.parse(cleanup)
@@ -183,6 +195,24 @@ class RefinerModel:
         if self.cleanup is not None:
             post["cc_report"] = eng.cleanup_post(logits, post, self.cleanup, post.get("cc_report"))
         return post
+
+    def perturb_masks(self, eng, d_masks, B):
+        """perturb: the first B frames of d_masks u8 [>= B,N,H,W] (device) are replaced by their perturbed versions, in place as far as
+        the caller can tell (the kernel writes a fresh tensor, which is copied back and returned for the output dicts).
+        -> (perturbed u8 [B,N,H,W], report i32 [B,N,4]) or None."""
+        if self.perturb is None or d_masks is None or d_masks.shape[1] == 0:
+            return None
+        N, key = d_masks.shape[1], (B, d_masks.shape[1], eng.H, eng.W)
+        if key not in self._perturb_dev:
+            if len(self._perturb_dev) >= 8:
+                self._perturb_dev.pop(next(iter(self._perturb_dev)))
+            self._perturb_dev[key] = (torch.from_numpy(self.perturb.programs(B, N, eng.H, eng.W).copy()).to(self.device),
+                                      torch.from_numpy(self.perturb.targets(B, N)).to(self.device))
+        prog, tgt = self._perturb_dev[key]
+        src = d_masks[:B]
+        out, rep = eng.perturb_masks(src, prog, tgt)
+        src.copy_(out)
+        return out, rep
 
     # -- device-side pipeline on already-resident tensors --
     def run(self, bgr, depth, offsets):
@@ -281,11 +311,12 @@ class RefinerModel:
         ids = it["ids"] if it is not None else eng.relabel_panoptic(post)
         return eng.overlap_masks(d_masks, ids, eng.cap, out=out)
 
-    def frame_dict(self, eng, logits_b, post, b, k, masks_b, err=None, n_masks=None, it=None, conv=0, ov=None, n_own=None):
+    def frame_dict(self, eng, logits_b, post, b, k, masks_b, err=None, n_masks=None, it=None, conv=0, ov=None, n_own=None, pt=None):
         """The reference's output dict of one frame (model.py:304-356) from the device-side results.  err: what decode() returned
         for the batch; n_masks: the frame's own initial masks (the leading rows of its mask histogram and of initial_overlap);
         it / conv: what refine() returned and the frame's refine_converged_at on the host; ov: what track() returned; n_own: per frame
-        of the batch, the rows of initial_overlap where n_masks is not given (collect_batch: the mask histogram keeps all N rows)."""
+        of the batch, the rows of initial_overlap where n_masks is not given (collect_batch: the mask histogram keeps all N rows);
+        pt: what perturb_masks() returned."""
         qc = eng.qcfg
         ncls, o = qc.error_classes, 4
         r = {"sem_seg": logits_b[0:1], "panoptic_seg": (post["panoptic"][b], None)}
@@ -298,6 +329,9 @@ class RefinerModel:
             r[head + "_classes"], r[head + "_hist"] = cls[b], hist[b]
             if mh is not None:
                 r[head + "_mask_hist"] = mh[b] if n_masks is None else mh[b, :n_masks]
+        if pt is not None:
+            n = n_masks if n_masks is not None else int(n_own[b]) if n_own is not None else pt[0].shape[1]
+            r["perturbed_masks"], r["perturb_report"] = pt[0][b, :n], pt[1][b, :n].to(torch.int64)
         if it is not None:
             r["refine_passes"], r["refine_converged_at"] = it["passes"], int(conv)
         if ov is not None:
@@ -318,7 +352,7 @@ class RefinerModel:
             r["instances"] = inst
         return r
 
-    def results(self, eng, logits, post, d_masks=None, n_masks=None, it=None, ov=None):
+    def results(self, eng, logits, post, d_masks=None, n_masks=None, it=None, ov=None, pt=None):
         """One D2H of the small per-frame tables, then mask extraction for exactly max(count) slots.  d_masks / n_masks (decode_errors):
         the initial masks on the device and how many of them are each frame's own.  it / ov: what refine() / track() returned."""
         B = logits.shape[0]
@@ -328,7 +362,7 @@ class RefinerModel:
         kmax = int(count.max()) if B else 0
         masks = eng.extract_masks(post, kmax) if kmax > 0 else None
         return [self.frame_dict(eng, logits[b], post, b, int(count[b]), masks[b, :int(count[b])].bool() if count[b] > 0 else None,
-                                err, None if n_masks is None else n_masks[b], it, conv[b], ov)
+                                err, None if n_masks is None else n_masks[b], it, conv[b], ov, None, pt)
                 for b in range(B)]
 
     def predict_one(self, bgr, depth, masks):
@@ -368,6 +402,7 @@ class RefinerModel:
         d_bgr = stg.dev_in[:3 * f * hw].view(f, H, W, 3)
         d_dep = stg.dev_in[od:od + 3 * f * hw].view(f, H, W, 3) if two else None
         d_masks = stg.dev_in[om:om + f * n * hw].view(f, n, H, W)
+        pt = self.perturb_masks(eng, d_masks, 1)          # before the mirror, the encoding and everything else that reads the masks
         if f == 2:
             logits = self.tta_logits(eng, d_bgr, d_dep, d_masks, stg.offsets)     # merged: owned by the caller through the dict
         else:
@@ -396,7 +431,7 @@ class RefinerModel:
             masks_b = eng.extract_masks(post, k)[0].view(torch.bool)      # the kernel writes 0 / 1 bytes
         # (the caller's ``.to('cpu')`` of the masks is a plain D2H copy into fresh pageable memory: 0.17 ms for 5 MB, which a
         # prefetch into a pinned buffer plus the copy out of it does not beat - tools/predict_profile.py)
-        return self.frame_dict(eng, logits[0], post_out, 0, k, masks_b, err, None, it, int(stg.pin_count[1]) if it is not None else 0, ov)
+        return self.frame_dict(eng, logits[0], post_out, 0, k, masks_b, err, None, it, int(stg.pin_count[1]) if it is not None else 0, ov, None, pt)
 
     # -- batched form on device-resident frames, split into "enqueue" and "collect" so that a caller can keep one batch in flight --
     def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None):
@@ -413,9 +448,10 @@ class RefinerModel:
         eng = self.engine_for(H, W, f * max(B, capacity), d_masks.shape[1])      # (`capacity`: the caller's batch size - a short last batch must not rebuild)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
+        if self.tta and not halves:
+            d_bgr, d_depth, d_masks = self.tta_buffers(d_bgr, d_depth, d_masks)
+        pt = self.perturb_masks(eng, d_masks, B)          # (in the caller's tensor, unless tta_buffers has just copied it)
         if self.tta:
-            if not halves:
-                d_bgr, d_depth, d_masks = self.tta_buffers(d_bgr, d_depth, d_masks)
             logits = self.tta_logits(eng, d_bgr, d_depth, d_masks)
         else:
             if d_masks.shape[1]:
@@ -438,7 +474,7 @@ class RefinerModel:
         eng._in_flight = getattr(eng, "_in_flight", 0) + 1
         return {"eng": eng, "logits": logits, "post": post, "masks": masks, "slots": slots, "count": count, "e0": e0, "e1": e1,
                 "err": err, "it": it, "conv": pinned[1], "ov": ov,
-                "n_masks": n_masks}
+                "n_masks": n_masks, "pt": pt}
 
     def collect_batch(self, hd, host_masks=False):
         """-> (list of the reference's per-frame output dicts, device milliseconds of the whole batch[, per-frame numpy masks]).
@@ -455,7 +491,7 @@ class RefinerModel:
             ready = torch.cuda.Event()
             ready.record()
         outs = [self.frame_dict(eng, hd["logits"][b], post, b, int(count[b]), masks[b, :int(count[b])].view(torch.bool) if count[b] > 0 else None,
-                                hd.get("err"), None, hd.get("it"), conv[b], hd.get("ov"), hd.get("n_masks"))
+                                hd.get("err"), None, hd.get("it"), conv[b], hd.get("ov"), hd.get("n_masks"), hd.get("pt"))
                 for b in range(len(count))]
         ms = hd["e0"].elapsed_time(hd["e1"])
         eng._in_flight = max(0, getattr(eng, "_in_flight", 1) - 1)
@@ -523,9 +559,12 @@ class RefinerModel:
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
                  seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False,
-                 cleanup=None):
+                 cleanup=None, perturb=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
+        if perturb is not None and not isinstance(perturb, Perturb):
+            raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
+        self.perturb = perturb                        # the initial masks degraded on the device before they are encoded; None: as uploaded
         self.cleanup = Cleanup.parse(cleanup)         # the connected-component clean-up after post-processing; None: none
         if config_file is None:
             self.cfg = qconfig.canonical_cfg()
@@ -558,13 +597,16 @@ class MaskRefinerPredictor:
         # predict() / predict_batch() stop at a fixed point; track_initial: initial_overlap / initial_index / initial_iou in every dict
         self.iterations, self.until_converged, self.track_initial = int(iterations), bool(until_converged), bool(track_initial)
         self.model = RefinerModel(self.cfg, sd, device, tta=self.tta, decode_errors=self.decode_errors, iterations=self.iterations,
-                                  until_converged=self.until_converged, track_initial=self.track_initial, cleanup=self.cleanup)
+                                  until_converged=self.until_converged, track_initial=self.track_initial, cleanup=self.cleanup,
+                                  perturb=self.perturb)
         self.device = torch.device(device)
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
     # -- reference signature (predictor.py:287) --
     def predict(self, rgb_img, depth_img=None, perturbed_masks=None):
         masks = np.zeros((0,) + rgb_img.shape[:2], np.uint8) if perturbed_masks is None else np.asarray(perturbed_masks)
+        if self.perturb is not None and masks.dtype == np.bool_:
+            masks = masks.view(np.uint8) * np.uint8(255)          # perturb_seg thresholds at 127: a bool mask counts as 0 / 255
         if not self.fast_path or masks.dtype not in (np.uint8, np.bool_) or masks.ndim != 3:
             return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks])
         if self.depth_on and depth_img is None:
@@ -588,7 +630,11 @@ class MaskRefinerPredictor:
         mk = np.zeros((B, n, H, W), np.uint8)
         for b, m in enumerate(masks_list):
             if len(m):
-                mk[b, :len(m)] = np.asarray(m) != 0
+                m = np.asarray(m)
+                if self.perturb is None:
+                    mk[b, :len(m)] = m != 0
+                else:                                     # perturb_seg reads the bytes: uint8 as they stand, anything else as 0 / 255
+                    mk[b, :len(m)] = m if m.dtype == np.uint8 else (m != 0) * np.uint8(255)
         dev = self.device
         eng = self.model.engine_for(H, W, 2 * B if self.tta else B, n)
         if self.tta:                                      # uploaded straight into the first halves of the 2B-frame buffers
@@ -597,14 +643,16 @@ class MaskRefinerPredictor:
             if depth is not None:
                 depth[:B].copy_(torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)))
             d_masks[:B].copy_(torch.from_numpy(mk))
+            pt = self.model.perturb_masks(eng, d_masks, B)
             logits = self.model.tta_logits(eng, bgr, depth, d_masks)
         else:
             d_masks = torch.from_numpy(mk).to(dev)
             bgr = torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)).to(dev)
             depth = None if depth_imgs is None else torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)).to(dev)
+            pt = self.model.perturb_masks(eng, d_masks, B)
             offsets = eng.encode(d_masks)
             logits = eng.forward(bgr, depth, offsets)
         post = self.model.postprocess(eng, logits)
         logits, post, it = self.model.refine(eng, bgr, depth, logits, post, B, True)
         ov = self.model.track(eng, d_masks[:B], post, it)
-        return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list], it, ov)
+        return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list], it, ov, pt)
