@@ -310,6 +310,32 @@ int quber_perturb_masks(quber_ctx* ctx, const uint8_t* dev_masks, int32_t batch,
                         int32_t n_ops, int32_t ops_per_round, const double* dev_iou_targets, uint8_t* dev_out, uint32_t* dev_report,
                         int32_t placement, void* stream);
 
+/* Mask NMS (csrc/masknms.hip): scored, overlapping, possibly duplicated initial masks made disjoint on the device - the reference's
+ * nms + combine_masks_with_NMS, which it runs on the host in numpy at eval/refiner_model.py:683-740, eval/base_model.py:1027-1086 and
+ * eval/base_model.py:1154-1190 (one full-frame np.multiply + np.sum per pair of masks).  The numpy statement of what this call computes
+ * is tests/test_masknms_cpu.py: mask_nms_np; INTEGRATION.md "Overlapping initial masks" has it in words.
+ *   dev_masks u8 [B][n_masks][H][W] in (non-zero = inside), dev_scores f32 [B][n_masks] in; a mask whose score is NaN is absent (never
+ *     visited, never kept, never a source): the padding of a frame that has fewer masks than n_masks
+ *   inter[i][j] = pixels inside both masks, area[i] = inter[i][i].  Masks are visited by score, descending, among equal scores the
+ *     higher index first; a visited mask that is still alive is kept and every later alive j stays alive iff
+ *     inter / ((area_i + area_j) - inter) <= thresh, evaluated in float32 in that order (a NaN - two empty masks - suppresses).
+ *   The survivors are painted into one map, later over earlier, in the order (area ascending, visit position ascending) for
+ *     on_top = 0 ("large", the reference) or in the reverse of it for on_top = 1 ("small"); id = 1 + position in that order.
+ *   -> dev_out_masks u8 [B][n_masks][H][W]: map == id for the ids still visible, in ascending id, 0 / 255, zero planes behind count.
+ *      May be dev_masks itself (only the first launch reads the input); any other overlap is an error.
+ *   -> dev_ids i32 [B][H][W]: 0 or the 1-based index of the output mask that owns the pixel
+ *   -> dev_source i32 [B][n_masks]: the input index of each output mask, -1 behind count
+ *   -> dev_out_scores f32 [B][n_masks]: the output masks' scores, 0 behind count
+ *   -> dev_report i32 [B][4]: count, kept (NMS survivors, before hidden ones drop out), 0, 0
+ * Every output is overwritten by every call.  n_masks <= min(max_instances, 1024); H * W <= 2^24 (counts are compared in float32).
+ * Launches (pack, zero, gram, select, paint, compaction, write) on `stream`; no host copy, no synchronisation, no memset node.  The
+ * workspace (bit planes, pair table, rank map, per-frame tables, sized for max_batch x min(max_instances, 1024) masks) is not part of
+ * quber_create: the FIRST call with n_masks > 0 allocates it and keeps it (quber_workspace_bytes counts it from then on), so that
+ * call is not capturable into a graph; later calls are.  Works on a context created with with_network = 0. */
+int quber_mask_nms(quber_ctx* ctx, const uint8_t* dev_masks, const float* dev_scores, int32_t batch, int32_t n_masks, float thresh,
+                   int32_t on_top, uint8_t* dev_out_masks, int32_t* dev_ids, int32_t* dev_source, float* dev_out_scores,
+                   int32_t* dev_report, void* stream);
+
 /* evaluation support - all pairwise overlap counts of two label maps in one pass.  Replaces the per-pair
  * np.count_nonzero loops of eval/evaluation.py:180-199 (multilabel_metrics).
  *   dev_pred, dev_gt i32 [n_pixels], label values in 0..65535, at most `cap` (<= 1024) distinct values per map

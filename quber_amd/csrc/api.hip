@@ -120,6 +120,7 @@ void quber_destroy(quber_ctx* c) {
     }
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->perturb_ws) (void)hipFree(c->perturb_ws);
+    if (c->masknms_ws) (void)hipFree(c->masknms_ws);
     delete c;
 }
 
@@ -522,6 +523,29 @@ int quber_perturb_masks(quber_ctx* c, const uint8_t* masks, int32_t batch, int32
         }
     }
     return launch_perturb(masks, M, H, W, programs, n_ops, ops_per_round, iou_targets, out, report, lds ? 1 : 0, c->perturb_ws, (hipStream_t)stream);
+}
+
+// ---- mask NMS of scored, overlapping initial masks (masknms.hip); usable on a context without a network ----
+int quber_mask_nms(quber_ctx* c, const uint8_t* masks, const float* scores, int32_t batch, int32_t n_masks, float thresh, int32_t on_top,
+                   uint8_t* out_masks, int32_t* ids, int32_t* source, float* out_scores, int32_t* report, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    const int limit = std::min(c->cfg.max_instances, mask_nms_max());
+    if (n_masks < 0 || n_masks > limit) return fail("mask nms: n_masks outside 0..min(max_instances, 1024)");
+    if (on_top != 0 && on_top != 1) return fail("mask nms: on_top must be 0 (large) or 1 (small)");
+    if (!(thresh == thresh)) return fail("mask nms: thresh is not a number");
+    const int H = c->cfg.height, W = c->cfg.width;
+    if ((long)H * W > (1L << 24)) return fail("mask nms: a frame of more than 2^24 pixels (the overlap counts are compared in float32)");
+    if (!ids || !report || (n_masks > 0 && (!masks || !scores || !out_masks || !source || !out_scores))) return fail("mask nms: null tensor");
+    const size_t bytes = (size_t)batch * n_masks * H * W;
+    if (out_masks != masks && out_masks < masks + bytes && masks < out_masks + bytes) return fail("mask nms: dev_out_masks overlaps dev_masks partially");
+    if (n_masks > 0 && !c->masknms_ws) {     // the only allocation of this entry: made by the first call, for max_batch x limit masks, and kept
+        const size_t need = mask_nms_ws_bytes(c->cfg.max_batch, limit, H, W);
+        QB_CHECK(hipMalloc(&c->masknms_ws, need));
+        c->masknms_ws_bytes = need;
+        c->alloc_bytes += need;
+    }
+    return launch_mask_nms(masks, scores, batch, n_masks, H, W, thresh, on_top, out_masks, ids, source, out_scores, report, c->masknms_ws,
+                           (hipStream_t)stream);
 }
 
 int64_t quber_contingency_workspace_bytes(int32_t cap) { return (int64_t)contingency_ws_bytes(cap); }

@@ -342,6 +342,12 @@ int launch_perturb(const uint8_t* masks, long n_masks, int H, int W, const int* 
                    uint8_t* out, unsigned* report, int lds, void* ws, hipStream_t st);
 bool perturb_fits_lds(int H, int W);
 size_t perturb_ws_bytes(long n_masks, int H, int W);
+// mask NMS of scored, overlapping masks (masknms.hip): pack -> gram -> select -> paint -> compaction and write, all on `st`; ws:
+// mask_nms_ws_bytes(>= B, >= N, H, W) bytes.  out_masks may be `masks` itself (only the first launch reads the input).
+int launch_mask_nms(const uint8_t* masks, const float* scores, int B, int N, int H, int W, float thresh, int small_on_top, uint8_t* out_masks,
+                    int* ids, int* source, float* out_scores, int* report, void* ws, hipStream_t st);
+size_t mask_nms_ws_bytes(int B, int N, int H, int W);
+int mask_nms_max();
 int launch_group_pixels(const float* logits, int nch, int B, int H, int W, int cap, const int* centers, const int* ncenters,
                         uint8_t* idmap, unsigned* area, hipStream_t st);
 

@@ -77,6 +77,8 @@ struct quber_ctx {
     void* cleanup_ws = nullptr;   // parent map, per-root tables, per-instance keys of the connected-component clean-up (cleanup.hip)
     void* perturb_ws = nullptr;   // bit planes of quber_perturb_masks in its device-memory placement: allocated on first use, grown on demand
     size_t perturb_ws_bytes = 0;
+    void* masknms_ws = nullptr;   // bit planes, pair table, rank map and per-frame tables of quber_mask_nms: allocated by its first call
+    size_t masknms_ws_bytes = 0;
     double* gn_stats = nullptr;   // [GN_SLOTS][launch group <= 4][max_batch][32 groups][sum, sum of squares]
     int gn_slots = 0;
     float* splitk_ws = nullptr;

@@ -510,6 +510,35 @@ class Engine:
                                                     _ptr(out), _ptr(report), int(placement), _stream()))
         return out, report
 
+    # ---- mask NMS of scored, overlapping initial masks (csrc/masknms.hip; INTEGRATION.md "Overlapping initial masks") ----
+    def mask_nms(self, masks, scores, nms=None, out=None, ids=None, source=None, out_scores=None, report=None):
+        """masks u8 [B,N,H,W] (non-zero = inside), scores f32 [B,N] (finite), both on the device; nms: a masknms.MaskNMS (default: the
+        reference's, IoU 0.7, large on top) -> {"masks": u8 [B,N,H,W] of 0 / 255, disjoint, compacted to the front; "ids": i32 [B,H,W]
+        (0, 1..count); "source": i32 [B,N] (input index, -1 behind count); "scores": f32 [B,N]; "report": i32 [B,4] (count, kept, 0, 0)}.
+        `out` may be `masks` itself.  N <= min(max_instances, 1024).  Nothing is copied to the host; the first call on an engine
+        allocates the workspace and cannot be captured into a graph."""
+        from .masknms import MaskNMS
+        nms = MaskNMS() if nms is None else nms
+        B, N = masks.shape[:2]
+        dev = self.device
+        assert masks.dtype == torch.uint8 and masks.is_contiguous() and masks.shape == (B, N, self.H, self.W)
+        assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.shape == (B, N)
+        out = torch.empty_like(masks) if out is None else out
+        ids = torch.empty((B, self.H, self.W), dtype=torch.int32, device=dev) if ids is None else ids
+        source = torch.empty((B, N), dtype=torch.int32, device=dev) if source is None else source
+        out_scores = torch.empty((B, N), dtype=torch.float32, device=dev) if out_scores is None else out_scores
+        report = torch.empty((B, 4), dtype=torch.int32, device=dev) if report is None else report
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == masks.shape
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.shape == (B, self.H, self.W)
+        assert source.dtype == torch.int32 and source.is_contiguous() and source.shape == (B, N)
+        assert out_scores.dtype == torch.float32 and out_scores.is_contiguous() and out_scores.shape == (B, N)
+        assert report.dtype == torch.int32 and report.is_contiguous() and report.shape == (B, 4)
+        thresh, on_top = nms.args()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_mask_nms(self.h, _ptr(masks), _ptr(scores), B, N, thresh, on_top, _ptr(out), _ptr(ids), _ptr(source),
+                                               _ptr(out_scores), _ptr(report), _stream()))
+        return {"masks": out, "ids": ids, "source": source, "scores": out_scores, "report": report}
+
     def extract_masks(self, post, max_inst, out=None):
         B = post["panoptic"].shape[0]
         if out is None:

@@ -33,6 +33,7 @@ import torch
 from PIL import Image
 
 from .. import engine as qengine
+from ..masknms import check_scores
 from ..maskrefiner.predictor import MaskRefinerPredictor
 
 W = 640
@@ -78,7 +79,8 @@ def resize_shortest_edge_shape(oldh, oldw, short_edge_length=800, max_size=1333)
 class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
                  lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
-                 decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None):
+                 decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
+                 nms=None):
         # tta: every frame and its W-mirror in one forward, logits merged on the device (MaskRefinerPredictor(tta=True))
         # decode_errors: the error heads' class maps, histograms and per-mask class counts in every output dict
         # iterations / until_converged / track_initial: the refined masks fed back for further passes on the device, early stop at a
@@ -88,10 +90,13 @@ class MaskRefiner:
         # (the SAM refiner's remove_small_regions(mask, 300, "holes")), applied on the device after post-processing
         # perturb: None or a quber_amd.perturb.Perturb - the initial masks degraded by the reference's perturb_seg on the device before
         # they are encoded (INTEGRATION.md "Perturbed initial masks"); predict() and predict_stream(batch=k) alike
+        # nms: None or a quber_amd.masknms.MaskNMS - the initial masks are scored, overlapping proposals (a SAM-style base model) and
+        # the reference's nms + combine_masks_with_NMS makes them disjoint on the device first (INTEGRATION.md "Overlapping initial
+        # masks"); predict(..., mask_scores=) and a fifth element of predict_stream's items carry the scores
         self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, tta=tta,
                                                       decode_errors=decode_errors, iterations=iterations,
                                                       until_converged=until_converged, track_initial=track_initial, cleanup=cleanup,
-                                                      perturb=perturb)
+                                                      perturb=perturb, nms=nms)
         self.dataset = dataset
         self.lmffnet = None
         # "host" / True (default): csrc/inpaint.hip on the calling (worker) thread; "device": csrc/inpaint_dev.hip, bit-equal, for hosts
@@ -112,18 +117,21 @@ class MaskRefiner:
             return np.ascontiguousarray(img)
         return qengine.resize_u8(self._dev(img), h, w, linear).cpu().numpy()
 
-    def _load(self, rgb_path, depth_path, initial_masks):
+    def _load(self, rgb_path, depth_path, initial_masks, mask_scores=None):
         """File reading and the adapter's pre-processing of one frame (eval/refiner_model.py:224-263): everything before the
         reference's timer starts.  Safe to run on a worker thread (predict_stream): its device work goes to a side stream."""
         rgb = np.asarray(Image.open(rgb_path).convert("RGB"))[:, :, ::-1]        # BGR like cv2.imread
         initial_masks = np.asarray(initial_masks)
         if initial_masks.dtype == np.bool_:
             initial_masks = np.uint8(initial_masks) * 255
+        scores = None
+        if self.refiner_predictor.nms is not None:        # missing or non-finite scores: refused here, before any device work
+            scores = check_scores(mask_scores, len(initial_masks))
         if self.dataset == "armbench":
             h, w = resize_shortest_edge_shape(rgb.shape[0], rgb.shape[1], 800, 1333)
             rgb = self._resize(rgb, h, w, linear=True)                           # cv2.resize(rgb_img, (w, h))
             initial_masks = np.array([self._resize(m, h, w, linear=False) for m in initial_masks])   # INTER_NEAREST
-            return {"rgb": np.ascontiguousarray(rgb), "depth": None, "masks": initial_masks, "zero_depth": None}
+            return {"rgb": np.ascontiguousarray(rgb), "depth": None, "masks": initial_masks, "zero_depth": None, "scores": scores}
         depth = np.load(depth_path) if "npy" in depth_path else np.asarray(Image.open(depth_path))
         rgb = self._resize(rgb, H, W, linear=True)                               # cv2.resize(rgb_img, (W, H))
         zero_depth = np.where(depth == 0)
@@ -144,15 +152,16 @@ class MaskRefiner:
             d_dev = None
         else:
             depth = d_dev.cpu().numpy()
-        return {"rgb": np.ascontiguousarray(rgb), "depth": depth, "masks": initial_masks, "zero_depth": zero_depth, "depth_dev": d_dev}
+        return {"rgb": np.ascontiguousarray(rgb), "depth": depth, "masks": initial_masks, "zero_depth": zero_depth, "depth_dev": d_dev,
+                "scores": scores}
 
     def _refine(self, fr):
         """The reference's timed region and what follows it (eval/refiner_model.py:265-297) on a loaded frame."""
         start = time.time()
         if self.dataset == "armbench":
-            output = self.refiner_predictor.predict(fr["rgb"], None, fr["masks"])[0]
+            output = self.refiner_predictor.predict(fr["rgb"], None, fr["masks"], fr["scores"])[0]
         else:
-            output = self.refiner_predictor.predict(fr["rgb"], fr["depth"], fr["masks"])[0]
+            output = self.refiner_predictor.predict(fr["rgb"], fr["depth"], fr["masks"], fr["scores"])[0]
         refined = output["instances"].to("cpu").pred_masks.numpy() if "instances" in output else []
         return self._finish(fr, output, refined, start)
 
@@ -181,8 +190,8 @@ class MaskRefiner:
             refined = np.asarray(out)
         return refined, output, elapsed, fg
 
-    def predict(self, rgb_path, depth_path, initial_masks, fg_mask=None):
-        return self._refine(self._load(rgb_path, depth_path, initial_masks))
+    def predict(self, rgb_path, depth_path, initial_masks, fg_mask=None, mask_scores=None):
+        return self._refine(self._load(rgb_path, depth_path, initial_masks, mask_scores))
 
     # -- the predicted error maps of one frame: scored against a ground truth, painted over the image (csrc/errhead.hip) --
     def _error_engine(self, h, w, n_masks=64):
@@ -228,7 +237,8 @@ class MaskRefiner:
         return eng.error_overlay(self._dev(bgr[None]), self._error_classes(eng, output, head), palette)[0].cpu().numpy()
 
     def predict_stream(self, items, workers=2, batch=1):
-        """items: iterable of (rgb_path, depth_path, initial_masks[, fg_mask]) -> yields predict()'s tuple per item, in order.
+        """items: iterable of (rgb_path, depth_path, initial_masks[, fg_mask[, mask_scores]]) -> yields predict()'s tuple per item, in
+        order (mask_scores: required with nms=).
         The reference's evaluation loop (eval/eval_utils.py:235-286) calls predict() frame after frame; the host side of a frame -
         file decoding and, above all, the TELEA depth in-painting (9-14 ms, two to three times the refiner's GPU time) - is
         independent of the previous frame's refinement, so it runs ahead on `workers` threads (the in-painting is a ctypes call
@@ -253,7 +263,7 @@ class MaskRefiner:
                 sides[tid] = torch.cuda.Stream(device=dev)
             side = sides[tid]
             with torch.cuda.stream(side):
-                fr = self._load(item[0], item[1], item[2])
+                fr = self._load(item[0], item[1], item[2], item[4] if len(item) > 4 else None)
                 if k > 1:                        # the frame goes to the device here, off the main thread
                     m = fr["masks"]
                     fr["d_rgb"] = torch.from_numpy(fr["rgb"]).to(dev, non_blocking=True)
@@ -263,6 +273,8 @@ class MaskRefiner:
                         fr["d_depth"] = None if fr["depth"] is None else torch.from_numpy(np.ascontiguousarray(fr["depth"])).to(dev, non_blocking=True)
                     # (the encoder tests the mask bytes for non-zero, csrc/encode.hip: bool / 0-255 masks upload as they are)
                     fr["d_masks"] = torch.from_numpy(np.ascontiguousarray(m.view(np.uint8) if m.dtype == np.bool_ else m.astype(np.uint8, copy=False))).to(dev, non_blocking=True)
+                    if fr["scores"] is not None:
+                        fr["d_scores"] = torch.from_numpy(fr["scores"]).to(dev, non_blocking=True)
                     fr["ready"] = torch.cuda.Event()
                     fr["ready"].record(side)
                     side.synchronize()           # (pageable sources: the copies are complete when this returns)
@@ -286,15 +298,22 @@ class MaskRefiner:
             for b, f in enumerate(frs):
                 if f["d_masks"].shape[0]:
                     d_masks[b, :f["d_masks"].shape[0]] = f["d_masks"]
+            d_scores = None
+            if model.nms is not None:                       # NaN: no such mask (the rows of a frame with fewer than n)
+                d_scores = torch.full((B_, n), float("nan"), dtype=torch.float32, device=dev)
+                for b, f in enumerate(frs):
+                    if f["d_masks"].shape[0]:
+                        d_scores[b, :f["d_masks"].shape[0]] = f["d_scores"]
             img = [f["d_rgb"] if self.refiner_predictor.rgb_on else f["d_depth"] for f in frs]   # depth-only: the image IS the depth map
             if model.tta:
                 torch.stack(img, out=d_rgb[:B_])
                 if two:
                     torch.stack([f["d_depth"] for f in frs], out=d_depth[:B_])
-                return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, halves=True, n_masks=own)
+                return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, halves=True, n_masks=own,
+                                           d_scores=d_scores)
             d_rgb = torch.stack(img)
             d_depth = torch.stack([f["d_depth"] for f in frs]) if two else None
-            return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, n_masks=own)
+            return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, n_masks=own, d_scores=d_scores)
 
         def collect(frs, hd):
             outs, ms, host = self.refiner_predictor.model.collect_batch(hd, host_masks=True)

@@ -27,6 +27,13 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
     (never the fed-back masks), ``track_initial``, the per-mask histograms.  Every dict gains ``perturbed_masks`` (u8 [n,H,W], 0 / 255)
     and ``perturb_report`` (i64 [n,4]: rounds, |seg & g|, |seg | g|, |seg|).  uint8 masks are perturbed as their bytes stand (> 127 is
     the mask, non-zero the ground truth), bool masks count as 0 / 255.  Default: none, today's keys.
+  * ``nms=MaskNMS(thresh=0.7, on_top="large")``: the caller's initial masks are scored, overlapping proposals (SAM, MSMFormer, UCN with
+    zoom-in); the reference's ``nms`` + ``combine_masks_with_NMS`` makes them disjoint on the device (csrc/masknms.hip; INTEGRATION.md
+    "Overlapping initial masks") before anything else reads them - ``perturb``, the encoding, the mirror of ``tta``, the first pass of
+    ``iterations=k``, ``track_initial``, the per-mask histograms all see its output as THE initial masks.  The scores are required
+    (``predict(..., mask_scores=)``, ``predict_batch(..., scores_list=)``, ``enqueue_batch(..., d_scores=)``).  Every dict gains
+    ``nms_masks`` (u8 [count,H,W], 0 / 255, disjoint), ``nms_source`` (i64 [count]: the input index of each), ``nms_scores`` (f32 [count])
+    and ``nms_report`` (i64 [2]: count, kept = survivors of the NMS before hidden ones drop out).  Default: none, today's keys.
 There is no CPU fallback: construction fails if the HIP library or a GPU is missing.
 """
 import os
@@ -37,6 +44,7 @@ import torch
 
 from .. import arch, config as qconfig, engine as qengine
 from ..cleanup import Cleanup
+from ..masknms import MaskNMS, check_scores
 from ..perturb import Perturb
 from ..structures import Boxes, Instances
 
@@ -121,11 +129,14 @@ class RefinerModel:
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
     def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False, iterations=1, until_converged=False,
-                 track_initial=False, cleanup=None, perturb=None):
+                 track_initial=False, cleanup=None, perturb=None, nms=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
         if perturb is not None and not isinstance(perturb, Perturb):
             raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
+        # scored, overlapping initial masks made disjoint on the device before anything else reads them (INTEGRATION.md "Overlapping
+        # initial masks"); None: the masks are an instance segmentation already
+        self.nms = MaskNMS.parse(nms)
         # the initial masks degraded on the device before anything reads them (INTEGRATION.md "Perturbed initial masks"); None: as uploaded
         self.perturb = perturb
         self._perturb_dev = {}    # (frames, masks, H, W) -> the programs and targets of such a call on the device
@@ -195,6 +206,22 @@ class RefinerModel:
         if self.cleanup is not None:
             post["cc_report"] = eng.cleanup_post(logits, post, self.cleanup, post.get("cc_report"))
         return post
+
+    def nms_masks(self, eng, d_masks, d_scores, B):
+        """nms: the first B frames of d_masks u8 [>= B,N,H,W] (device) are replaced by the disjoint masks the mask NMS makes of them and
+        their scores f32 [B,N] (a NaN score: no such mask - the padding of a frame with fewer masks), in place as far as the caller can
+        tell (the kernels write a fresh tensor, which is copied back and kept for the output dicts).  -> what Engine.mask_nms returns,
+        or None."""
+        if self.nms is None:
+            return None
+        if d_scores is None:
+            raise ValueError("nms: the masks' scores are required when nms= is set")
+        if d_masks is None or d_masks.shape[1] == 0:
+            return None
+        src = d_masks[:B]
+        nm = eng.mask_nms(src, d_scores, self.nms)
+        src.copy_(nm["masks"])
+        return nm
 
     def perturb_masks(self, eng, d_masks, B):
         """perturb: the first B frames of d_masks u8 [>= B,N,H,W] (device) are replaced by their perturbed versions, in place as far as
@@ -311,12 +338,12 @@ class RefinerModel:
         ids = it["ids"] if it is not None else eng.relabel_panoptic(post)
         return eng.overlap_masks(d_masks, ids, eng.cap, out=out)
 
-    def frame_dict(self, eng, logits_b, post, b, k, masks_b, err=None, n_masks=None, it=None, conv=0, ov=None, n_own=None, pt=None):
+    def frame_dict(self, eng, logits_b, post, b, k, masks_b, err=None, n_masks=None, it=None, conv=0, ov=None, n_own=None, pt=None, nm=None):
         """The reference's output dict of one frame (model.py:304-356) from the device-side results.  err: what decode() returned
         for the batch; n_masks: the frame's own initial masks (the leading rows of its mask histogram and of initial_overlap);
         it / conv: what refine() returned and the frame's refine_converged_at on the host; ov: what track() returned; n_own: per frame
         of the batch, the rows of initial_overlap where n_masks is not given (collect_batch: the mask histogram keeps all N rows);
-        pt: what perturb_masks() returned."""
+        pt: what perturb_masks() returned; nm: what nms_masks() returned (its masks are then the initial masks n_masks / n_own count)."""
         qc = eng.qcfg
         ncls, o = qc.error_classes, 4
         r = {"sem_seg": logits_b[0:1], "panoptic_seg": (post["panoptic"][b], None)}
@@ -329,6 +356,10 @@ class RefinerModel:
             r[head + "_classes"], r[head + "_hist"] = cls[b], hist[b]
             if mh is not None:
                 r[head + "_mask_hist"] = mh[b] if n_masks is None else mh[b, :n_masks]
+        if nm is not None:
+            n = n_masks if n_masks is not None else int(n_own[b]) if n_own is not None else nm["masks"].shape[1]
+            r["nms_masks"], r["nms_source"], r["nms_scores"] = nm["masks"][b, :n], nm["source"][b, :n].to(torch.int64), nm["scores"][b, :n]
+            r["nms_report"] = nm["report"][b, :2].to(torch.int64)
         if pt is not None:
             n = n_masks if n_masks is not None else int(n_own[b]) if n_own is not None else pt[0].shape[1]
             r["perturbed_masks"], r["perturb_report"] = pt[0][b, :n], pt[1][b, :n].to(torch.int64)
@@ -352,17 +383,20 @@ class RefinerModel:
             r["instances"] = inst
         return r
 
-    def results(self, eng, logits, post, d_masks=None, n_masks=None, it=None, ov=None, pt=None):
+    def results(self, eng, logits, post, d_masks=None, n_masks=None, it=None, ov=None, pt=None, nm=None):
         """One D2H of the small per-frame tables, then mask extraction for exactly max(count) slots.  d_masks / n_masks (decode_errors):
-        the initial masks on the device and how many of them are each frame's own.  it / ov: what refine() / track() returned."""
+        the initial masks on the device and how many of them are each frame's own.  it / ov: what refine() / track() returned.
+        nm: what nms_masks() returned - each frame's own initial masks are then the `count` of its report."""
         B = logits.shape[0]
+        if nm is not None:
+            n_masks = [int(c) for c in nm["report"][:, 0].cpu().numpy()]
         err = self.decode(eng, logits, d_masks if it is None else None)       # (a pass >= 2 has no initial masks to attribute to)
         count = post["count"].cpu().numpy()
         conv = it["conv"].cpu().numpy() if it is not None else np.zeros((B,), np.int32)
         kmax = int(count.max()) if B else 0
         masks = eng.extract_masks(post, kmax) if kmax > 0 else None
         return [self.frame_dict(eng, logits[b], post, b, int(count[b]), masks[b, :int(count[b])].bool() if count[b] > 0 else None,
-                                err, None if n_masks is None else n_masks[b], it, conv[b], ov, None, pt)
+                                err, None if n_masks is None else n_masks[b], it, conv[b], ov, None, pt, nm)
                 for b in range(B)]
 
     def predict_one(self, bgr, depth, masks):
@@ -434,12 +468,15 @@ class RefinerModel:
         return self.frame_dict(eng, logits[0], post_out, 0, k, masks_b, err, None, it, int(stg.pin_count[1]) if it is not None else 0, ov, None, pt)
 
     # -- batched form on device-resident frames, split into "enqueue" and "collect" so that a caller can keep one batch in flight --
-    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None):
+    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None, d_scores=None):
         """d_bgr / d_depth: u8 [B,H,W,3] (depth None for single-stream configs), d_masks: u8 [B,N,H,W] on the device.  Enqueues a1 ...
         a11 and the extraction of the first `slots` instance masks of every frame on the current stream WITHOUT synchronising;
         returns a handle for collect_batch().  halves=True (test-time augmentation only): the tensors are 2B-frame buffers
         (tta_alloc) whose first halves hold the B frames.  n_masks: how many of the N masks are each frame's own (the rows of
-        `initial_overlap` under track_initial; default: all N)."""
+        `initial_overlap` under track_initial; default: all N).  d_scores (required with nms=): f32 [B,N] on the device, the masks'
+        scores, NaN for a mask that is not there; each frame's own masks are then the NMS's `count` and n_masks is not used."""
+        if self.nms is not None and d_scores is None:
+            raise ValueError("nms: d_scores is required when nms= is set")
         if halves:
             assert self.tta and d_bgr.shape[0] % 2 == 0
         B, H, W = d_bgr.shape[:3]
@@ -450,7 +487,8 @@ class RefinerModel:
         e0.record()
         if self.tta and not halves:
             d_bgr, d_depth, d_masks = self.tta_buffers(d_bgr, d_depth, d_masks)
-        pt = self.perturb_masks(eng, d_masks, B)          # (in the caller's tensor, unless tta_buffers has just copied it)
+        nm = self.nms_masks(eng, d_masks, d_scores, B)    # (in the caller's tensor, unless tta_buffers has just copied it)
+        pt = self.perturb_masks(eng, d_masks, B)
         if self.tta:
             logits = self.tta_logits(eng, d_bgr, d_depth, d_masks)
         else:
@@ -470,11 +508,15 @@ class RefinerModel:
         count.copy_(post["count"], non_blocking=True)
         if it is not None:
             pinned[1].copy_(it["conv"], non_blocking=True)
+        if nm is not None:                                # each frame's own initial masks: the NMS's count, read at collect_batch
+            rep = torch.zeros((B, 4), dtype=torch.int32).pin_memory()
+            rep.copy_(nm["report"], non_blocking=True)
+            n_masks = rep[:, 0]
         e1.record()
         eng._in_flight = getattr(eng, "_in_flight", 0) + 1
         return {"eng": eng, "logits": logits, "post": post, "masks": masks, "slots": slots, "count": count, "e0": e0, "e1": e1,
                 "err": err, "it": it, "conv": pinned[1], "ov": ov,
-                "n_masks": n_masks, "pt": pt}
+                "n_masks": n_masks, "pt": pt, "nm": nm}
 
     def collect_batch(self, hd, host_masks=False):
         """-> (list of the reference's per-frame output dicts, device milliseconds of the whole batch[, per-frame numpy masks]).
@@ -491,7 +533,7 @@ class RefinerModel:
             ready = torch.cuda.Event()
             ready.record()
         outs = [self.frame_dict(eng, hd["logits"][b], post, b, int(count[b]), masks[b, :int(count[b])].view(torch.bool) if count[b] > 0 else None,
-                                hd.get("err"), None, hd.get("it"), conv[b], hd.get("ov"), hd.get("n_masks"), hd.get("pt"))
+                                hd.get("err"), None, hd.get("it"), conv[b], hd.get("ov"), hd.get("n_masks"), hd.get("pt"), hd.get("nm"))
                 for b in range(len(count))]
         ms = hd["e0"].elapsed_time(hd["e1"])
         eng._in_flight = max(0, getattr(eng, "_in_flight", 1) - 1)
@@ -559,11 +601,12 @@ class RefinerModel:
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
                  seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False,
-                 cleanup=None, perturb=None):
+                 cleanup=None, perturb=None, nms=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
         if perturb is not None and not isinstance(perturb, Perturb):
             raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
+        self.nms = MaskNMS.parse(nms)                 # scored, overlapping initial masks made disjoint on the device first; None: taken as they are
         self.perturb = perturb                        # the initial masks degraded on the device before they are encoded; None: as uploaded
         self.cleanup = Cleanup.parse(cleanup)         # the connected-component clean-up after post-processing; None: none
         if config_file is None:
@@ -598,13 +641,15 @@ class MaskRefinerPredictor:
         self.iterations, self.until_converged, self.track_initial = int(iterations), bool(until_converged), bool(track_initial)
         self.model = RefinerModel(self.cfg, sd, device, tta=self.tta, decode_errors=self.decode_errors, iterations=self.iterations,
                                   until_converged=self.until_converged, track_initial=self.track_initial, cleanup=self.cleanup,
-                                  perturb=self.perturb)
+                                  perturb=self.perturb, nms=self.nms)
         self.device = torch.device(device)
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
     # -- reference signature (predictor.py:287) --
-    def predict(self, rgb_img, depth_img=None, perturbed_masks=None):
+    def predict(self, rgb_img, depth_img=None, perturbed_masks=None, mask_scores=None):
         masks = np.zeros((0,) + rgb_img.shape[:2], np.uint8) if perturbed_masks is None else np.asarray(perturbed_masks)
+        if self.nms is not None:                          # the general path: how many masks there are is known on the device only
+            return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks], [mask_scores])
         if self.perturb is not None and masks.dtype == np.bool_:
             masks = masks.view(np.uint8) * np.uint8(255)          # perturb_seg thresholds at 127: a bool mask counts as 0 / 255
         if not self.fast_path or masks.dtype not in (np.uint8, np.bool_) or masks.ndim != 3:
@@ -617,9 +662,17 @@ class MaskRefinerPredictor:
             depth_img = None
         return [self.model.predict_one(rgb_img, depth_img, masks)]
 
-    def predict_batch(self, rgb_imgs, depth_imgs, masks_list):
-        """rgb_imgs/depth_imgs: u8 [B,H,W,3] arrays; masks_list: B arrays u8/bool [N_b,H,W].  -> list of B dicts."""
+    def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None):
+        """rgb_imgs/depth_imgs: u8 [B,H,W,3] arrays; masks_list: B arrays u8/bool [N_b,H,W]; scores_list (required with nms=): B arrays
+        [N_b] of finite scores.  -> list of B dicts."""
         B, H, W = rgb_imgs.shape[:3]
+        sc = None
+        if self.nms is not None:                          # checked before anything is uploaded or launched
+            if scores_list is None or len(scores_list) != len(masks_list):
+                raise ValueError("nms: the scores of every frame's masks are required when nms= is set")
+            sc = np.full((B, max([len(m) for m in masks_list] + [1])), np.nan, np.float32)      # NaN: no such mask (a frame with fewer)
+            for b, (m, s) in enumerate(zip(masks_list, scores_list)):
+                sc[b, :len(m)] = check_scores(s, len(m), "the scores of frame %d" % b)
         if self.depth_on and depth_imgs is None:
             raise ValueError("this config has INPUT.DEPTH_ON: a depth image is required")
         if not self.rgb_on:                               # depth-only: the image IS the depth map (predictor.py:296-298)
@@ -631,9 +684,9 @@ class MaskRefinerPredictor:
         for b, m in enumerate(masks_list):
             if len(m):
                 m = np.asarray(m)
-                if self.perturb is None:
+                if self.perturb is None and self.nms is None:
                     mk[b, :len(m)] = m != 0
-                else:                                     # perturb_seg reads the bytes: uint8 as they stand, anything else as 0 / 255
+                else:                                     # perturb_seg reads the bytes: uint8 as they stand, anything else as 0 / 255 (the NMS: non-zero)
                     mk[b, :len(m)] = m if m.dtype == np.uint8 else (m != 0) * np.uint8(255)
         dev = self.device
         eng = self.model.engine_for(H, W, 2 * B if self.tta else B, n)
@@ -643,16 +696,18 @@ class MaskRefinerPredictor:
             if depth is not None:
                 depth[:B].copy_(torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)))
             d_masks[:B].copy_(torch.from_numpy(mk))
+            nm = self.model.nms_masks(eng, d_masks, None if sc is None else torch.from_numpy(sc).to(dev), B)
             pt = self.model.perturb_masks(eng, d_masks, B)
             logits = self.model.tta_logits(eng, bgr, depth, d_masks)
         else:
             d_masks = torch.from_numpy(mk).to(dev)
             bgr = torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)).to(dev)
             depth = None if depth_imgs is None else torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)).to(dev)
+            nm = self.model.nms_masks(eng, d_masks, None if sc is None else torch.from_numpy(sc).to(dev), B)
             pt = self.model.perturb_masks(eng, d_masks, B)
             offsets = eng.encode(d_masks)
             logits = eng.forward(bgr, depth, offsets)
         post = self.model.postprocess(eng, logits)
         logits, post, it = self.model.refine(eng, bgr, depth, logits, post, B, True)
         ov = self.model.track(eng, d_masks[:B], post, it)
-        return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list], it, ov, pt)
+        return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list], it, ov, pt, nm)
