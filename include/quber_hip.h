@@ -336,7 +336,53 @@ int quber_mask_nms(quber_ctx* ctx, const uint8_t* dev_masks, const float* dev_sc
                    int32_t on_top, uint8_t* dev_out_masks, int32_t* dev_ids, int32_t* dev_source, float* dev_out_scores,
                    int32_t* dev_report, void* stream);
 
-/* evaluation support - all pairwise overlap counts of two label maps in one pass.  Replaces the per-pair
+/* Zoom-in refinement (csrc/zoom.hip): the gather / scatter around a second pass that shows the network every first-pass instance as
+ * a padded crop resized to a fixed square - the reference's crop_rois and match_label_crop (eval/base_model.py:843-961, copies at :1088
+ * and :1192), which run one mask at a time with torch.unique, nonzero and a .cpu() per paste.  The numpy statement of what the three
+ * calls compute is tests/test_zoom_cpu.py: zoom_rois_np, zoom_crop_np, zoom_paste_np; INTEGRATION.md "Zoom-in refinement" has it in words.
+ *
+ * quber_zoom_rois: dev_ids i32 [B][H][W], a compact map (0 = none, 1..n_ids; other values are ignored), n_ids <= 254
+ *   -> dev_rois i32 [B][n_ids][4] = (x0, y0, x1, y1), inclusive: the tight extent of id j + 1, each side moved out by
+ *      rint(float32(x1 - x0) * padding) (y alike; round half to even, base_model.py:865) and clamped to the frame; (0, 0, -1, -1) for
+ *      an id without a pixel.  0 <= padding <= 16.
+ * quber_zoom_crop: dev_bgr (and dev_depth, or NULL) u8 [B][H][W][3], dev_ids as above, dev_slots i32 [n_slots][2] = (frame, id): one
+ *   crop per slot, dev_rois as above; 2 <= crop = S <= 512; n_slots <= 254 * max_batch
+ *   -> dev_bgr_crop (dev_depth_crop) u8 [n_slots][S][S][3]: the ROI resized bilinearly with align_corners (F.upsample_bilinear) in exact
+ *      rational arithmetic on the bytes: with d = S - 1, y0 = dy (h - 1) / d, ry = dy (h - 1) % d (x alike), weights (d - r) and r, the
+ *      neighbour clamped to the ROI, out = (sum + d d / 2) / (d d)
+ *   -> dev_mask_crop u8 [n_slots][1][S][S]: 255 where ids == id at the source pixel of F.upsample_nearest, whose index is
+ *      min(int(floorf(float32(dst) * (float32(in) / float32(out)))), in - 1), else 0
+ *   A slot that is no crop (frame or id out of range, a ROI that is empty or leaves the frame) gives zero crops.
+ * quber_zoom_paste: dev_crop_ids i32 [n_slots][S][S] (the crop pass's compact ids, 0..n_crop_ids), dev_crop_scores f32
+ *   [n_slots][n_crop_ids], dev_table / dev_area u32 [n_slots][n_crop_ids + 1] (quber_overlap_masks of (dev_mask_crop, dev_crop_ids):
+ *   pixels of id i inside the crop's own mask, pixels of id i), dev_depth_crop or NULL, dev_slots ascending by frame, dev_rois
+ *   keep   crop-pass instance i >= 1 with area > 0 is kept iff float32(overlap) / float32(area) >= min_overlap (base_model.py:898-907)
+ *   order  a frame's crops are painted in descending mean of the positive channel-2 depths under their kept instances, compared as
+ *          exact fractions, a crop without such a pixel first, equal keys in slot order (:909-930); dev_depth_crop NULL: in descending
+ *          ROI area
+ *   paste  in that order, a crop's kept instances in ascending id: the crop's id plane resized back to the ROI by the nearest rule
+ *          overwrites the frame where it is a kept instance (:932-959); the instances that still own a pixel get the final ids 1.. in
+ *          that order, at most max_inst (1..254) of them - the surplus is dropped
+ *   -> dev_out_ids i32 [B][H][W]; dev_out_masks u8 [B][max_inst][H][W] (0 / 255, zero planes behind count); dev_source i32
+ *      [B][max_inst][2] (first-pass id, crop-pass id; -1 behind count); dev_out_scores f32 [B][max_inst] (0 behind); dev_boxes f32
+ *      [B][max_inst][4] (x_min, y_min, x_max + 1, y_max + 1; 0 behind); dev_report i32 [B][4]: crops, kept instances, kept instances
+ *      that got no final id (painted over or surplus), count
+ * Every output is overwritten by every call; the inputs are not written.  All launches go to `stream`: no host copy, no
+ * synchronisation, no memset node (the tables are cleared by the zero-fill kernel).  The workspace (extents, keep flags, depth keys,
+ * paint order, key map, sized for max_batch frames) is not part of quber_create: the FIRST call of quber_zoom_rois or quber_zoom_paste
+ * allocates it and keeps it (quber_workspace_bytes counts it from then on), so that call is not capturable into a graph; later calls
+ * are.  The entries of one context share it: they run on one stream at a time.  They work on a context created with with_network = 0. */
+int quber_zoom_rois(quber_ctx* ctx, const int32_t* dev_ids, int32_t batch, int32_t n_ids, float padding, int32_t* dev_rois, void* stream);
+int quber_zoom_crop(quber_ctx* ctx, const uint8_t* dev_bgr, const uint8_t* dev_depth, const int32_t* dev_ids, const int32_t* dev_slots,
+                    const int32_t* dev_rois, int32_t batch, int32_t n_ids, int32_t n_slots, int32_t crop, uint8_t* dev_bgr_crop,
+                    uint8_t* dev_depth_crop, uint8_t* dev_mask_crop, void* stream);
+int quber_zoom_paste(quber_ctx* ctx, const int32_t* dev_crop_ids, const float* dev_crop_scores, const uint32_t* dev_table,
+                     const uint32_t* dev_area, const uint8_t* dev_depth_crop, const int32_t* dev_slots, const int32_t* dev_rois,
+                     int32_t batch, int32_t n_ids, int32_t n_slots, int32_t crop, int32_t n_crop_ids, float min_overlap, int32_t max_inst,
+                     int32_t* dev_out_ids, uint8_t* dev_out_masks, int32_t* dev_source, float* dev_out_scores, float* dev_boxes,
+                     int32_t* dev_report, void* stream);
+
+/* evaluation support - all pairwise overlap counts of two label maps in one pass. Replaces the per-pair
  * np.count_nonzero loops of eval/evaluation.py:180-199 (multilabel_metrics).
  *   dev_pred, dev_gt i32 [n_pixels], label values in 0..65535, at most `cap` (<= 1024) distinct values per map
  *   workspace (quber_contingency_workspace_bytes(cap) bytes, device) receives, in this order:

@@ -121,6 +121,7 @@ void quber_destroy(quber_ctx* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->perturb_ws) (void)hipFree(c->perturb_ws);
     if (c->masknms_ws) (void)hipFree(c->masknms_ws);
+    if (c->zoom_ws) (void)hipFree(c->zoom_ws);
     delete c;
 }
 
@@ -546,6 +547,66 @@ int quber_mask_nms(quber_ctx* c, const uint8_t* masks, const float* scores, int3
     }
     return launch_mask_nms(masks, scores, batch, n_masks, H, W, thresh, on_top, out_masks, ids, source, out_scores, report, c->masknms_ws,
                            (hipStream_t)stream);
+}
+
+// ---- zoom-in refinement: rois, crops, paste (zoom.hip); usable on a context without a network ----
+static int zoom_ws(quber_ctx* c) {           // the only allocation of the three entries: made by the first call, for max_batch frames, and kept
+    if (c->zoom_ws) return 0;
+    const size_t need = zoom_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width);
+    QB_CHECK(hipMalloc(&c->zoom_ws, need));
+    c->alloc_bytes += need;
+    return 0;
+}
+
+static int zoom_aligned4(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if ((uintptr_t)p & 3) return fail("zoom: a 32-bit tensor that is not 4-byte aligned");
+    return 0;
+}
+
+int quber_zoom_rois(quber_ctx* c, const int32_t* ids, int32_t batch, int32_t n_ids, float padding, int32_t* rois, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_ids < 0 || n_ids > 254) return fail("zoom rois: n_ids outside 0..254");
+    if (!(padding >= 0.f) || padding > 16.f) return fail("zoom rois: padding outside 0..16");
+    if (!ids || (n_ids > 0 && !rois)) return fail("zoom rois: null tensor");
+    if (zoom_aligned4({ids, rois})) return -1;
+    if (n_ids == 0) return 0;
+    if (zoom_ws(c)) return -1;
+    return launch_zoom_rois(ids, batch, n_ids, c->cfg.height, c->cfg.width, padding, rois, c->zoom_ws, c->cfg.max_batch, (hipStream_t)stream);
+}
+
+int quber_zoom_crop(quber_ctx* c, const uint8_t* bgr, const uint8_t* depth, const int32_t* ids, const int32_t* slots, const int32_t* rois,
+                    int32_t batch, int32_t n_ids, int32_t n_slots, int32_t crop, uint8_t* bgr_crop, uint8_t* depth_crop, uint8_t* mask_crop,
+                    void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_ids < 0 || n_ids > 254) return fail("zoom crop: n_ids outside 0..254");
+    if (n_slots < 0 || n_slots > c->cfg.max_batch * 254) return fail("zoom crop: n_slots outside 0..254 * max_batch");
+    if (crop < 2 || crop > 512) return fail("zoom crop: crop outside 2..512");
+    if (n_slots == 0) return 0;
+    if (!bgr || !ids || !slots || !rois || !bgr_crop || !mask_crop || (depth && !depth_crop)) return fail("zoom crop: null tensor");
+    if (zoom_aligned4({ids, slots, rois})) return -1;
+    return launch_zoom_crop(bgr, depth, ids, slots, rois, batch, n_ids, n_slots, crop, c->cfg.height, c->cfg.width, bgr_crop,
+                            depth ? depth_crop : nullptr, mask_crop, (hipStream_t)stream);
+}
+
+int quber_zoom_paste(quber_ctx* c, const int32_t* crop_ids, const float* crop_scores, const uint32_t* table, const uint32_t* area,
+                     const uint8_t* depth_crop, const int32_t* slots, const int32_t* rois, int32_t batch, int32_t n_ids, int32_t n_slots,
+                     int32_t crop, int32_t n_crop_ids, float min_overlap, int32_t max_inst, int32_t* out_ids, uint8_t* out_masks,
+                     int32_t* source, float* out_scores, float* boxes, int32_t* report, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_ids < 0 || n_ids > 254) return fail("zoom paste: n_ids outside 0..254");
+    if (n_slots < 0 || n_slots > c->cfg.max_batch * 254) return fail("zoom paste: n_slots outside 0..254 * max_batch");
+    if (crop < 2 || crop > 512) return fail("zoom paste: crop outside 2..512");
+    if (n_crop_ids < 1 || n_crop_ids > 254) return fail("zoom paste: n_crop_ids outside 1..254");
+    if (max_inst < 1 || max_inst > 254) return fail("zoom paste: max_inst outside 1..254");
+    if (!(min_overlap == min_overlap)) return fail("zoom paste: min_overlap is not a number");
+    if (!out_ids || !out_masks || !source || !out_scores || !boxes || !report) return fail("zoom paste: null tensor");
+    if (n_slots > 0 && (!crop_ids || !crop_scores || !table || !area || !slots || !rois)) return fail("zoom paste: null tensor");
+    if (zoom_aligned4({crop_ids, crop_scores, table, area, slots, rois, out_ids, source, out_scores, boxes, report})) return -1;
+    if (zoom_ws(c)) return -1;
+    return launch_zoom_paste(crop_ids, crop_scores, table, area, depth_crop, slots, rois, batch, n_ids, n_slots, crop, n_crop_ids, min_overlap,
+                             max_inst, c->cfg.height, c->cfg.width, out_ids, out_masks, source, out_scores, boxes, report, c->zoom_ws,
+                             c->cfg.max_batch, (hipStream_t)stream);
 }
 
 int64_t quber_contingency_workspace_bytes(int32_t cap) { return (int64_t)contingency_ws_bytes(cap); }

@@ -348,6 +348,16 @@ int launch_mask_nms(const uint8_t* masks, const float* scores, int B, int N, int
                     int* ids, int* source, float* out_scores, int* report, void* ws, hipStream_t st);
 size_t mask_nms_ws_bytes(int B, int N, int H, int W);
 int mask_nms_max();
+// zoom-in refinement (zoom.hip): the gather / scatter between the two passes, all on `st`; ws: zoom_ws_bytes(cap_b >= B, H, W) bytes.
+// T slots <= cap_b * 254, 2 <= S <= 512, C crop-pass ids <= 254, max_inst 1..254.
+int launch_zoom_rois(const int* ids, int B, int n_ids, int H, int W, float padding, int* rois, void* ws, int cap_b, hipStream_t st);
+int launch_zoom_crop(const uint8_t* bgr, const uint8_t* depth, const int* ids, const int* slots, const int* rois, int B, int n_ids, int T, int S,
+                     int H, int W, uint8_t* bgr_crop, uint8_t* depth_crop, uint8_t* mask_crop, hipStream_t st);
+int launch_zoom_paste(const int* crop_ids, const float* crop_scores, const unsigned* table, const unsigned* area, const uint8_t* depth_crop,
+                      const int* slots, const int* rois, int B, int n_ids, int T, int S, int C, float min_overlap, int max_inst, int H, int W,
+                      int* out_ids, uint8_t* out_masks, int* source, float* out_scores, float* boxes, int* report, void* ws, int cap_b,
+                      hipStream_t st);
+size_t zoom_ws_bytes(int cap_b, int H, int W);
 int launch_group_pixels(const float* logits, int nch, int B, int H, int W, int cap, const int* centers, const int* ncenters,
                         uint8_t* idmap, unsigned* area, hipStream_t st);
 

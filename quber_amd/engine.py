@@ -539,6 +539,73 @@ class Engine:
                                                _ptr(out_scores), _ptr(report), _stream()))
         return {"masks": out, "ids": ids, "source": source, "scores": out_scores, "report": report}
 
+    # ---- zoom-in refinement: rois, crops, paste (csrc/zoom.hip; INTEGRATION.md "Zoom-in refinement") ----
+    def zoom_rois(self, ids, n_ids, padding=0.25, out=None):
+        """ids i32 [B,H,W] (device; compact: 0 none, 1..n_ids) -> rois i32 [B,n_ids,4] = (x0, y0, x1, y1) inclusive: the tight extent of
+        every id, padded by rint(float32(extent) * padding) per side and clamped to the frame; (0, 0, -1, -1) for an id without a pixel."""
+        B = ids.shape[0]
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.shape == (B, self.H, self.W)
+        if out is None:
+            out = torch.empty((B, n_ids, 4), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == (B, n_ids, 4)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_zoom_rois(self.h, _ptr(ids), B, int(n_ids), float(padding), _ptr(out), _stream()))
+        return out
+
+    def zoom_crop(self, bgr, depth, ids, slots, rois, crop, out=None):
+        """bgr (and depth, or None) u8 [B,H,W,3], ids i32 [B,H,W], slots i32 [T,2] = (frame, id), rois i32 [B,n_ids,4], all on the device
+        -> (bgr_crop u8 [T,S,S,3], depth_crop likewise or None, mask_crop u8 [T,1,S,S] of 0 / 255), S = crop: the ROI of every slot resized
+        bilinearly (align_corners, exact on the bytes), its own mask by the nearest rule.  out: such a triple to write into."""
+        B, T, S = ids.shape[0], slots.shape[0], int(crop)
+        n_ids = rois.shape[1]
+        assert bgr.dtype == torch.uint8 and bgr.is_contiguous() and bgr.shape == (B, self.H, self.W, 3)
+        assert depth is None or (depth.dtype == torch.uint8 and depth.is_contiguous() and depth.shape == bgr.shape)
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.shape == (B, self.H, self.W)
+        assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape == (T, 2)
+        assert rois.dtype == torch.int32 and rois.is_contiguous() and rois.shape == (B, n_ids, 4)
+        bc, dc, mc = out if out is not None else (None, None, None)
+        dev = self.device
+        bc = torch.empty((T, S, S, 3), dtype=torch.uint8, device=dev) if bc is None else bc
+        dc = (torch.empty((T, S, S, 3), dtype=torch.uint8, device=dev) if dc is None else dc) if depth is not None else None
+        mc = torch.empty((T, 1, S, S), dtype=torch.uint8, device=dev) if mc is None else mc
+        for t, shape in ((bc, (T, S, S, 3)), (dc, (T, S, S, 3)), (mc, (T, 1, S, S))):
+            assert t is None or (t.dtype == torch.uint8 and t.is_contiguous() and t.shape == shape)
+        _lib.check(self.lib.quber_zoom_crop(self.h, _ptr(bgr), _ptr(depth), _ptr(ids), _ptr(slots), _ptr(rois), B, n_ids, T, S, _ptr(bc), _ptr(dc),
+                                            _ptr(mc), _stream()))
+        return bc, dc, mc
+
+    def zoom_paste(self, crop_ids, crop_scores, table, area, depth_crop, slots, rois, batch, min_overlap=0.5, max_inst=254, out=None):
+        """crop_ids i32 [T,S,S] (the crop pass's compact ids), crop_scores f32 [T,C], table / area i32 [T,C+1] (overlap_masks of the mask
+        crops with crop_ids, on the crop engine), depth_crop u8 [T,S,S,3] or None, slots i32 [T,2] ascending by frame, rois i32 [B,n_ids,4]
+        -> {"ids": i32 [B,H,W], "masks": u8 [B,max_inst,H,W] of 0 / 255, "source": i32 [B,max_inst,2] (first-pass id, crop-pass id; -1
+        behind count), "scores": f32 [B,max_inst], "boxes": f32 [B,max_inst,4], "report": i32 [B,4] = crops, kept, kept without a final
+        id, count}.  out: such a dict to write into.  Nothing is copied to the host."""
+        B, T = int(batch), slots.shape[0]
+        S = crop_ids.shape[1] if T else 2
+        C = crop_scores.shape[1] if T else 1
+        n_ids, N, dev = rois.shape[1], int(max_inst), self.device
+        if T:
+            assert crop_ids.dtype == torch.int32 and crop_ids.is_contiguous() and crop_ids.shape == (T, S, S)
+            assert crop_scores.dtype == torch.float32 and crop_scores.is_contiguous() and crop_scores.shape == (T, C)
+            for t in (table, area):
+                assert t.dtype == torch.int32 and t.is_contiguous() and t.shape == (T, C + 1)
+            assert depth_crop is None or (depth_crop.dtype == torch.uint8 and depth_crop.is_contiguous() and depth_crop.shape == (T, S, S, 3))
+        assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape == (T, 2)
+        assert rois.dtype == torch.int32 and rois.is_contiguous() and rois.shape == (B, n_ids, 4)
+        spec = {"ids": ((B, self.H, self.W), torch.int32), "masks": ((B, N, self.H, self.W), torch.uint8), "source": ((B, N, 2), torch.int32),
+                "scores": ((B, N), torch.float32), "boxes": ((B, N, 4), torch.float32), "report": ((B, 4), torch.int32)}
+        o = {} if out is None else out
+        for k, (shape, dt) in spec.items():
+            if o.get(k) is None:
+                o[k] = torch.empty(shape, dtype=dt, device=dev)
+            assert o[k].dtype == dt and o[k].is_contiguous() and o[k].shape == shape, k
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_zoom_paste(self.h, _ptr(crop_ids if T else None), _ptr(crop_scores if T else None), _ptr(table if T else None),
+                                                 _ptr(area if T else None), _ptr(depth_crop if T else None), _ptr(slots), _ptr(rois), B, n_ids, T, S, C,
+                                                 float(min_overlap), N, _ptr(o["ids"]), _ptr(o["masks"]), _ptr(o["source"]), _ptr(o["scores"]),
+                                                 _ptr(o["boxes"]), _ptr(o["report"]), _stream()))
+        return o
+
     def extract_masks(self, post, max_inst, out=None):
         B = post["panoptic"].shape[0]
         if out is None:

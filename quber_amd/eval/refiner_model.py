@@ -80,7 +80,7 @@ class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
                  lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
                  decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
-                 nms=None):
+                 nms=None, zoom=None):
         # tta: every frame and its W-mirror in one forward, logits merged on the device (MaskRefinerPredictor(tta=True))
         # decode_errors: the error heads' class maps, histograms and per-mask class counts in every output dict
         # iterations / until_converged / track_initial: the refined masks fed back for further passes on the device, early stop at a
@@ -93,10 +93,13 @@ class MaskRefiner:
         # nms: None or a quber_amd.masknms.MaskNMS - the initial masks are scored, overlapping proposals (a SAM-style base model) and
         # the reference's nms + combine_masks_with_NMS makes them disjoint on the device first (INTEGRATION.md "Overlapping initial
         # masks"); predict(..., mask_scores=) and a fifth element of predict_stream's items carry the scores
+        # zoom: None or a quber_amd.zoom.ZoomIn - a second pass on a padded, resized crop of every refined instance, pasted back on the
+        # device, the reference's ucn-zoomin / msmformer-zoomin base models' second stage (INTEGRATION.md "Zoom-in refinement"); predict()
+        # only: predict_stream refuses it
         self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, tta=tta,
                                                       decode_errors=decode_errors, iterations=iterations,
                                                       until_converged=until_converged, track_initial=track_initial, cleanup=cleanup,
-                                                      perturb=perturb, nms=nms)
+                                                      perturb=perturb, nms=nms, zoom=zoom)
         self.dataset = dataset
         self.lmffnet = None
         # "host" / True (default): csrc/inpaint.hip on the calling (worker) thread; "device": csrc/inpaint_dev.hip, bit-equal, for hosts
@@ -250,6 +253,8 @@ class MaskRefiner:
         current one are copied out - the GPU's batched throughput through the reference's own adapter API.  The per-frame tuples
         are the ones predict() returns (`seconds` = the batch's device time / k); a frame's logits may differ from its batch-1
         logits in the last bits (split-K partitions follow the launch size), which tests/test_gpu_network.py bounds and explains."""
+        if self.refiner_predictor.zoom is not None:
+            raise ValueError("zoom: predict_stream has no zoomed form; call predict() per frame (or construct without zoom=)")
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         import threading

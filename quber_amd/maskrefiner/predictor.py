@@ -34,6 +34,16 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
     (``predict(..., mask_scores=)``, ``predict_batch(..., scores_list=)``, ``enqueue_batch(..., d_scores=)``).  Every dict gains
     ``nms_masks`` (u8 [count,H,W], 0 / 255, disjoint), ``nms_source`` (i64 [count]: the input index of each), ``nms_scores`` (f32 [count])
     and ``nms_report`` (i64 [2]: count, kept = survivors of the NMS before hidden ones drop out).  Default: none, today's keys.
+  * ``zoom=ZoomIn(crop=224, padding=0.25, min_overlap=0.5)``: the second, zoomed-in pass of the reference's base models (``crop_rois`` /
+    ``match_label_crop``, eval/base_model.py:843-961) without leaving the device (csrc/zoom.hip; INTEGRATION.md "Zoom-in refinement"):
+    every instance of pass 1 - run with all configured options, through post-processing and ``cleanup`` - is cropped with a padded box,
+    resized to crop x crop together with its own mask, refined by the same network as a batch of crops (same ``tta``, ``iterations``,
+    ``cleanup``; no ``perturb``, ``nms``, ``decode_errors``, ``track_initial``), and the crop results that agree with the mask they came
+    from are painted back, far objects first.  ``instances`` then holds the zoomed result (``pred_masks``, ``scores``, ``pred_boxes``,
+    ``pred_classes`` all 0, ``zoom_source`` i64 [count,2]: first-pass id, crop-pass id); pass 1's move to ``coarse_instances``; the dict
+    gains ``zoom_ids`` (i32 [H,W]), ``zoom_rois`` (i32 [k,4]) and ``zoom_report`` (i64 [4]: crops, kept, kept without a final id, count);
+    ``sem_seg``, ``panoptic_seg`` and the error heads stay pass 1's.  ``predict`` and ``predict_batch``; ``enqueue_batch`` /
+    ``predict_stream`` refuse it.  Default: none, today's keys, nothing launched or allocated.
 There is no CPU fallback: construction fails if the HIP library or a GPU is missing.
 """
 import os
@@ -47,6 +57,7 @@ from ..cleanup import Cleanup
 from ..masknms import MaskNMS, check_scores
 from ..perturb import Perturb
 from ..structures import Boxes, Instances
+from ..zoom import ZoomIn
 
 LABEL_DIVISOR = 1000  # maskrefiner/data/datasets/register_uoais_sim_panoptic.py:177-186
 
@@ -129,11 +140,16 @@ class RefinerModel:
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
     def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False, iterations=1, until_converged=False,
-                 track_initial=False, cleanup=None, perturb=None, nms=None):
+                 track_initial=False, cleanup=None, perturb=None, nms=None, zoom=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
         if perturb is not None and not isinstance(perturb, Perturb):
             raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
+        # a second pass on a padded, resized crop of every instance, pasted back on the device (INTEGRATION.md "Zoom-in refinement"); None:
+        # one look at the full frame
+        self.zoom = ZoomIn.parse(zoom)
+        self._zoom_model = None   # the crop pass: a RefinerModel on the same cfg and weights, built by the first zoomed call
+        self.debug_zoom = None    # tests: a list that receives, per zoomed call, the inputs and outputs of every stage
         # scored, overlapping initial masks made disjoint on the device before anything else reads them (INTEGRATION.md "Overlapping
         # initial masks"); None: the masks are an instance segmentation already
         self.nms = MaskNMS.parse(nms)
@@ -338,6 +354,73 @@ class RefinerModel:
         ids = it["ids"] if it is not None else eng.relabel_panoptic(post)
         return eng.overlap_masks(d_masks, ids, eng.cap, out=out)
 
+    # -- zoom-in refinement (INTEGRATION.md "Zoom-in refinement") --
+    def zoom_model(self):
+        """The crop pass: this model's cfg, weights, tta, iterations and cleanup; nothing that concerns the caller's initial masks."""
+        if self._zoom_model is None:
+            self._zoom_model = RefinerModel(self.cfg, self.state_dict, self.device, tta=self.tta, iterations=self.iterations, cleanup=self.cleanup)
+        return self._zoom_model
+
+    def zoom_pass(self, eng, bgr, depth, post, it, count, outs):
+        """zoom: pass 2 on the instances pass 1 left in `post` (bgr / depth: the B frames on the device; count: their instance counts on
+        the host; it: what refine() returned).  rois -> crops -> the crop pass in chunks of zoom.batch crops through enqueue_batch /
+        collect_batch on the engine for (crop, crop) -> paste; then the dicts `outs` are rewritten: instances -> coarse_instances, the
+        zoomed instances, zoom_ids / zoom_rois / zoom_report."""
+        z, dev = self.zoom, self.device
+        B, S, n_ids = len(outs), self.zoom.crop, eng.cap
+        ids = it["ids"] if it is not None else eng.relabel_panoptic(post)
+        rois = eng.zoom_rois(ids, n_ids, z.padding)
+        slots_h = np.array([(b, j) for b in range(B) for j in range(1, int(count[b]) + 1)], np.int32).reshape(-1, 2)
+        T = len(slots_h)
+        slots = torch.from_numpy(slots_h).to(dev)
+        bgr, depth = bgr[:B], None if depth is None else depth[:B]
+        C = eng.cap
+        if T:
+            bc, dc, mc = eng.zoom_crop(bgr, depth, ids, slots, rois, S)
+            inner = self.zoom_model()
+            parts, crop_count = [], []
+            for a in range(0, T, z.batch):
+                e = min(T, a + z.batch)
+                hd = inner.enqueue_batch(bc[a:e], None if dc is None else dc[a:e], mc[a:e], slots=1, capacity=z.batch)
+                ceng = hd["eng"]
+                cid = hd["it"]["ids"] if hd["it"] is not None else ceng.relabel_panoptic(hd["post"])
+                table, area = ceng.overlap_masks(mc[a:e], cid, ceng.cap)
+                parts.append((cid, hd["post"]["scores"], table.view(e - a, ceng.cap + 1), area))
+                inner.collect_batch(hd)
+                crop_count.extend(int(c) for c in hd["count"].numpy())
+            C = ceng.cap
+            crop_ids, crop_scores, table, area = (torch.cat([p[i] for p in parts]).contiguous() for i in range(4))
+            per_frame = np.bincount(slots_h[:, 0], weights=np.asarray(crop_count, np.float64), minlength=B)
+            max_inst = int(min(254, max(1, per_frame.max())))          # an upper bound of every frame's final count
+        else:
+            e8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)
+            bc, dc, mc = e8(0, S, S, 3), None if depth is None else e8(0, S, S, 3), e8(0, 1, S, S)
+            crop_ids = torch.empty((0, S, S), dtype=torch.int32, device=dev)
+            crop_scores = torch.empty((0, C), dtype=torch.float32, device=dev)
+            table = area = torch.empty((0, C + 1), dtype=torch.int32, device=dev)
+            max_inst = 1
+        final = eng.zoom_paste(crop_ids, crop_scores, table, area, dc, slots, rois, B, z.min_overlap, max_inst)
+        report = final["report"].cpu().numpy()
+        if self.debug_zoom is not None:
+            self.debug_zoom.append({"ids": ids.clone(), "bgr": bgr, "depth": depth, "slots": slots, "rois": rois, "bgr_crop": bc, "depth_crop": dc,
+                                    "mask_crop": mc, "crop_ids": crop_ids, "crop_scores": crop_scores, "table": table, "area": area,
+                                    "final": final})
+        for b, r in enumerate(outs):
+            k = int(report[b, 3])
+            if "instances" in r:
+                r["coarse_instances"] = r.pop("instances")
+            r["zoom_ids"], r["zoom_rois"] = final["ids"][b], rois[b, :int(count[b])]
+            r["zoom_report"] = torch.from_numpy(report[b].astype(np.int64))
+            if k > 0:
+                inst = Instances((eng.H, eng.W))
+                inst.pred_masks = final["masks"][b, :k] != 0
+                inst.scores = final["scores"][b, :k]
+                inst.pred_boxes = Boxes(final["boxes"][b, :k])
+                inst.pred_classes = torch.zeros((k,), dtype=torch.int64, device=dev)
+                inst.zoom_source = final["source"][b, :k].to(torch.int64)
+                r["instances"] = inst
+        return outs
+
     def frame_dict(self, eng, logits_b, post, b, k, masks_b, err=None, n_masks=None, it=None, conv=0, ov=None, n_own=None, pt=None, nm=None):
         """The reference's output dict of one frame (model.py:304-356) from the device-side results.  err: what decode() returned
         for the batch; n_masks: the frame's own initial masks (the leading rows of its mask histogram and of initial_overlap);
@@ -383,10 +466,11 @@ class RefinerModel:
             r["instances"] = inst
         return r
 
-    def results(self, eng, logits, post, d_masks=None, n_masks=None, it=None, ov=None, pt=None, nm=None):
+    def results(self, eng, logits, post, d_masks=None, n_masks=None, it=None, ov=None, pt=None, nm=None, images=None):
         """One D2H of the small per-frame tables, then mask extraction for exactly max(count) slots.  d_masks / n_masks (decode_errors):
         the initial masks on the device and how many of them are each frame's own.  it / ov: what refine() / track() returned.
-        nm: what nms_masks() returned - each frame's own initial masks are then the `count` of its report."""
+        nm: what nms_masks() returned - each frame's own initial masks are then the `count` of its report.  images (required with zoom=):
+        the (bgr, depth) device tensors pass 1 ran on."""
         B = logits.shape[0]
         if nm is not None:
             n_masks = [int(c) for c in nm["report"][:, 0].cpu().numpy()]
@@ -395,14 +479,21 @@ class RefinerModel:
         conv = it["conv"].cpu().numpy() if it is not None else np.zeros((B,), np.int32)
         kmax = int(count.max()) if B else 0
         masks = eng.extract_masks(post, kmax) if kmax > 0 else None
-        return [self.frame_dict(eng, logits[b], post, b, int(count[b]), masks[b, :int(count[b])].bool() if count[b] > 0 else None,
+        outs = [self.frame_dict(eng, logits[b], post, b, int(count[b]), masks[b, :int(count[b])].bool() if count[b] > 0 else None,
                                 err, None if n_masks is None else n_masks[b], it, conv[b], ov, None, pt, nm)
                 for b in range(B)]
+        if self.zoom is not None:
+            if images is None:
+                raise ValueError("zoom: this call path has no zoomed form (predict and predict_batch have)")
+            outs = self.zoom_pass(eng, images[0], images[1], post, it, count, outs)
+        return outs
 
     def predict_one(self, bgr, depth, masks):
         """The reference's call path (one frame per call, predictor.py:287-359) with nothing allocated per call but the
         outputs: the inputs go through one pinned block in a few pipelined H2D copies; the instance count comes back through
         a pinned word and exactly `count` masks are extracted."""
+        if self.zoom is not None:
+            raise ValueError("zoom: predict_one has no zoomed form; MaskRefinerPredictor.predict takes the batched path")
         H, W = bgr.shape[:2]
         n = int(masks.shape[0])
         f = 2 if self.tta else 1                     # frames on the device: the frame [and its mirror]
@@ -477,6 +568,8 @@ class RefinerModel:
         scores, NaN for a mask that is not there; each frame's own masks are then the NMS's `count` and n_masks is not used."""
         if self.nms is not None and d_scores is None:
             raise ValueError("nms: d_scores is required when nms= is set")
+        if self.zoom is not None:
+            raise ValueError("zoom: enqueue_batch / predict_stream have no zoomed form; use predict or predict_batch")
         if halves:
             assert self.tta and d_bgr.shape[0] % 2 == 0
         B, H, W = d_bgr.shape[:3]
@@ -574,6 +667,9 @@ class RefinerModel:
                 e.close()
         for e in self._engines.values():
             e.close()
+        if self._zoom_model is not None:
+            self._zoom_model.close()
+            self._zoom_model = None
         self._retired.clear()
         self._engines.clear()
         self._staging.clear()
@@ -601,11 +697,12 @@ class RefinerModel:
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
                  seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False,
-                 cleanup=None, perturb=None, nms=None):
+                 cleanup=None, perturb=None, nms=None, zoom=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
         if perturb is not None and not isinstance(perturb, Perturb):
             raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
+        self.zoom = ZoomIn.parse(zoom)                # a second, zoomed-in pass on every instance, pasted back on the device; None: none
         self.nms = MaskNMS.parse(nms)                 # scored, overlapping initial masks made disjoint on the device first; None: taken as they are
         self.perturb = perturb                        # the initial masks degraded on the device before they are encoded; None: as uploaded
         self.cleanup = Cleanup.parse(cleanup)         # the connected-component clean-up after post-processing; None: none
@@ -641,7 +738,7 @@ class MaskRefinerPredictor:
         self.iterations, self.until_converged, self.track_initial = int(iterations), bool(until_converged), bool(track_initial)
         self.model = RefinerModel(self.cfg, sd, device, tta=self.tta, decode_errors=self.decode_errors, iterations=self.iterations,
                                   until_converged=self.until_converged, track_initial=self.track_initial, cleanup=self.cleanup,
-                                  perturb=self.perturb, nms=self.nms)
+                                  perturb=self.perturb, nms=self.nms, zoom=self.zoom)
         self.device = torch.device(device)
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
@@ -650,6 +747,8 @@ class MaskRefinerPredictor:
         masks = np.zeros((0,) + rgb_img.shape[:2], np.uint8) if perturbed_masks is None else np.asarray(perturbed_masks)
         if self.nms is not None:                          # the general path: how many masks there are is known on the device only
             return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks], [mask_scores])
+        if self.zoom is not None:                         # the general path: it keeps the frame on the device for the crops
+            return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks])
         if self.perturb is not None and masks.dtype == np.bool_:
             masks = masks.view(np.uint8) * np.uint8(255)          # perturb_seg thresholds at 127: a bool mask counts as 0 / 255
         if not self.fast_path or masks.dtype not in (np.uint8, np.bool_) or masks.ndim != 3:
@@ -710,4 +809,4 @@ class MaskRefinerPredictor:
         post = self.model.postprocess(eng, logits)
         logits, post, it = self.model.refine(eng, bgr, depth, logits, post, B, True)
         ov = self.model.track(eng, d_masks[:B], post, it)
-        return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list], it, ov, pt, nm)
+        return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list], it, ov, pt, nm, (bgr, depth))
