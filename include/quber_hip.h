@@ -405,6 +405,37 @@ int quber_boundary_overlap(const int32_t* dev_pred, const int32_t* dev_gt, int32
                            int32_t n_pred, int32_t n_gt, int32_t bound_pix, void* dev_workspace, uint32_t* dev_out,
                            void* stream);
 
+/* evaluation support - multilabel_metrics (eval/evaluation.py:57-274) for `batch` pairs of label maps in one call, with no read-back in
+ * between: the label counts, the F-measure matrix and the Munkres assignment (eval/munkres.py, with its tie-breaking) stay on the
+ * device, the caller copies dev_out back once and does the final float sums (numpy's summation order is part of the reference's numbers).
+ *   dev_pred, dev_gt i32 [batch][h][w] (h * w <= 2^32), batch 1..4096
+ *   cap 1..256: most distinct labels per map, background included; a frame above it is flagged (status 2), never truncated
+ *   bound_pix, with_boundary: as quber_boundary_overlap (same frame-size limit: h * ceil(w / 64) * 8 <= 160 KiB - 64); 0 = no boundary work
+ *   placement of the solver's cost matrix: 0 = LDS for a frame of up to 128 objects a side, device memory above; 1 = LDS (a larger frame
+ *     gets status 8); 2 = device memory
+ *   dev_workspace: quber_eval_batch_workspace_bytes(batch, h, w, cap, with_boundary) bytes =
+ *     batch * (786440 + 16 cap^2 [+ 3 * 2 cap * h * ceil(w / 64) * 8]), rounded up to 8
+ *   -> dev_out: one record per frame, R = 24 cap^2 + 68 cap + 32 bytes rounded up to 8, every byte written by every call; at byte offset
+ *        0                      u64 table[cap][cap]   row = gt label index, column = predicted label index (quber_label_contingency)
+ *        8 cap^2                f64 F[cap][cap]       F-measure, row = gt OBJECT, column = predicted OBJECT (labels != 0), row stride cap
+ *        16 cap^2               u64 area[2][cap]      pixels per label index, predicted then gt
+ *        16 cap^2 + 16 cap      u64 pair_tps[cap], u64 pair_union[cap]     per assigned pair
+ *        16 cap^2 + 32 cap      u32 ptps[cap][cap], u32 rtps[cap][cap]     boundary true positives [gt object][predicted object]
+ *        24 cap^2 + 32 cap      i32 hdr[8] = labels in pred, labels in gt, out-of-range flag, STATUS, objects in pred, objects in gt, pairs, the solver's bits
+ *        ... + 32               i32 labels[2][cap] (sorted), u32 boundary size[2][cap] (per object), i32 assign[cap] (per gt object the
+ *                               predicted object or -1), i32 pairs[cap][2] (gt object, predicted object), u32 pair_ptps[cap], u32 pair_rtps[cap]
+ *      STATUS bits: 1 a label outside 0..65535, 2 more than cap labels in a map, 4 the solver reached one of its iteration bounds
+ *      (non-finite scores only), 8 placement 1 and the frame does not fit.  A frame with a status has no usable tables.
+ * quber_munkres_batch is the solver alone: dev_score f64 [batch][cap][cap] holds a dev_rows[b] x dev_cols[b] cost matrix per frame (row
+ * stride cap; zero-padded to square as the reference does), dev_assign i32 [batch][cap] receives per row the assigned column or -1,
+ * dev_status i32 [batch] the bits 2 (shape outside 0..cap), 4, 8.  dev_workspace: batch * cap^2 * 8 bytes for placement 2, and for
+ * placement 0 with cap > 128; may be NULL otherwise. */
+int64_t quber_eval_batch_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t cap, int32_t with_boundary);
+int quber_eval_batch(const int32_t* dev_pred, const int32_t* dev_gt, int32_t batch, int32_t h, int32_t w, int32_t cap, int32_t bound_pix,
+                     int32_t with_boundary, int32_t placement, void* dev_workspace, void* dev_out, void* stream);
+int quber_munkres_batch(const double* dev_score, const int32_t* dev_rows, const int32_t* dev_cols, int32_t batch, int32_t cap,
+                        int32_t placement, void* dev_workspace, int32_t* dev_assign, int32_t* dev_status, void* stream);
+
 /* post-filter of eval/refiner_model.py:273-277 on LMFFNet logits (foreground_segmentation/predictor.py:85,98):
  *   dev_fg_logits f32 [B][n_classes][HW] -> dev_fg_mask u8 [B][HW] = (argmax == fg_class)
  *   dev_masks u8 [B][n_masks][HW] (may be NULL with n_masks = 0)

@@ -76,6 +76,9 @@ SIGNATURES = {
     "quber_label_contingency": (C.c_int, [_P, _P, C.c_int64, _I, _P, _P]),
     "quber_boundary_workspace_bytes": (C.c_int64, [_I, _I, _I]),
     "quber_boundary_overlap": (C.c_int, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "quber_eval_batch_workspace_bytes": (C.c_int64, [_I, _I, _I, _I, _I]),
+    "quber_eval_batch": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "quber_munkres_batch": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "quber_foreground_filter": (C.c_int, [_P, _I, _I, _P, _I, _I, C.c_int64, _P, _P, _P]),
     "quber_normalize_depth": (C.c_int, [_P, _I, C.c_int64, C.c_double, C.c_double, _P, _P, _P]),
     "quber_inpaint_telea_u8": (C.c_int, [_P, _P, _I, _I, _I, _P]),

@@ -627,6 +627,29 @@ int quber_boundary_overlap(const int32_t* pred, const int32_t* gt, int32_t h, in
     return launch_boundary_overlap(pred, gt, h, w, labels, n_pred, n_gt, bound_pix, workspace, out, (hipStream_t)stream);
 }
 
+int64_t quber_eval_batch_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t cap, int32_t with_boundary) {
+    if (batch < 1 || h < 1 || w < 1 || cap < 1 || cap > 256) return 0;
+    return (int64_t)eval_batch_ws_bytes(batch, h, w, cap, with_boundary);
+}
+
+int quber_eval_batch(const int32_t* pred, const int32_t* gt, int32_t batch, int32_t h, int32_t w, int32_t cap, int32_t bound_pix,
+                     int32_t with_boundary, int32_t placement, void* workspace, void* out, void* stream) {
+    if (!pred || !gt || !workspace || !out) return fail("quber_eval_batch: null pointer");
+    if (((uintptr_t)pred & 3) || ((uintptr_t)gt & 3) || ((uintptr_t)workspace & 7) || ((uintptr_t)out & 7))
+        return fail("quber_eval_batch: label maps must be 4-byte aligned, workspace and out 8-byte aligned");
+    return launch_eval_batch(pred, gt, batch, h, w, cap, bound_pix, with_boundary, placement, workspace, out, (hipStream_t)stream);
+}
+
+int quber_munkres_batch(const double* score, const int32_t* rows, const int32_t* cols, int32_t batch, int32_t cap, int32_t placement,
+                        void* workspace, int32_t* assign, int32_t* status, void* stream) {
+    if (!score || !rows || !cols || !assign || !status) return fail("quber_munkres_batch: null pointer");
+    if (((uintptr_t)score & 7) || ((uintptr_t)workspace & 7) || ((uintptr_t)rows & 3) || ((uintptr_t)cols & 3) || ((uintptr_t)assign & 3) ||
+        ((uintptr_t)status & 3))
+        return fail("quber_munkres_batch: misaligned pointer");
+    return launch_munkres_batch(score, rows, cols, batch, cap, placement, reinterpret_cast<double*>(workspace), assign, cap, status, 1,
+                                (hipStream_t)stream);
+}
+
 int quber_foreground_filter(const float* fg_logits, int32_t n_classes, int32_t fg_class, const uint8_t* masks,
                             int32_t batch, int32_t n_masks, int64_t hw, uint8_t* fg_mask, uint64_t* counts, void* stream) {
     if (!fg_logits || !fg_mask || batch < 1 || hw < 1 || n_classes < 2) return fail("bad argument to quber_foreground_filter");

@@ -274,6 +274,15 @@ int launch_boundary_overlap(const int* pred, const int* gt, int H, int W, const 
 size_t boundary_ws_bytes(int H, int W, int n_masks);
 int launch_contingency(const int* pred, const int* gt, long n, int cap, void* ws, hipStream_t st);
 size_t contingency_ws_bytes(int cap);
+// batched evaluation (evalbatch.hip): labels -> boundary -> score matrix -> Munkres assignment -> gather for B pairs of label maps, all on
+// `st`, no read-back; ws: eval_batch_ws_bytes, out: eval_batch_out_bytes.  launch_munkres_batch: the solver alone; assign / status of
+// frame b at assign + b * assign_stride / status + b * status_stride (strides in ints); mat [B][cap][cap] for the device-memory placement
+int launch_eval_batch(const int* pred, const int* gt, int batch, int H, int W, int cap, int radius, int with_boundary, int placement, void* ws,
+                      void* out, hipStream_t st);
+size_t eval_batch_ws_bytes(int batch, int H, int W, int cap, int with_boundary);
+size_t eval_batch_out_bytes(int batch, int cap);
+int launch_munkres_batch(const double* score, const int* rows, const int* cols, int batch, int cap, int placement, double* mat, int* assign,
+                         long assign_stride, int* status, long status_stride, hipStream_t st);
 
 int launch_encode(const uint8_t* masks, int B, int N, int H, int W, const float* gauss, int sigma, int legacy_f32,
                   void* ws, float* out, hipStream_t st);

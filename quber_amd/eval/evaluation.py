@@ -4,6 +4,10 @@ counts come from ONE pass of a HIP kernel over the two label maps instead of one
 true-positive counts of every pair (evaluation.py:21-54) come from three launches on bit planes (csrc/boundary.hip:
 seg2bmap as an outside flood fill + 4-neighbour test, disk dilation as shifted ORs).
 
+``multilabel_metrics_batch`` (``enqueue_metrics`` + ``collect_metrics``) evaluates B pairs in one call (csrc/evalbatch.hip): the tables, the
+F-measure matrix and the Munkres assignment stay on the device, one copy comes back, and ``_metrics_from_tables`` - the final arithmetic
+both paths share - turns every frame's record into the dictionary the per-frame function returns, bit for bit.
+
 The overlap half reproduces the imported reference bit for bit (tests/golden/metrics_*.npz).  The boundary half restates
 cv2.findContours / drawContours / dilate and skimage's disk from their published algorithms (neither library is in the
 image): parity unpinned."""
@@ -86,9 +90,12 @@ def boundary_counts(prediction, gt, labels_pred, labels_gt, bound_th=0.003, devi
             o[nm + n_gt * n_pred:].reshape(n_gt, n_pred))
 
 
-def multilabel_metrics(prediction, gt, i=0, N=0, obj_detect_threshold=0.75, compute_boundary_stuff=True, verbose=False,
-                       device="cuda:0"):
-    lp, lg, table = contingency(prediction, gt, device)
+def _metrics_from_tables(lp, lg, table, assignments=None, boundary=None, obj_detect_threshold=0.75):
+    """The final arithmetic of multilabel_metrics (evaluation.py:104-274), shared by the per-frame and the batched path.
+    lp / lg: sorted unique labels of the prediction / the ground truth; table int64 [len(lg), len(lp)]: the contingency table;
+    assignments: [(gt object, predicted object)] of the Munkres step, or None: solved here; boundary: None, the tuple
+    (bc_pred, bc_gt, ptps, rtps) of boundary_counts, or a callable (labels_pred, labels_gt) -> that tuple, called only for a frame
+    that has objects on both sides.  Every float sum stays a numpy sum in the reference's order."""
     area_pred, area_gt = table.sum(axis=0), table.sum(axis=1)     # incl. the background row / column
     kp, kg = lp != BACKGROUND_LABEL, lg != BACKGROUND_LABEL
     num_pred, num_gt = int(kp.sum()), int(kg.sum())
@@ -107,7 +114,9 @@ def multilabel_metrics(prediction, gt, i=0, N=0, obj_detect_threshold=0.75, comp
         P, R = tps / ap[None, :], tps / ag[:, None]
         F = (2 * P * R) / (P + R)
     F[np.isnan(F)] = 0
-    assignments = munkres_assign(F.max() - F)
+    if assignments is None:
+        assignments = munkres_assign(F.max() - F)
+    assignments = [(int(i), int(j)) for i, j in assignments]
     idx = tuple(np.array(assignments).T)
     detected = sum(1 for a in assignments if F[a] > obj_detect_threshold)
     fg_pred = float(area_pred[lp >= 1].sum())                      # np.sum(prediction.clip(0,1) == 1)
@@ -119,8 +128,8 @@ def multilabel_metrics(prediction, gt, i=0, N=0, obj_detect_threshold=0.75, comp
         if np.isnan(f_measure):
             f_measure = 0
         b = dict.fromkeys(("F", "P", "R", "Fo", "Po", "Ro"))
-        if compute_boundary_stuff:                                   # evaluation.py:165-175, 200-206, 232-243
-            bc_pred, bc_gt, ptps, rtps = boundary_counts(prediction, gt, lp[kp], lg[kg], device=device)
+        if boundary is not None:                                     # evaluation.py:165-175, 200-206, 232-243
+            bc_pred, bc_gt, ptps, rtps = boundary(lp[kp], lg[kg]) if callable(boundary) else boundary
             bP, bR = ptps / bc_pred[None, :], rtps / bc_gt[:, None]
             bF = (2 * bP * bR) / (bP + bR)
             bF[np.isnan(bF)] = 0
@@ -139,3 +148,165 @@ def multilabel_metrics(prediction, gt, i=0, N=0, obj_detect_threshold=0.75, comp
                'obj_detected_075_percentage_normalized': detected / max(num_gt, num_pred),
                'obj_mIOU_osn': np.mean(iou[idx]), 'obj_mIOU': np.sum(tps[idx]) / np.sum(union[idx])}
     return out
+
+
+def multilabel_metrics(prediction, gt, i=0, N=0, obj_detect_threshold=0.75, compute_boundary_stuff=True, verbose=False,
+                       device="cuda:0"):
+    lp, lg, table = contingency(prediction, gt, device)
+    boundary = (lambda op, og: boundary_counts(prediction, gt, op, og, device=device)) if compute_boundary_stuff else None
+    return _metrics_from_tables(lp, lg, table, None, boundary, obj_detect_threshold)
+
+
+# ------------------------------------------------------------------------------------------------ the batched path (csrc/evalbatch.hip)
+_EVAL_WS = {}           # (device, stream, B, h, w, cap, with_boundary) -> workspace tensor; the calls of one stream are ordered, so its handles share it
+_EVAL_WS_MAX = 8
+STATUS_BAD_LABEL, STATUS_OVER_CAP, STATUS_SOLVER_BOUND, STATUS_NO_LDS = 1, 2, 4, 8
+
+
+def record_layout(cap):
+    """Byte offsets of one frame's record in quber_eval_batch's dev_out (include/quber_hip.h) -> (offsets dict, record bytes)."""
+    c, cc = cap, cap * cap
+    off, o = {}, 0
+    for name, nbytes in (("table", 8 * cc), ("F", 8 * cc), ("area", 16 * c), ("pair_tps", 8 * c), ("pair_union", 8 * c),
+                         ("ptps", 4 * cc), ("rtps", 4 * cc), ("hdr", 32), ("labels", 8 * c), ("bc", 8 * c), ("assign", 4 * c),
+                         ("pairs", 8 * c), ("pair_ptps", 4 * c), ("pair_rtps", 4 * c)):
+        off[name] = o
+        o += nbytes
+    return off, (o + 7) & ~7
+
+
+class MetricsList(list):
+    """The dicts of collect_metrics.  `fallback`: {frame index: status} of the frames the batched call flagged (quber_eval_batch's
+    status bits) and the per-frame multilabel_metrics answered instead; `tables`: per frame the stage tables (return_tables=True)."""
+    fallback = None
+    tables = None
+
+
+class _Handle:
+    pass
+
+
+def _workspace(lib, device, B, h, w, cap, with_boundary):
+    key = (str(device), torch.cuda.current_stream().cuda_stream, B, h, w, cap, with_boundary)
+    ws = _EVAL_WS.get(key)
+    if ws is None:
+        if len(_EVAL_WS) >= _EVAL_WS_MAX:
+            _EVAL_WS.pop(next(iter(_EVAL_WS)))
+        nbytes = lib.quber_eval_batch_workspace_bytes(B, h, w, cap, with_boundary)
+        if nbytes <= 0:
+            raise ValueError(f"batched metrics: no workspace for batch {B}, {h} x {w}, cap {cap}")
+        ws = _EVAL_WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _as_device_maps(a, device):
+    """-> (int32 device tensor [B,H,W], the numpy original or None)."""
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda or a.dtype != torch.int32 or a.dim() != 3:
+            raise ValueError("batched metrics: tensors must be int32 [B,H,W] on the device (numpy arrays: any integer type)")
+        return a.contiguous(), None
+    host = np.asarray(a)
+    if host.ndim != 3 or host.dtype.kind not in "iub":
+        raise ValueError("batched metrics: label maps must be integer arrays [B,H,W]")
+    narrow = host
+    if host.dtype.itemsize > 4 or host.dtype == np.uint32:
+        narrow = np.clip(host, -1, 65536)        # what int32 cannot hold stays outside 0..65535: the frame is flagged, never aliased
+    return torch.from_numpy(np.ascontiguousarray(narrow, dtype=np.int32)).to(device), host
+
+
+def enqueue_metrics(preds, gts, compute_boundary_stuff=True, cap=64, bound_th=0.003, placement=0, obj_detect_threshold=0.75,
+                    return_tables=False, device="cuda:0"):
+    """multilabel_metrics for B pairs of label maps, enqueued on the current stream with nothing read back -> handle for collect_metrics.
+    preds, gts: numpy integer arrays or device int32 tensors [B,H,W].  cap: most distinct labels per map (background included) the
+    batched call handles, 1..256; placement: where the solver keeps its cost matrix (0 auto, 1 LDS, 2 device memory)."""
+    lib = _lib.load()
+    p, p_host = _as_device_maps(preds, device)
+    g, g_host = _as_device_maps(gts, p.device if isinstance(preds, torch.Tensor) else device)
+    if p.shape != g.shape or p.device != g.device:
+        raise ValueError("batched metrics: predictions and ground truths differ in shape or device")
+    B, h, w = (int(v) for v in p.shape)
+    with_boundary = int(bool(compute_boundary_stuff))
+    bound_pix = int(bound_th if bound_th >= 1 else np.ceil(bound_th * np.linalg.norm((h, w))))
+    hd = _Handle()
+    hd.shape, hd.cap, hd.with_boundary, hd.threshold, hd.return_tables = (B, h, w), int(cap), with_boundary, obj_detect_threshold, return_tables
+    hd.device = p.device
+    hd.inputs = (p, g)                       # alive until collected
+    hd.host = (p_host, g_host)
+    hd.offsets, hd.record = record_layout(hd.cap)
+    if B == 0:
+        hd.out = None
+        return hd
+    with torch.cuda.device(p.device):
+        ws = _workspace(lib, p.device, B, h, w, hd.cap, with_boundary)
+        hd.out = torch.empty(B * hd.record, dtype=torch.uint8, device=p.device)
+        _lib.check(lib.quber_eval_batch(C.c_void_p(p.data_ptr()), C.c_void_p(g.data_ptr()), B, h, w, hd.cap, bound_pix, with_boundary,
+                                        int(placement), C.c_void_p(ws.data_ptr()), C.c_void_p(hd.out.data_ptr()),
+                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        hd.done = torch.cuda.Event()
+        hd.done.record()
+    return hd
+
+
+def collect_metrics(handle):
+    """-> MetricsList of the dicts multilabel_metrics returns, one per pair, after ONE device-to-host copy."""
+    hd = handle
+    res = MetricsList()
+    res.fallback = {}
+    res.tables = [] if hd.return_tables else None
+    B, h, w = hd.shape
+    if B == 0:
+        return res
+    hd.done.synchronize()
+    host = hd.out.cpu().numpy().reshape(B, hd.record)
+    cap, off = hd.cap, hd.offsets
+
+    def field(b, name, dtype, count):
+        return host[b, off[name]:off[name] + count * np.dtype(dtype).itemsize].view(dtype)
+
+    for b in range(B):
+        n_pred, n_gt, _, status, no_p, no_g, n_pairs, _ = (int(v) for v in field(b, "hdr", np.int32, 8))
+        if status:
+            if status & STATUS_BAD_LABEL and hd.host[0] is None and hd.host[1] is None:
+                raise ValueError(f"batched metrics: frame {b} has label values outside 0..65535")
+            # flagged: answered by the per-frame function (which renumbers out-of-range labels of numpy input, as contingency does)
+            pm = hd.host[0][b] if hd.host[0] is not None else hd.inputs[0][b].cpu().numpy()
+            gm = hd.host[1][b] if hd.host[1] is not None else hd.inputs[1][b].cpu().numpy()
+            res.append(multilabel_metrics(pm, gm, obj_detect_threshold=hd.threshold, compute_boundary_stuff=bool(hd.with_boundary),
+                                          device=hd.device))
+            res.fallback[b] = status
+            if hd.return_tables:
+                res.tables.append({"status": status, "fallback": True})
+            continue
+        labels = field(b, "labels", np.int32, 2 * cap).reshape(2, cap)
+        lp, lg = labels[0, :n_pred].astype(np.int64), labels[1, :n_gt].astype(np.int64)
+        table = field(b, "table", np.uint64, cap * cap).reshape(cap, cap)[:n_gt, :n_pred].astype(np.int64)
+        pairs = field(b, "pairs", np.int32, 2 * cap).reshape(cap, 2)[:n_pairs]
+        assignment = [(int(i), int(j)) for i, j in pairs]
+        boundary = None
+        if hd.with_boundary:
+            bc = field(b, "bc", np.uint32, 2 * cap).reshape(2, cap).astype(np.float64)
+            ptps = field(b, "ptps", np.uint32, cap * cap).reshape(cap, cap)[:no_g, :no_p].astype(np.float64)
+            rtps = field(b, "rtps", np.uint32, cap * cap).reshape(cap, cap)[:no_g, :no_p].astype(np.float64)
+            boundary = (bc[0, :no_p], bc[1, :no_g], ptps, rtps)
+        res.append(_metrics_from_tables(lp, lg, table, assignment, boundary, hd.threshold))
+        if hd.return_tables:
+            t = {"labels_pred": lp, "labels_gt": lg, "table": table, "status": status, "fallback": False, "assignment": assignment,
+                 "F": field(b, "F", np.float64, cap * cap).reshape(cap, cap)[:no_g, :no_p].copy(),
+                 "bc_pred": None, "bc_gt": None, "ptps": None, "rtps": None,
+                 "pair_tps": field(b, "pair_tps", np.uint64, cap)[:n_pairs].astype(np.int64),
+                 "pair_union": field(b, "pair_union", np.uint64, cap)[:n_pairs].astype(np.int64),
+                 "pair_ptps": field(b, "pair_ptps", np.uint32, cap)[:n_pairs].astype(np.int64),
+                 "pair_rtps": field(b, "pair_rtps", np.uint32, cap)[:n_pairs].astype(np.int64)}
+            if boundary is not None:
+                t["bc_pred"], t["bc_gt"], t["ptps"], t["rtps"] = boundary
+            res.tables.append(t)
+    return res
+
+
+def multilabel_metrics_batch(preds, gts, compute_boundary_stuff=True, cap=64, bound_th=0.003, placement=0, obj_detect_threshold=0.75,
+                             return_tables=False, device="cuda:0"):
+    """[multilabel_metrics(p, g) for p, g in zip(preds, gts)], bit for bit, from one enqueue and one copy back.  With
+    return_tables=True -> (dicts, tables)."""
+    res = collect_metrics(enqueue_metrics(preds, gts, compute_boundary_stuff, cap, bound_th, placement, obj_detect_threshold,
+                                          return_tables, device))
+    return (res, res.tables) if return_tables else res

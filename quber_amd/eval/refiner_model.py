@@ -66,6 +66,43 @@ def inpaint_depth(depth, kernel_size=3):
     return out
 
 
+# the annotation labels the reference's evaluation loop treats as background on OCID (eval/eval_utils.py:33-35)
+OCID_BG_LABELS = {"floor": (0, 1), "table": (0, 1, 2)}
+
+
+def load_annotation(anno_path, rgb_path, dataset, resize=None):
+    """The annotation of one frame as the reference's loop prepares it (eval/eval_utils.py:240-248): read, nearest resize to 640x480,
+    and on OCID the floor / table labels set to 0.  anno_path: a file, or the array already read; resize: cv2.resize's stand-in
+    (img u8, h, w, linear) -> img, e.g. MaskRefiner._resize - needed only for an annotation of another size."""
+    anno = np.array(anno_path) if isinstance(anno_path, np.ndarray) else np.array(Image.open(anno_path))
+    if anno.shape[:2] != (H, W):
+        if resize is None:
+            raise ValueError(f"annotation of {anno.shape[:2]}: pass resize= (MaskRefiner._resize) to bring it to {(H, W)}")
+        if anno.dtype == np.uint8:
+            anno = np.array(resize(anno, H, W, False))
+        elif anno.ndim == 2:                         # nearest picks whole pixels: the bytes of a wider type go through as channels
+            raw = np.ascontiguousarray(anno)
+            planes = raw.view(np.uint8).reshape(raw.shape[0], raw.shape[1], raw.dtype.itemsize)
+            anno = np.ascontiguousarray(resize(planes, H, W, False)).view(raw.dtype).reshape(H, W)
+        else:
+            raise ValueError("annotation: only 8-bit images have a multi-channel resize")
+    if dataset == "OCID":
+        floor_table = "floor" if "floor" in rgb_path else "table" if "table" in rgb_path else None
+        if floor_table is None:
+            raise ValueError(f"OCID frame {rgb_path!r}: neither a floor nor a table scene")
+        for label in OCID_BG_LABELS[floor_table]:
+            anno[anno == label] = 0
+    return anno
+
+
+def label_map_from_masks(masks, shape, dtype=np.int32):
+    """The label map the reference's loop paints from a list of masks (eval/eval_utils.py:281-286): mask i as i + 1, later masks on top."""
+    pred = np.zeros(shape, dtype)
+    for i, mask in enumerate(masks):
+        pred[np.asarray(mask) > False] = i + 1
+    return pred
+
+
 def resize_shortest_edge_shape(oldh, oldw, short_edge_length=800, max_size=1333):
     """[d2] ResizeShortestEdge.get_output_shape, used by the armbench branch (refiner_model.py:228)."""
     scale = short_edge_length * 1.0 / min(oldh, oldw)
@@ -363,6 +400,53 @@ class MaskRefiner:
                 pending = (group, hd)
             if pending is not None:
                 yield from collect(*pending)
+
+    def evaluate_stream(self, items, anno_paths, workers=2, batch=1, cap=64):
+        """predict_stream plus the evaluation step of the reference's loop (eval/eval_utils.py:240-250, 281-286, 337-338): yields
+        (refined_masks, output, seconds, fg_mask, initial_metrics, refined_metrics) per item, in order.  anno_paths: one annotation file
+        (or array) per item.  Per group of up to max(batch, 1) frames of one size the initial and the refined label maps are painted and
+        their 2k pairs evaluated by ONE multilabel_metrics_batch call (csrc/evalbatch.hip) on a stream of its own, while
+        predict_stream already has the next group enqueued.  cap: most labels per map the batched call handles; a frame above it is
+        answered by the per-frame function."""
+        from .evaluation import multilabel_metrics_batch
+        from collections import deque
+        k = max(int(batch), 1)
+        dev = self.refiner_predictor.device
+        seen = deque()                               # (initial masks, rgb path) of the items predict_stream has pulled, in order
+
+        def tee():
+            for item in items:
+                seen.append((item[2], item[0]))
+                yield item
+
+        side = torch.cuda.Stream(device=dev)
+
+        def evaluate(group):
+            shape = group[0][1].shape
+            preds = np.stack([label_map_from_masks(init, shape) for _, _, init in group] +
+                             [label_map_from_masks(res[0], shape) for res, _, _ in group])
+            gts = np.stack([anno for _, anno, _ in group] * 2)
+            with torch.cuda.stream(side):
+                metrics = multilabel_metrics_batch(preds, gts, cap=cap, device=dev)
+            n = len(group)
+            for i, (res, _, _) in enumerate(group):
+                yield tuple(res) + (metrics[i], metrics[n + i])
+
+        group = []
+        for res, anno_path in zip(self.predict_stream(tee(), workers=workers, batch=batch), anno_paths):
+            init, rgb_path = seen.popleft()
+            anno = load_annotation(anno_path, rgb_path, self.dataset, self._resize)
+            if anno.ndim != 2:
+                raise ValueError("annotation must be a single-channel label image")
+            if group and anno.shape != group[0][1].shape:
+                yield from evaluate(group)
+                group = []
+            group.append((res, anno, init))
+            if len(group) >= k:                      # predict_stream has the next group enqueued by now
+                yield from evaluate(group)
+                group = []
+        if group:
+            yield from evaluate(group)
 
 
 class MaskRefinerTTA(MaskRefiner):
