@@ -686,6 +686,33 @@ int quber_op_upsample_logits(const float* dev_q, float* dev_out, int32_t batch, 
 int quber_op_preprocess(const uint8_t* dev_bgr, const uint8_t* dev_depth, const float* dev_offsets, void* dev_x, int32_t x_c, int32_t es,
                         int32_t batch, int32_t batch_cap, int32_t h, int32_t w, const float* mean6, const float* std6, int32_t streams,
                         void* stream);
+/* The kernels of the LMFFNet foreground network (csrc/lmff.hip), each on explicit fp32 NHWC views - test hooks: the network reaches them
+ * only through quber_forward of a with_network = 2 context.  A view is (pointer to its first channel, cs = elements between two pixels)
+ * over batch x h x w x c; scale / shift / slope are per-channel device arrays of c floats.  A view the launcher refuses returns the
+ * launcher's error and launches nothing.  No op allocates or synchronises.
+ *   quber_op_lmff_preprocess   u8 HWC bgr + depth [pixels][3] -> x [pixels][8]: (bgr / 255 - mean) / std in float64, depth / 255, two zeros
+ *   quber_op_lmff_dwconv       y = prelu(bn(depthwise 3x3 of x, dilation = padding = dil)); dev_w9 [c][3][3].  16-byte accesses when c, both
+ *                              cs and both base addresses allow it, one channel per lane otherwise
+ *   quber_op_lmff_pool         mode 0: AvgPool2d(3, 2, 1) (divisor 9), mode 1: MaxPool2d(2, 2), h x w -> oh x ow; a max pool whose window
+ *                              leaves the map (h < 2 oh or w < 2 ow) is refused
+ *   quber_op_lmff_affine       y = prelu((a [+ b]) * scale + shift); dev_b may be NULL
+ *   quber_op_lmff_pmca         dev_wts f32 [batch][c] = sigmoid(fc2(prelu(fc0(dw2x2(adaptive_avg_pool 2x2 (x)) + global_avg_pool(x))))), c = 64 or
+ *                              128 in aligned groups of 4 (anything else is refused); dev_sums: f64 [batch][c][5] scratch
+ *   quber_op_lmff_scale        y[b][pixel][ch] = dev_wts[b][ch] * x[b][pixel][ch]
+ *   quber_op_lmff_gate         planar dev_q [batch][c][h*w] = o * sigmoid(att) of two NHWC views */
+int quber_op_lmff_preprocess(const uint8_t* dev_bgr, const uint8_t* dev_depth, int64_t pixels, float* dev_x, void* stream);
+int quber_op_lmff_dwconv(const float* dev_x, int32_t x_cs, float* dev_y, int32_t y_cs, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t dil,
+                         const float* dev_w9, const float* dev_scale, const float* dev_shift, const float* dev_slope, void* stream);
+int quber_op_lmff_pool(const float* dev_x, int32_t x_cs, float* dev_y, int32_t y_cs, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t oh,
+                       int32_t ow, int32_t mode, void* stream);
+int quber_op_lmff_affine(const float* dev_a, int32_t a_cs, const float* dev_b, int32_t b_cs, float* dev_y, int32_t y_cs, int32_t batch, int32_t h,
+                         int32_t w, int32_t c, const float* dev_scale, const float* dev_shift, const float* dev_slope, void* stream);
+int quber_op_lmff_pmca(const float* dev_x, int32_t x_cs, int32_t batch, int32_t h, int32_t w, int32_t c, const float* dev_w2x2, const float* dev_fc0,
+                       const float* dev_alpha, const float* dev_fc2, float* dev_wts, double* dev_sums, void* stream);
+int quber_op_lmff_scale(const float* dev_x, int32_t x_cs, const float* dev_wts, float* dev_y, int32_t y_cs, int32_t batch, int32_t h, int32_t w,
+                        int32_t c, void* stream);
+int quber_op_lmff_gate(const float* dev_o, int32_t o_cs, const float* dev_att, int32_t att_cs, float* dev_q, int32_t batch, int32_t h, int32_t w,
+                       int32_t c, void* stream);
 /* a9 alone, on a caller-supplied centre list in ANY order - group_pixels(ctr, offsets) of post_processing.py:44-76
  * (quber_postprocess derives its centres from the centre plane, i.e. always in raster order; the reference's function takes
  * whatever list it is handed).  The grouping kernel quber_postprocess launches, unchanged.

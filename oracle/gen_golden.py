@@ -49,7 +49,8 @@ def gen_lmffnet():
     ref_keys = [k for k in net.state_dict() if "num_batches" not in k]
     assert set(ref_keys) == set(sd) and all(tuple(net.state_dict()[k].shape) == sd[k].shape for k in ref_keys)
     net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=False)
-    for (h, wd, seed) in [(64, 96, 1), (120, 160, 2)]:
+    # 72 x 88: the stride-8 map is 9 x 11, odd both ways (the 2 x 2 adaptive-pool bins of the 128-channel PMCA overlap in rows and columns)
+    for (h, wd, seed) in [(64, 96, 1), (120, 160, 2), (72, 88, 3)]:
         sc = synth.make_scene(seed, h, wd, 3)
         with torch.no_grad():
             ref = net(L.preprocess(sc["rgb"], sc["depth"]))

@@ -653,6 +653,7 @@ int quber_munkres_batch(const double* score, const int32_t* rows, const int32_t*
 int quber_foreground_filter(const float* fg_logits, int32_t n_classes, int32_t fg_class, const uint8_t* masks,
                             int32_t batch, int32_t n_masks, int64_t hw, uint8_t* fg_mask, uint64_t* counts, void* stream) {
     if (!fg_logits || !fg_mask || batch < 1 || hw < 1 || n_classes < 2) return fail("bad argument to quber_foreground_filter");
+    if (n_masks < 0 || n_masks > 65535) return fail("quber_foreground_filter: n_masks outside 0..65535");     // grid.y of the overlap kernel
     hipStream_t st = (hipStream_t)stream;
     int rc = launch_argmax_fg(fg_logits, batch, hw, n_classes, fg_class, fg_mask, st);
     if (rc || n_masks == 0) return rc;

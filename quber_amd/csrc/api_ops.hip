@@ -283,6 +283,42 @@ int quber_op_group_pixels(const float* logits, int32_t n_planes, int32_t batch, 
     return launch_group_pixels(logits, n_planes, batch, h, w, cap, centers, ncenters, ids, area, (hipStream_t)stream);
 }
 
+// ---- the LMFFNet kernels of lmff.hip on explicit fp32 views (tests): arguments -> View -> launcher, nothing else ----
+static View lview(const void* p, int B, int h, int w, int c, int cs) { return opview(p, B, h, w, c, cs, 0, 4); }
+
+int quber_op_lmff_preprocess(const uint8_t* bgr, const uint8_t* depth, int64_t pixels, float* x, void* stream) {
+    return launch_lmff_preprocess(bgr, depth, (long)pixels, x, (hipStream_t)stream);
+}
+
+int quber_op_lmff_dwconv(const float* x, int32_t x_cs, float* y, int32_t y_cs, int32_t B, int32_t h, int32_t w, int32_t c, int32_t dil, const float* w9,
+                         const float* scale, const float* shift, const float* slope, void* stream) {
+    return launch_dwconv3x3(lview(x, B, h, w, c, x_cs), lview(y, B, h, w, c, y_cs), B, dil, w9, scale, shift, slope, (hipStream_t)stream);
+}
+
+int quber_op_lmff_pool(const float* x, int32_t x_cs, float* y, int32_t y_cs, int32_t B, int32_t h, int32_t w, int32_t c, int32_t oh, int32_t ow, int32_t mode,
+                       void* stream) {
+    return launch_pool_s2(lview(x, B, h, w, c, x_cs), lview(y, B, oh, ow, c, y_cs), B, mode, (hipStream_t)stream);
+}
+
+int quber_op_lmff_affine(const float* a, int32_t a_cs, const float* b, int32_t b_cs, float* y, int32_t y_cs, int32_t B, int32_t h, int32_t w, int32_t c,
+                         const float* scale, const float* shift, const float* slope, void* stream) {
+    const View bv = lview(b, B, h, w, c, b_cs);
+    return launch_affine_prelu(lview(a, B, h, w, c, a_cs), b ? &bv : nullptr, lview(y, B, h, w, c, y_cs), B, scale, shift, slope, (hipStream_t)stream);
+}
+
+int quber_op_lmff_pmca(const float* x, int32_t x_cs, int32_t B, int32_t h, int32_t w, int32_t c, const float* w2x2, const float* fc0, const float* alpha,
+                       const float* fc2, float* wts, double* sums, void* stream) {
+    return launch_pmca(lview(x, B, h, w, c, x_cs), B, w2x2, fc0, alpha, fc2, wts, sums, (hipStream_t)stream);
+}
+
+int quber_op_lmff_scale(const float* x, int32_t x_cs, const float* wts, float* y, int32_t y_cs, int32_t B, int32_t h, int32_t w, int32_t c, void* stream) {
+    return launch_scale_channels(lview(x, B, h, w, c, x_cs), wts, lview(y, B, h, w, c, y_cs), B, (hipStream_t)stream);
+}
+
+int quber_op_lmff_gate(const float* o, int32_t o_cs, const float* att, int32_t att_cs, float* q, int32_t B, int32_t h, int32_t w, int32_t c, void* stream) {
+    return launch_mad_gate(lview(o, B, h, w, c, o_cs), lview(att, B, h, w, c, att_cs), q, B, c, (hipStream_t)stream);
+}
+
 int quber_op_maxpool3x3s2(const float* x, int32_t B, int32_t h, int32_t w, int32_t c, float* y, void* stream) {
     if (c % 4) return fail("maxpool: channels must be a multiple of 4");
     return launch_maxpool3x3s2(mkview(x, B, h, w, c), mkview(y, B, (h + 1) / 2, (w + 1) / 2, c), B, 1, (hipStream_t)stream);

@@ -122,6 +122,103 @@ def test_lmffnet_oracle_matches_reference(path):
     assert len(w) == 402 and sum(v.numel() for v in w.values()) == 1356859 - 65     # the reference state_dict minus its 65 num_batches_tracked counters
 
 
+def _lmffnet_forward_unstaged(x, w):
+    """oracle.lmffnet_torch.forward as it was before it became the composition of per-launch functions: kept to hold the staged
+    form to the same bits."""
+    import torch.nn.functional as F
+    from oracle.lmffnet_torch import SEM1_DIL, SEM2_DIL
+
+    def bnp(t, n):
+        t = F.batch_norm(t, w[n + ".bn.running_mean"], w[n + ".bn.running_var"], w[n + ".bn.weight"], w[n + ".bn.bias"],
+                         False, 0.0, 1e-3)
+        return F.prelu(t, w[n + ".acti.weight"])
+
+    def conv(t, n, stride=1, pad=0, dil=1, groups=1):
+        return F.conv2d(t, w[n + ".conv.weight"], None, stride, pad, dil, groups)
+
+    def cbp(t, n, **kw):
+        return bnp(conv(t, n, **kw), n + ".bn_prelu")
+
+    def sem(t, n, d):
+        c = t.shape[1]
+        o = cbp(t, n + ".conv3x3", pad=1)
+        left = cbp(o[:, :c // 4], n + ".dconv_left", pad=1, groups=c // 4)
+        right = cbp(o[:, c // 4:], n + ".dconv_right", pad=d, dil=d, groups=c // 4)
+        o = cbp(torch.cat([left, right], 1), n + ".conv3x3_resume.conv3x3", pad=1)
+        o = conv(o, n + ".conv3x3_resume.conv1x1_resume")
+        return bnp(o + t, n + ".bn_relu_1")
+
+    def down(t, n, cout):
+        o = conv(t, n + ".conv3x3", stride=2, pad=1)
+        if t.shape[1] < cout:
+            o = torch.cat([o, F.max_pool2d(t, 2, 2)], 1)
+        return bnp(o, n + ".bn_prelu")
+
+    def inject(t, r):
+        for _ in range(r):
+            t = F.avg_pool2d(t, 3, 2, 1)
+        return t
+
+    def pmca(t, n):
+        c = t.shape[1]
+        o1 = F.conv2d(F.adaptive_avg_pool2d(t, (2, 2)), w[n + ".conv2x2.conv.weight"], None, 1, 0, 1, c)
+        s = (o1 + F.adaptive_avg_pool2d(t, 1)).flatten(1)
+        s = F.prelu(F.linear(s, w[n + ".SE_Block.fc.0.weight"]), w[n + ".SE_Block.fc.1.weight"])
+        s = torch.sigmoid(F.linear(s, w[n + ".SE_Block.fc.2.weight"]))
+        return s[:, :, None, None] * t
+
+    init = x
+    for i in range(3):
+        init = cbp(init, f"Init_Block.init_conv.{i}", stride=2 if i == 0 else 1, pad=1)
+    ffa = conv(bnp(torch.cat([init, inject(x, 1)], 1), "FFM_A.bn_prelu"), "FFM_A.conv1x1")
+    d1 = down(ffa, "downsample_1", 64)
+    s1 = d1
+    for i, d in enumerate(SEM1_DIL):
+        s1 = sem(s1, f"SEM_B_Block1.SEM_B_Block.SEM_Block_1{i}", d)
+    fb1 = conv(bnp(torch.cat([s1, pmca(d1, "FFM_B1.PMCA"), inject(x, 2)], 1), "FFM_B1.bn_prelu"), "FFM_B1.conv1x1")
+    d2 = down(fb1, "downsample_2", 128)
+    s2 = d2
+    for i, d in enumerate(SEM2_DIL):
+        s2 = sem(s2, f"SEM_B_Block2.SEM_B_Block.SEM_Block_2{i}", d)
+    fb2 = conv(bnp(torch.cat([s2, pmca(d2, "FFM_B2.PMCA"), inject(x, 3)], 1), "FFM_B2.bn_prelu"), "FFM_B2.conv1x1")
+    h, ww = fb2.shape[-2:]
+    up = lambda t, f: F.interpolate(t, [h * f, ww * f], mode="bilinear", align_corners=False)
+    cat = torch.cat([conv(fb1, "MAD.mid_layer_1x1"), up(conv(fb2, "MAD.deep_layer_1x1"), 2)], 1)
+    att = torch.sigmoid(conv(cbp(cat, "MAD.DwConv1", pad=1, groups=48), "MAD.PwConv1"))
+    o = up(conv(cbp(fb2, "MAD.DwConv2", pad=1, groups=fb2.shape[1]), "MAD.PwConv2"), 2)
+    return up(o * att, 8), {"ffm_a": ffa, "d1": d1, "ffm_b1": fb1, "ffm_b2": fb2}
+
+
+@pytest.mark.parametrize("path", golden("lmffnet"), ids=os.path.basename)
+def test_lmffnet_staged_oracle_same_bits(path):
+    """The oracle's forward is the composition of one function per launch of the HIP plan (oracle.lmffnet_torch.plan).  It returns
+    the bits of the unstaged forward it replaced - logits and the four intermediates both name - stays within 1e-5 of the reference
+    module's logits, and names one step per plan op: 96 ops, the PMCA op and the last op being two launches each."""
+    from oracle import lmffnet_torch as L
+    from quber_amd import lmff_arch
+    z = np.load(path)
+    w = {k: torch.from_numpy(v) for k, v in lmff_arch.init_state_dict(seed=int(z["seed"])).items()}
+    x = L.preprocess(z["rgb"], z["depth"])
+    taps = {}
+    with torch.no_grad():
+        got = L.forward(x, w, taps)
+        old, old_taps = _lmffnet_forward_unstaged(x, w)
+    assert got.dtype == torch.float32
+    assert np.array_equal(got.numpy().view(np.uint32), old.numpy().view(np.uint32))
+    for k, v in old_taps.items():
+        assert np.array_equal(taps[k].numpy(), v.numpy()), k
+    np.testing.assert_allclose(got[0].numpy(), z["logits"], rtol=0, atol=1e-5)
+    steps = L.plan()
+    assert [s.op for s in steps if s.kind not in ("scale", "upsample")] == list(range(96)) and len(steps) == 99
+    assert len({s.out for s in steps}) == 99 and all(s.out in taps for s in steps)
+    assert taps["A"].shape[1] == 38 and taps["Bc"].shape[1] == 134 and taps["Cc"].shape[1] == 262
+    # every function runs in float64 as well, and float32 stays at rounding distance of it
+    w64 = {k: v.double() for k, v in w.items()}
+    with torch.no_grad():
+        ref = L.forward(x.double(), w64)
+    assert ref.dtype == torch.float64 and float((got.double() - ref).abs().max()) < 5e-5
+
+
 def _same_metrics(got, exp):
     assert set(got) == set(exp)
     for k, v in exp.items():
