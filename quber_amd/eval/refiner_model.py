@@ -34,7 +34,7 @@ from PIL import Image
 
 from .. import engine as qengine
 from ..masknms import check_scores
-from ..maskrefiner.predictor import MaskRefinerPredictor
+from ..maskrefiner.predictor import MaskRefinerPredictor, RefineOptions, mask_bytes
 
 W = 640
 H = 480
@@ -118,25 +118,14 @@ class MaskRefiner:
                  lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
                  decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
                  nms=None, zoom=None):
-        # tta: every frame and its W-mirror in one forward, logits merged on the device (MaskRefinerPredictor(tta=True))
-        # decode_errors: the error heads' class maps, histograms and per-mask class counts in every output dict
-        # iterations / until_converged / track_initial: the refined masks fed back for further passes on the device, early stop at a
-        # fixed point (predict() only: the stream always runs the fixed count), initial_overlap / initial_index / initial_iou in every
-        # output dict (INTEGRATION.md "Iterative refinement")
-        # cleanup: None, a quber_amd.cleanup.Cleanup, "largest" (the UOIS path's largest_connected_component, 4-connected) or "holes"
-        # (the SAM refiner's remove_small_regions(mask, 300, "holes")), applied on the device after post-processing
-        # perturb: None or a quber_amd.perturb.Perturb - the initial masks degraded by the reference's perturb_seg on the device before
-        # they are encoded (INTEGRATION.md "Perturbed initial masks"); predict() and predict_stream(batch=k) alike
-        # nms: None or a quber_amd.masknms.MaskNMS - the initial masks are scored, overlapping proposals (a SAM-style base model) and
-        # the reference's nms + combine_masks_with_NMS makes them disjoint on the device first (INTEGRATION.md "Overlapping initial
-        # masks"); predict(..., mask_scores=) and a fifth element of predict_stream's items carry the scores
-        # zoom: None or a quber_amd.zoom.ZoomIn - a second pass on a padded, resized crop of every refined instance, pasted back on the
-        # device, the reference's ucn-zoomin / msmformer-zoomin base models' second stage (INTEGRATION.md "Zoom-in refinement"); predict()
-        # only: predict_stream refuses it
-        self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, tta=tta,
-                                                      decode_errors=decode_errors, iterations=iterations,
-                                                      until_converged=until_converged, track_initial=track_initial, cleanup=cleanup,
-                                                      perturb=perturb, nms=nms, zoom=zoom)
+        # tta ... zoom: the predictor's options (maskrefiner/predictor.py: module docstring, RefineOptions), for predict()
+        # and predict_stream(batch=k) alike, except: until_converged stops early in predict() only (the stream always runs the fixed
+        # count); cleanup "largest" is the UOIS path's largest_connected_component (4-connected), "holes" the SAM refiner's
+        # remove_small_regions(mask, 300, "holes"); nms takes its scores from predict(..., mask_scores=) and a fifth element of
+        # predict_stream's items; zoom is predict() only: predict_stream refuses it
+        options = RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
+                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom)
+        self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, options=options)
         self.dataset = dataset
         self.lmffnet = None
         # "host" / True (default): csrc/inpaint.hip on the calling (worker) thread; "device": csrc/inpaint_dev.hip, bit-equal, for hosts
@@ -161,9 +150,7 @@ class MaskRefiner:
         """File reading and the adapter's pre-processing of one frame (eval/refiner_model.py:224-263): everything before the
         reference's timer starts.  Safe to run on a worker thread (predict_stream): its device work goes to a side stream."""
         rgb = np.asarray(Image.open(rgb_path).convert("RGB"))[:, :, ::-1]        # BGR like cv2.imread
-        initial_masks = np.asarray(initial_masks)
-        if initial_masks.dtype == np.bool_:
-            initial_masks = np.uint8(initial_masks) * 255
+        initial_masks = mask_bytes(initial_masks, True)   # a bool mask is 0 / 255 from here on, whatever the options
         scores = None
         if self.refiner_predictor.nms is not None:        # missing or non-finite scores: refused here, before any device work
             scores = check_scores(mask_scores, len(initial_masks))
@@ -313,8 +300,8 @@ class MaskRefiner:
                         fr["d_depth"] = fr["depth_dev"]          # already there (normalised, resized, in-painted on the device)
                     else:
                         fr["d_depth"] = None if fr["depth"] is None else torch.from_numpy(np.ascontiguousarray(fr["depth"])).to(dev, non_blocking=True)
-                    # (the encoder tests the mask bytes for non-zero, csrc/encode.hip: bool / 0-255 masks upload as they are)
-                    fr["d_masks"] = torch.from_numpy(np.ascontiguousarray(m.view(np.uint8) if m.dtype == np.bool_ else m.astype(np.uint8, copy=False))).to(dev, non_blocking=True)
+                    # (0-255 masks upload as they are; what is neither bool nor uint8 is cast, here alone)
+                    fr["d_masks"] = torch.from_numpy(np.ascontiguousarray(mask_bytes(m, False).astype(np.uint8, copy=False))).to(dev, non_blocking=True)
                     if fr["scores"] is not None:
                         fr["d_scores"] = torch.from_numpy(fr["scores"]).to(dev, non_blocking=True)
                     fr["ready"] = torch.cuda.Event()
@@ -331,12 +318,9 @@ class MaskRefiner:
             two = self.refiner_predictor.depth_on and self.refiner_predictor.rgb_on
             B_ = len(frs)
             own = [f["d_masks"].shape[0] for f in frs]      # each frame's own masks among the n rows of the batch
-            if model.tta:
-                # test-time augmentation: the frames go straight into the first halves of 2B-frame buffers (the flip fills the rest)
-                d_rgb, d_depth, d_masks = model.tta_alloc(B_, H_, W_, n, two)
-                d_masks[:B_].zero_()
-            else:
-                d_masks = torch.zeros((B_, n, H_, W_), dtype=torch.uint8, device=dev)
+            # B-frame tensors; test-time augmentation: the frames go straight into the first halves of 2B-frame buffers (the flip fills the rest)
+            d_rgb, d_depth, d_masks = model.batch_buffers(B_, H_, W_, n, two)
+            d_masks[:B_].zero_()
             for b, f in enumerate(frs):
                 if f["d_masks"].shape[0]:
                     d_masks[b, :f["d_masks"].shape[0]] = f["d_masks"]
@@ -347,15 +331,11 @@ class MaskRefiner:
                     if f["d_masks"].shape[0]:
                         d_scores[b, :f["d_masks"].shape[0]] = f["d_scores"]
             img = [f["d_rgb"] if self.refiner_predictor.rgb_on else f["d_depth"] for f in frs]   # depth-only: the image IS the depth map
-            if model.tta:
-                torch.stack(img, out=d_rgb[:B_])
-                if two:
-                    torch.stack([f["d_depth"] for f in frs], out=d_depth[:B_])
-                return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, halves=True, n_masks=own,
-                                           d_scores=d_scores)
-            d_rgb = torch.stack(img)
-            d_depth = torch.stack([f["d_depth"] for f in frs]) if two else None
-            return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, n_masks=own, d_scores=d_scores)
+            torch.stack(img, out=d_rgb[:B_])
+            if two:
+                torch.stack([f["d_depth"] for f in frs], out=d_depth[:B_])
+            return model.enqueue_batch(d_rgb, d_depth, d_masks, slots=max(32, n + 12), capacity=k, halves=model.tta, n_masks=own,
+                                       d_scores=d_scores)
 
         def collect(frs, hd):
             outs, ms, host = self.refiner_predictor.model.collect_batch(hd, host_masks=True)

@@ -48,6 +48,7 @@ There is no CPU fallback: construction fails if the HIP library or a GPU is miss
 """
 import os
 import warnings
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -99,6 +100,80 @@ def match_initial(table, area, n, k):
     return tab, torch.where(touched, first, torch.full_like(first, -1)), torch.where(touched, best, torch.zeros_like(best)).to(torch.float32)
 
 
+@dataclass(frozen=True)
+class RefineOptions:
+    """The options of the module docstring, validated and parsed once.  MaskRefiner, MaskRefinerPredictor and RefinerModel take them as
+    keywords and hand this record on; each holds it as `options` and its fields as plain attributes (`model.tta`, `model.nms`, ...)."""
+    tta: bool = False                 # every frame and its W-mirror in one forward of 2B frames, logits merged on the device
+    decode_errors: bool = False       # per error head the class map, its histogram and the per-mask class counts in every dict
+    iterations: int = 1               # passes per call, the refined masks fed back on the device
+    until_converged: bool = False     # stop at a fixed point (predict / predict_batch; the stream always runs the fixed count)
+    track_initial: bool = False       # initial_overlap / initial_index / initial_iou in every dict
+    cleanup: Cleanup = None           # connected-component clean-up right after every post-processing pass
+    perturb: Perturb = None           # the initial masks degraded on the device before anything reads them
+    nms: MaskNMS = None               # scored, overlapping initial masks made disjoint on the device before anything else reads them
+    zoom: ZoomIn = None               # a second pass on a padded, resized crop of every instance, pasted back on the device
+
+    @classmethod
+    def parse(cls, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
+              nms=None, zoom=None):
+        if int(iterations) < 1:
+            raise ValueError("iterations must be >= 1")
+        if perturb is not None and not isinstance(perturb, Perturb):
+            raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
+        zoom, nms = ZoomIn.parse(zoom), MaskNMS.parse(nms)
+        return cls(bool(tta), bool(decode_errors), int(iterations), bool(until_converged), bool(track_initial), Cleanup.parse(cleanup),
+                   perturb, nms, zoom)
+
+    def for_crops(self):
+        """The crop pass of zoom: the same tta, iterations and cleanup; nothing that concerns the caller's initial masks."""
+        return RefineOptions(tta=self.tta, iterations=self.iterations, cleanup=self.cleanup)
+
+
+@dataclass(slots=True)
+class PassResult:
+    """What device_pass enqueued for B frames: the engine, the last pass's logits and post tables, the initial masks u8 [B,N,H,W] as
+    the network saw them, and what refine() / track() / decode() / perturb_masks() / nms_masks() returned (None: option off).  own: per
+    frame, how many of the N mask rows are the frame's own - the rows of initial_overlap, perturbed_masks and nms_masks; a sequence
+    indexed by frame (under nms in the stream: a pinned tensor the NMS's counts are copied into, valid once e1 has passed).
+    enqueue_batch alone fills the rest - this record is its handle: the pre-extracted masks u8 [B,slots,H,W], the pinned instance
+    counts and refine_converged_at, the events around the batch."""
+    eng: object
+    B: int
+    logits: object
+    post: dict
+    d_masks: object = None
+    own: object = None
+    it: dict = None
+    ov: tuple = None
+    err: dict = None
+    pt: tuple = None
+    nm: dict = None
+    masks: object = None
+    slots: int = 0
+    count: object = None
+    conv: object = None
+    e0: object = None
+    e1: object = None
+
+
+def mask_bytes(m, as_bytes, binarise=False):
+    """The bytes an array of initial masks uploads as.  uint8 goes as it stands; bool as 0 / 1 - the encoder tests for non-zero
+    (csrc/encode.hip) - or, with as_bytes (perturb or nms will read the byte values: perturb_seg thresholds at 127), as 0 / 255.  The
+    call sites differ in the rest, and each keeps its bytes: MaskRefiner._load passes as_bytes=True whatever the options (a bool mask is
+    0 / 255 from there on) and leaves every other dtype to predict(), which sends it through predict_batch; predict_stream's load casts
+    what is left to uint8; predict_batch alone passes binarise=True: every dtype goes through `m != 0`, so without as_bytes a uint8 255
+    uploads as 1 there and as 255 through predict() - the same network input, different bytes."""
+    m = np.asarray(m)
+    if m.dtype == np.uint8 and (as_bytes or not binarise):
+        return m
+    if m.dtype != np.bool_:
+        if not binarise:
+            return m
+        m = m != 0
+    return m.view(np.uint8) * np.uint8(255) if as_bytes else m.view(np.uint8)
+
+
 class _FrameStaging:
     """Buffers of the batch-1 call path for one frame size, allocated once: ONE pinned host block and ONE device block for the
     frame's inputs (bgr | depth | initial masks, uploaded in a few pipelined pieces), the device-side intermediates, and pinned
@@ -140,37 +215,18 @@ class RefinerModel:
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
     def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False, iterations=1, until_converged=False,
-                 track_initial=False, cleanup=None, perturb=None, nms=None, zoom=None):
-        if int(iterations) < 1:
-            raise ValueError("iterations must be >= 1")
-        if perturb is not None and not isinstance(perturb, Perturb):
-            raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
-        # a second pass on a padded, resized crop of every instance, pasted back on the device (INTEGRATION.md "Zoom-in refinement"); None:
-        # one look at the full frame
-        self.zoom = ZoomIn.parse(zoom)
+                 track_initial=False, cleanup=None, perturb=None, nms=None, zoom=None, options=None):
+        # options: a RefineOptions in place of the nine keywords.  Its fields become plain attributes, which is what the code below
+        # reads (a test and a tool switch model.decode_errors between calls)
+        self.options = options or RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
+                                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom)
+        vars(self).update(vars(self.options))
         self._zoom_model = None   # the crop pass: a RefinerModel on the same cfg and weights, built by the first zoomed call
         self.debug_zoom = None    # tests: a list that receives, per zoomed call, the inputs and outputs of every stage
-        # scored, overlapping initial masks made disjoint on the device before anything else reads them (INTEGRATION.md "Overlapping
-        # initial masks"); None: the masks are an instance segmentation already
-        self.nms = MaskNMS.parse(nms)
-        # the initial masks degraded on the device before anything reads them (INTEGRATION.md "Perturbed initial masks"); None: as uploaded
-        self.perturb = perturb
         self._perturb_dev = {}    # (frames, masks, H, W) -> the programs and targets of such a call on the device
-        # connected-component clean-up of the instances right after every post-processing pass (INTEGRATION.md): None, a Cleanup,
-        # "largest" or "holes"; everything downstream - masks, the feed-back of a further pass, tracking - sees the cleaned instances
-        self.cleanup = Cleanup.parse(cleanup)
         self.cfg = cfg
         self.state_dict = state_dict
         self.device = torch.device(device)
-        self.tta = bool(tta)      # horizontal-flip test-time augmentation in predict_one / enqueue_batch: engines of capacity 2B
-        # every frame dict also carries, per error head, the class map, its histogram and (where the initial masks are on the device)
-        # the per-mask class counts (INTEGRATION.md "Predicted error maps"); off: today's keys, no extra kernel
-        self.decode_errors = bool(decode_errors)
-        # iterative refinement (INTEGRATION.md): passes per call, early stop at a fixed point (predict_one / predict_batch only),
-        # initial_overlap / initial_index / initial_iou in every dict
-        self.iterations = int(iterations)
-        self.until_converged = bool(until_converged)
-        self.track_initial = bool(track_initial)
         self.top_k = 200 if cfg is None else int(cfg.MODEL.PANOPTIC_DEEPLAB.TOP_K_INSTANCE)
         assert 1 <= self.top_k <= 254, "the label-map encoding holds at most 254 instances per frame"
         self.debug_passes = None  # tests: a list that receives, per pass, its input ids, logits, post tables and refined ids
@@ -257,47 +313,35 @@ class RefinerModel:
         src.copy_(out)
         return out, rep
 
-    # -- device-side pipeline on already-resident tensors --
-    def run(self, bgr, depth, offsets):
-        B, H, W = bgr.shape[:3]
-        eng = self.engine_for(H, W, B)
-        logits = eng.forward(bgr, depth, offsets)
-        post = self.postprocess(eng, logits)
-        return eng, logits, post
-
     # -- horizontal-flip test-time augmentation --
-    def tta_alloc(self, B, H, W, n, depth=True):
+    def tta_alloc(self, B, H, W, n, depth=True, frames=2):
         """Empty 2B-frame device buffers (bgr, depth or None, masks [2B,n,H,W]): the caller fills frames [0, B) directly, the flip
         kernel fills [B, 2B)."""
         dev = self.device
-        bgr = torch.empty((2 * B, H, W, 3), dtype=torch.uint8, device=dev)
-        return bgr, torch.empty_like(bgr) if depth else None, torch.empty((2 * B, n, H, W), dtype=torch.uint8, device=dev)
+        bgr = torch.empty((frames * B, H, W, 3), dtype=torch.uint8, device=dev)
+        return bgr, torch.empty_like(bgr) if depth else None, torch.empty((frames * B, n, H, W), dtype=torch.uint8, device=dev)
 
-    def tta_buffers(self, d_bgr, d_depth, d_masks):
-        """2B-frame buffers holding copies of B frames that are already on the device in B-frame tensors (enqueue_batch called without
-        `halves`); callers that can fill the first halves directly use tta_alloc instead."""
-        B, H, W = d_bgr.shape[:3]
-        bufs = self.tta_alloc(B, H, W, d_masks.shape[1], d_depth is not None)
-        for buf, t in zip(bufs, (d_bgr, d_depth, d_masks)):
-            if t is not None:
-                buf[:B].copy_(t)
-        return bufs
+    def batch_buffers(self, B, H, W, n, depth=True):
+        """Empty device buffers a caller uploads B frames into, rows [0, B): B-frame tensors, or with tta the 2B-frame ones of tta_alloc
+        (enqueue_batch: halves=True)."""
+        return self.tta_alloc(B, H, W, n, depth, 2 if self.tta else 1)
+
+    def initial_offsets(self, eng, masks, frames, out=None):
+        """a1: the encoding of masks u8 [frames,N,H,W] -> f32 [frames,3,H,W] (`out`, if given); all zero for N = 0 or no masks."""
+        if masks is not None and masks.shape[1]:
+            return eng.encode(masks, out)
+        if out is None:
+            return torch.zeros((frames, 3, eng.H, eng.W), dtype=torch.float32, device=self.device)
+        return out.zero_()
 
     def tta_logits(self, eng, bgr2, depth2, masks2, offsets=None, ready=False):
         """The augmented forward on 2B-frame buffers whose first halves hold the frames, all on the current stream: mirror the
         inputs into the second halves, a1 on all 2B frames (the mirrored frames' own encoding), one forward of 2B frames, merge
         -> logits f32 [B,planes,H,W] of the B frames.  `offsets`: an optional [2B,3,H,W] buffer for a1.  ready=True (a pass >= 2 of
         the iterative refinement): the images are mirrored already and `offsets` holds a1 of all 2B frames."""
-        if ready:
-            return eng.tta_merge(eng.forward(bgr2, depth2, offsets))
-        n = 0 if masks2 is None else masks2.shape[1]
-        eng.tta_flip_inputs(bgr2, depth2, masks2 if n else None)
-        if n:
-            offsets = eng.encode(masks2, offsets)
-        elif offsets is None:
-            offsets = torch.zeros((bgr2.shape[0], 3, eng.H, eng.W), dtype=torch.float32, device=self.device)
-        else:
-            offsets.zero_()
+        if not ready:
+            eng.tta_flip_inputs(bgr2, depth2, masks2 if masks2 is not None and masks2.shape[1] else None)
+            offsets = self.initial_offsets(eng, masks2, bgr2.shape[0], offsets)
         return eng.tta_merge(eng.forward(bgr2, depth2, offsets))
 
     def decode(self, eng, logits, d_masks=None):
@@ -354,19 +398,46 @@ class RefinerModel:
         ids = it["ids"] if it is not None else eng.relabel_panoptic(post)
         return eng.overlap_masks(d_masks, ids, eng.cap, out=out)
 
+    # -- the one sequence predict_one, enqueue_batch and predict_batch run; they differ in who owns the buffers and where the host reads --
+    def device_pass(self, eng, bgr, depth, masks, scores, B, *, may_stop, bufs=None, own=None, slots=None):
+        """Enqueues nms -> perturb -> encode (tta: mirror, encode) -> forward -> postprocess -> refine -> track -> decode for B frames on
+        the current stream -> PassResult.  bgr / depth (or None) u8 [f*B,H,W,3] and masks u8 [f*B,N,H,W] on the device, f = 2 under tta
+        with the frames in the first halves; scores f32 [B,N] (required with nms).  Nothing is read back unless may_stop and
+        until_converged (refine()).  bufs: predict_one's _FrameStaging - its offsets, post tables, iteration buffers and overlap tables
+        are written instead of fresh tensors.  own: see PassResult; default all N rows.  slots (the stream): the first `slots` masks
+        of every frame are extracted between track and decode, where the stream has always launched that."""
+        N = masks.shape[1]
+        nm = self.nms_masks(eng, masks, scores, B)
+        pt = self.perturb_masks(eng, masks, B)            # before the mirror, the encoding and everything else that reads the masks
+        offsets = bufs.offsets if bufs is not None else None
+        if self.tta:                                      # (either way the logits are a fresh tensor, owned by the caller through the dict)
+            logits = self.tta_logits(eng, bgr, depth, masks, offsets)
+        else:
+            logits = eng.forward(bgr, depth, self.initial_offsets(eng, masks, B, offsets))
+        post = self.postprocess(eng, logits, bufs.post if bufs is not None else None)
+        logits, post, it = self.refine(eng, bgr, depth, logits, post, B, may_stop, bufs.iter_bufs if bufs is not None else None)
+        d_masks = masks[:B]
+        ov = self.track(eng, d_masks, post, it, (bufs.overlap[0][:, :N], bufs.overlap[1]) if bufs is not None and self.track_initial else None)
+        rec = PassResult(eng, B, logits, post, d_masks=d_masks, own=[N] * B if own is None else own, it=it, ov=ov, pt=pt, nm=nm)
+        if slots is not None:
+            rec.slots = min(max(1, slots), eng.cap)
+            rec.masks = eng.extract_masks(post, rec.slots)
+        rec.err = self.decode(eng, logits, d_masks if it is None else None)    # (a pass >= 2 has no initial masks to attribute to)
+        return rec
+
     # -- zoom-in refinement (INTEGRATION.md "Zoom-in refinement") --
     def zoom_model(self):
-        """The crop pass: this model's cfg, weights, tta, iterations and cleanup; nothing that concerns the caller's initial masks."""
+        """The crop pass: this model's cfg and weights with RefineOptions.for_crops()."""
         if self._zoom_model is None:
-            self._zoom_model = RefinerModel(self.cfg, self.state_dict, self.device, tta=self.tta, iterations=self.iterations, cleanup=self.cleanup)
+            self._zoom_model = RefinerModel(self.cfg, self.state_dict, self.device, options=self.options.for_crops())
         return self._zoom_model
 
-    def zoom_pass(self, eng, bgr, depth, post, it, count, outs):
-        """zoom: pass 2 on the instances pass 1 left in `post` (bgr / depth: the B frames on the device; count: their instance counts on
-        the host; it: what refine() returned).  rois -> crops -> the crop pass in chunks of zoom.batch crops through enqueue_batch /
-        collect_batch on the engine for (crop, crop) -> paste; then the dicts `outs` are rewritten: instances -> coarse_instances, the
-        zoomed instances, zoom_ids / zoom_rois / zoom_report."""
-        z, dev = self.zoom, self.device
+    def zoom_pass(self, rec, bgr, depth, count, outs):
+        """zoom: pass 2 on the instances pass 1 left in rec.post (bgr / depth: the B frames on the device; count: their instance counts
+        on the host).  rois -> crops -> the crop pass in chunks of zoom.batch crops through enqueue_batch / collect_batch on the engine
+        for (crop, crop) -> paste; then the dicts `outs` are rewritten: instances -> coarse_instances, the zoomed instances, zoom_ids /
+        zoom_rois / zoom_report."""
+        z, dev, eng, post, it = self.zoom, self.device, rec.eng, rec.post, rec.it
         B, S, n_ids = len(outs), self.zoom.crop, eng.cap
         ids = it["ids"] if it is not None else eng.relabel_panoptic(post)
         rois = eng.zoom_rois(ids, n_ids, z.padding)
@@ -382,12 +453,12 @@ class RefinerModel:
             for a in range(0, T, z.batch):
                 e = min(T, a + z.batch)
                 hd = inner.enqueue_batch(bc[a:e], None if dc is None else dc[a:e], mc[a:e], slots=1, capacity=z.batch)
-                ceng = hd["eng"]
-                cid = hd["it"]["ids"] if hd["it"] is not None else ceng.relabel_panoptic(hd["post"])
+                ceng = hd.eng
+                cid = hd.it["ids"] if hd.it is not None else ceng.relabel_panoptic(hd.post)
                 table, area = ceng.overlap_masks(mc[a:e], cid, ceng.cap)
-                parts.append((cid, hd["post"]["scores"], table.view(e - a, ceng.cap + 1), area))
+                parts.append((cid, hd.post["scores"], table.view(e - a, ceng.cap + 1), area))
                 inner.collect_batch(hd)
-                crop_count.extend(int(c) for c in hd["count"].numpy())
+                crop_count.extend(int(c) for c in hd.count.numpy())
             C = ceng.cap
             crop_ids, crop_scores, table, area = (torch.cat([p[i] for p in parts]).contiguous() for i in range(4))
             per_frame = np.bincount(slots_h[:, 0], weights=np.asarray(crop_count, np.float64), minlength=B)
@@ -421,36 +492,33 @@ class RefinerModel:
                 r["instances"] = inst
         return outs
 
-    def frame_dict(self, eng, logits_b, post, b, k, masks_b, err=None, n_masks=None, it=None, conv=0, ov=None, n_own=None, pt=None, nm=None):
-        """The reference's output dict of one frame (model.py:304-356) from the device-side results.  err: what decode() returned
-        for the batch; n_masks: the frame's own initial masks (the leading rows of its mask histogram and of initial_overlap);
-        it / conv: what refine() returned and the frame's refine_converged_at on the host; ov: what track() returned; n_own: per frame
-        of the batch, the rows of initial_overlap where n_masks is not given (collect_batch: the mask histogram keeps all N rows);
-        pt: what perturb_masks() returned; nm: what nms_masks() returned (its masks are then the initial masks n_masks / n_own count)."""
-        qc = eng.qcfg
+    def frame_dict(self, rec, b, k, masks_b, conv):
+        """The reference's output dict of frame b (model.py:304-356) from a PassResult.  k: its instance count and masks_b: its k masks
+        (bool, or None), conv: its refine_converged_at - all three read back by the caller.  The per-mask histograms keep all N rows
+        here (results() trims them to the frame's own)."""
+        eng, post, it, ov, pt, nm = rec.eng, rec.post, rec.it, rec.ov, rec.pt, rec.nm
+        qc, logits_b = eng.qcfg, rec.logits[b]
         ncls, o = qc.error_classes, 4
+        n = int(rec.own[b]) if rec.own is not None else None
         r = {"sem_seg": logits_b[0:1], "panoptic_seg": (post["panoptic"][b], None)}
         if qc.eee_boundary_on:                       # model.py:310-313
             r["eee_boundary"] = logits_b[o:o + ncls]
             o += ncls
         if qc.eee_mask_on:
             r["eee_mask"] = logits_b[o:o + ncls]
-        for head, (cls, hist, mh) in (err or {}).items():
+        for head, (cls, hist, mh) in (rec.err or {}).items():
             r[head + "_classes"], r[head + "_hist"] = cls[b], hist[b]
             if mh is not None:
-                r[head + "_mask_hist"] = mh[b] if n_masks is None else mh[b, :n_masks]
+                r[head + "_mask_hist"] = mh[b]
         if nm is not None:
-            n = n_masks if n_masks is not None else int(n_own[b]) if n_own is not None else nm["masks"].shape[1]
             r["nms_masks"], r["nms_source"], r["nms_scores"] = nm["masks"][b, :n], nm["source"][b, :n].to(torch.int64), nm["scores"][b, :n]
             r["nms_report"] = nm["report"][b, :2].to(torch.int64)
         if pt is not None:
-            n = n_masks if n_masks is not None else int(n_own[b]) if n_own is not None else pt[0].shape[1]
             r["perturbed_masks"], r["perturb_report"] = pt[0][b, :n], pt[1][b, :n].to(torch.int64)
         if it is not None:
             r["refine_passes"], r["refine_converged_at"] = it["passes"], int(conv)
         if ov is not None:
-            r["initial_overlap"], first, iou = match_initial(
-                ov[0][b], ov[1][b], n_masks if n_masks is not None else int(n_own[b]) if n_own is not None else ov[0].shape[1], k)
+            r["initial_overlap"], first, iou = match_initial(ov[0][b], ov[1][b], n, k)
         if k > 0:
             labels = post["labels"][b, :k]
             inst = Instances((eng.H, eng.W))
@@ -466,26 +534,26 @@ class RefinerModel:
             r["instances"] = inst
         return r
 
-    def results(self, eng, logits, post, d_masks=None, n_masks=None, it=None, ov=None, pt=None, nm=None, images=None):
-        """One D2H of the small per-frame tables, then mask extraction for exactly max(count) slots.  d_masks / n_masks (decode_errors):
-        the initial masks on the device and how many of them are each frame's own.  it / ov: what refine() / track() returned.
-        nm: what nms_masks() returned - each frame's own initial masks are then the `count` of its report.  images (required with zoom=):
-        the (bgr, depth) device tensors pass 1 ran on."""
-        B = logits.shape[0]
-        if nm is not None:
-            n_masks = [int(c) for c in nm["report"][:, 0].cpu().numpy()]
-        err = self.decode(eng, logits, d_masks if it is None else None)       # (a pass >= 2 has no initial masks to attribute to)
+    def results(self, rec, images=None):
+        """The dicts of a PassResult: one D2H of the small per-frame tables, then mask extraction for exactly max(count) slots.  Under
+        nms each frame's own initial masks are the `count` of the NMS's report, read here.  The per-mask histograms are trimmed to the
+        frame's own rows (the stream keeps all N).  images (required with zoom=): the (bgr, depth) device tensors pass 1 ran on."""
+        eng, post, B = rec.eng, rec.post, rec.B
+        if rec.nm is not None:
+            rec.own = [int(c) for c in rec.nm["report"][:, 0].cpu().numpy()]
         count = post["count"].cpu().numpy()
-        conv = it["conv"].cpu().numpy() if it is not None else np.zeros((B,), np.int32)
+        conv = rec.it["conv"].cpu().numpy() if rec.it is not None else np.zeros((B,), np.int32)
         kmax = int(count.max()) if B else 0
         masks = eng.extract_masks(post, kmax) if kmax > 0 else None
-        outs = [self.frame_dict(eng, logits[b], post, b, int(count[b]), masks[b, :int(count[b])].bool() if count[b] > 0 else None,
-                                err, None if n_masks is None else n_masks[b], it, conv[b], ov, None, pt, nm)
-                for b in range(B)]
+        outs = [self.frame_dict(rec, b, int(count[b]), masks[b, :int(count[b])].bool() if count[b] > 0 else None, conv[b]) for b in range(B)]
+        for b, r in enumerate(outs):
+            for key in r:
+                if key.endswith("_mask_hist"):
+                    r[key] = r[key][:rec.own[b]]
         if self.zoom is not None:
             if images is None:
                 raise ValueError("zoom: this call path has no zoomed form (predict and predict_batch have)")
-            outs = self.zoom_pass(eng, images[0], images[1], post, it, count, outs)
+            outs = self.zoom_pass(rec, images[0], images[1], count, outs)
         return outs
 
     def predict_one(self, bgr, depth, masks):
@@ -516,47 +584,31 @@ class RefinerModel:
             if two:
                 stg.dev_in[od:od + 3 * hw].copy_(stg.pin_in[3 * hw:6 * hw], non_blocking=True)
         if n:
-            # the encoder tests the mask bytes for non-zero (csrc/encode.hip), so uint8 / bool masks upload as they are
-            src = masks.view(np.uint8) if masks.dtype == np.bool_ else masks
+            # the encoder tests the mask bytes for non-zero (csrc/encode.hip), so uint8 / bool masks upload as they are (mask_bytes)
             step = max(1, (n + 2) // 3)
             for a in range(0, n, step):
                 b = min(n, a + step)
-                np.copyto(stg.np_in[o + a * hw:o + b * hw].reshape(b - a, H, W), src[a:b], casting="unsafe")
+                np.copyto(stg.np_in[o + a * hw:o + b * hw].reshape(b - a, H, W), masks[a:b], casting="unsafe")
                 stg.dev_in[om + a * hw:om + b * hw].copy_(stg.pin_in[o + a * hw:o + b * hw], non_blocking=True)
         stg.done.record()
         d_bgr = stg.dev_in[:3 * f * hw].view(f, H, W, 3)
         d_dep = stg.dev_in[od:od + 3 * f * hw].view(f, H, W, 3) if two else None
         d_masks = stg.dev_in[om:om + f * n * hw].view(f, n, H, W)
-        pt = self.perturb_masks(eng, d_masks, 1)          # before the mirror, the encoding and everything else that reads the masks
-        if f == 2:
-            logits = self.tta_logits(eng, d_bgr, d_dep, d_masks, stg.offsets)     # merged: owned by the caller through the dict
-        else:
-            if n:
-                eng.encode(d_masks, stg.offsets)
-            else:
-                stg.offsets.zero_()
-            logits = eng.forward(d_bgr, d_dep, stg.offsets)        # fresh tensor: owned by the caller through the dict
-        post = self.postprocess(eng, logits, stg.post)
-        logits, post, it = self.refine(eng, d_bgr, d_dep, logits, post, 1, True, stg.iter_bufs)
-        ov = None
-        if self.track_initial:
-            ov = self.track(eng, d_masks[:1], post, it, (stg.overlap[0][:, :n], stg.overlap[1]))
-        err = self.decode(eng, logits, d_masks[:1] if it is None else None)
+        rec = self.device_pass(eng, d_bgr, d_dep, d_masks, None, 1, may_stop=True, bufs=stg)
+        post = rec.post
         stg.pin_count[:1].copy_(post["count"], non_blocking=True)
-        if it is not None:
-            stg.pin_count[1:].copy_(it["conv"], non_blocking=True)
+        if rec.it is not None:
+            stg.pin_count[1:].copy_(rec.it["conv"], non_blocking=True)
         torch.cuda.current_stream().synchronize()
         k = int(stg.pin_count[0])
-        post_out = {"panoptic": post["panoptic"].clone(), "labels": post["labels"].clone(), "scores": post["scores"].clone(),
-                    "boxes": post["boxes"].clone()}
-        if "cc_report" in post:
-            post_out["cc_report"] = post["cc_report"].clone()
+        # the dict owns clones: the staging's tables are the next call's
+        rec.post = {key: post[key].clone() for key in ("panoptic", "labels", "scores", "boxes", "cc_report") if key in post}
         masks_b = None
         if k > 0:
             masks_b = eng.extract_masks(post, k)[0].view(torch.bool)      # the kernel writes 0 / 1 bytes
         # (the caller's ``.to('cpu')`` of the masks is a plain D2H copy into fresh pageable memory: 0.17 ms for 5 MB, which a
         # prefetch into a pinned buffer plus the copy out of it does not beat - tools/predict_profile.py)
-        return self.frame_dict(eng, logits[0], post_out, 0, k, masks_b, err, None, it, int(stg.pin_count[1]) if it is not None else 0, ov, None, pt)
+        return self.frame_dict(rec, 0, k, masks_b, int(stg.pin_count[1]) if rec.it is not None else 0)
 
     # -- batched form on device-resident frames, split into "enqueue" and "collect" so that a caller can keep one batch in flight --
     def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None, d_scores=None):
@@ -578,57 +630,45 @@ class RefinerModel:
         eng = self.engine_for(H, W, f * max(B, capacity), d_masks.shape[1])      # (`capacity`: the caller's batch size - a short last batch must not rebuild)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        if self.tta and not halves:
-            d_bgr, d_depth, d_masks = self.tta_buffers(d_bgr, d_depth, d_masks)
-        nm = self.nms_masks(eng, d_masks, d_scores, B)    # (in the caller's tensor, unless tta_buffers has just copied it)
-        pt = self.perturb_masks(eng, d_masks, B)
-        if self.tta:
-            logits = self.tta_logits(eng, d_bgr, d_depth, d_masks)
-        else:
-            if d_masks.shape[1]:
-                offsets = eng.encode(d_masks)
-            else:
-                offsets = torch.zeros((B, 3, H, W), dtype=torch.float32, device=self.device)
-            logits = eng.forward(d_bgr, d_depth, offsets)
-        post = self.postprocess(eng, logits)
-        logits, post, it = self.refine(eng, d_bgr, d_depth, logits, post, B)           # always the fixed count: nothing is read back here
-        ov = self.track(eng, d_masks[:B], post, it)
-        slots = min(max(1, slots), eng.cap)
-        masks = eng.extract_masks(post, slots)
-        err = self.decode(eng, logits, d_masks[:B] if it is None else None)
+        if self.tta and not halves:                       # B-frame tensors: copied into the first halves of 2B-frame buffers
+            src = (d_bgr, d_depth, d_masks)
+            d_bgr, d_depth, d_masks = self.tta_alloc(B, H, W, d_masks.shape[1], d_depth is not None)
+            for buf, t in zip((d_bgr, d_depth, d_masks), src):
+                if t is not None:
+                    buf[:B].copy_(t)
+        # (nms and perturb write the caller's masks, unless they have just been copied); may_stop=False: always the fixed count, nothing
+        # is read back here
+        rec = self.device_pass(eng, d_bgr, d_depth, d_masks, d_scores, B, may_stop=False, own=n_masks, slots=slots)
         pinned = torch.zeros((2, B), dtype=torch.int32).pin_memory()                   # instance counts, refine_converged_at
-        count = pinned[0]
-        count.copy_(post["count"], non_blocking=True)
-        if it is not None:
-            pinned[1].copy_(it["conv"], non_blocking=True)
-        if nm is not None:                                # each frame's own initial masks: the NMS's count, read at collect_batch
+        rec.count, rec.conv, rec.e0, rec.e1 = pinned[0], pinned[1], e0, e1
+        rec.count.copy_(rec.post["count"], non_blocking=True)
+        if rec.it is not None:
+            rec.conv.copy_(rec.it["conv"], non_blocking=True)
+        if rec.nm is not None:                            # each frame's own initial masks: the NMS's count, read at collect_batch
             rep = torch.zeros((B, 4), dtype=torch.int32).pin_memory()
-            rep.copy_(nm["report"], non_blocking=True)
-            n_masks = rep[:, 0]
+            rep.copy_(rec.nm["report"], non_blocking=True)
+            rec.own = rep[:, 0]
         e1.record()
         eng._in_flight = getattr(eng, "_in_flight", 0) + 1
-        return {"eng": eng, "logits": logits, "post": post, "masks": masks, "slots": slots, "count": count, "e0": e0, "e1": e1,
-                "err": err, "it": it, "conv": pinned[1], "ov": ov,
-                "n_masks": n_masks, "pt": pt, "nm": nm}
+        return rec
 
     def collect_batch(self, hd, host_masks=False):
         """-> (list of the reference's per-frame output dicts, device milliseconds of the whole batch[, per-frame numpy masks]).
         host_masks: also the refined masks of every frame as numpy bool [K_b, H, W] - what the reference's caller takes with
         output['instances'].to('cpu').pred_masks.numpy() - through ONE device-to-host copy for the whole batch (the arrays of a
         batch are views of one host block)."""
-        hd["e1"].synchronize()
-        eng, post, count, conv = hd["eng"], hd["post"], hd["count"].numpy(), hd["conv"].numpy()
+        hd.e1.synchronize()
+        eng, post, count, conv = hd.eng, hd.post, hd.count.numpy(), hd.conv.numpy()
         kmax = int(count.max()) if len(count) else 0
-        ready = hd["e1"]
-        masks = hd["masks"]
-        if kmax > hd["slots"]:                       # rare: more instances than pre-extracted slots - extracted now, on the caller's stream
+        ready = hd.e1
+        masks = hd.masks
+        if kmax > hd.slots:                          # rare: more instances than pre-extracted slots - extracted now, on the caller's stream
             masks = eng.extract_masks(post, kmax)
             ready = torch.cuda.Event()
             ready.record()
-        outs = [self.frame_dict(eng, hd["logits"][b], post, b, int(count[b]), masks[b, :int(count[b])].view(torch.bool) if count[b] > 0 else None,
-                                hd.get("err"), None, hd.get("it"), conv[b], hd.get("ov"), hd.get("n_masks"), hd.get("pt"), hd.get("nm"))
+        outs = [self.frame_dict(hd, b, int(count[b]), masks[b, :int(count[b])].view(torch.bool) if count[b] > 0 else None, conv[b])
                 for b in range(len(count))]
-        ms = hd["e0"].elapsed_time(hd["e1"])
+        ms = hd.e0.elapsed_time(hd.e1)
         eng._in_flight = max(0, getattr(eng, "_in_flight", 1) - 1)
         if not host_masks:
             self._release_retired(eng)
@@ -690,22 +730,20 @@ class RefinerModel:
         hwc = imgs.to(torch.uint8).permute(0, 2, 3, 1)
         bgr = hwc[..., :3].contiguous()
         depth = hwc[..., 3:].contiguous() if nch == 6 else None
-        eng, logits, post = self.run(bgr, depth, offs)
-        return self.results(eng, logits, post)
+        eng = self.engine_for(bgr.shape[1], bgr.shape[2], len(bgr))
+        logits = eng.forward(bgr, depth, offs)                  # ready-made offsets: no initial masks, so nothing to count, track or perturb
+        post = self.postprocess(eng, logits)
+        return self.results(PassResult(eng, len(bgr), logits, post, err=self.decode(eng, logits)))
 
 
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
                  seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False,
-                 cleanup=None, perturb=None, nms=None, zoom=None):
-        if int(iterations) < 1:
-            raise ValueError("iterations must be >= 1")
-        if perturb is not None and not isinstance(perturb, Perturb):
-            raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
-        self.zoom = ZoomIn.parse(zoom)                # a second, zoomed-in pass on every instance, pasted back on the device; None: none
-        self.nms = MaskNMS.parse(nms)                 # scored, overlapping initial masks made disjoint on the device first; None: taken as they are
-        self.perturb = perturb                        # the initial masks degraded on the device before they are encoded; None: as uploaded
-        self.cleanup = Cleanup.parse(cleanup)         # the connected-component clean-up after post-processing; None: none
+                 cleanup=None, perturb=None, nms=None, zoom=None, options=None):
+        # the options (module docstring), checked before anything is loaded; options: a RefineOptions in their place
+        self.options = options or RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
+                                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom)
+        vars(self).update(vars(self.options))
         if config_file is None:
             self.cfg = qconfig.canonical_cfg()
         else:
@@ -730,15 +768,7 @@ class MaskRefinerPredictor:
                 warnings.warn(f"weights '{weights_file}' not found; using seeded synthetic weights")
             sd = arch.init_state_dict(seed=seed, **kw)
         self.cfg.MODEL.WEIGHTS = path or "<synthetic seed %d>" % seed
-        self.tta = bool(tta)          # horizontal-flip test-time augmentation in predict() / predict_batch()
-        # the error heads decoded on the device: `<head>_classes`, `<head>_hist`, `<head>_mask_hist` beside the logits in every dict
-        self.decode_errors = bool(decode_errors)
-        # iterative refinement: `iterations` passes per call, the refined masks fed back on the device; until_converged:
-        # predict() / predict_batch() stop at a fixed point; track_initial: initial_overlap / initial_index / initial_iou in every dict
-        self.iterations, self.until_converged, self.track_initial = int(iterations), bool(until_converged), bool(track_initial)
-        self.model = RefinerModel(self.cfg, sd, device, tta=self.tta, decode_errors=self.decode_errors, iterations=self.iterations,
-                                  until_converged=self.until_converged, track_initial=self.track_initial, cleanup=self.cleanup,
-                                  perturb=self.perturb, nms=self.nms, zoom=self.zoom)
+        self.model = RefinerModel(self.cfg, sd, device, options=self.options)
         self.device = torch.device(device)
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
@@ -749,8 +779,6 @@ class MaskRefinerPredictor:
             return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks], [mask_scores])
         if self.zoom is not None:                         # the general path: it keeps the frame on the device for the crops
             return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks])
-        if self.perturb is not None and masks.dtype == np.bool_:
-            masks = masks.view(np.uint8) * np.uint8(255)          # perturb_seg thresholds at 127: a bool mask counts as 0 / 255
         if not self.fast_path or masks.dtype not in (np.uint8, np.bool_) or masks.ndim != 3:
             return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks])
         if self.depth_on and depth_img is None:
@@ -759,7 +787,7 @@ class MaskRefinerPredictor:
             rgb_img, depth_img = depth_img, None
         elif not self.depth_on:
             depth_img = None
-        return [self.model.predict_one(rgb_img, depth_img, masks)]
+        return [self.model.predict_one(rgb_img, depth_img, mask_bytes(masks, self.perturb is not None))]
 
     def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None):
         """rgb_imgs/depth_imgs: u8 [B,H,W,3] arrays; masks_list: B arrays u8/bool [N_b,H,W]; scores_list (required with nms=): B arrays
@@ -782,31 +810,15 @@ class MaskRefinerPredictor:
         mk = np.zeros((B, n, H, W), np.uint8)
         for b, m in enumerate(masks_list):
             if len(m):
-                m = np.asarray(m)
-                if self.perturb is None and self.nms is None:
-                    mk[b, :len(m)] = m != 0
-                else:                                     # perturb_seg reads the bytes: uint8 as they stand, anything else as 0 / 255 (the NMS: non-zero)
-                    mk[b, :len(m)] = m if m.dtype == np.uint8 else (m != 0) * np.uint8(255)
-        dev = self.device
-        eng = self.model.engine_for(H, W, 2 * B if self.tta else B, n)
-        if self.tta:                                      # uploaded straight into the first halves of the 2B-frame buffers
-            bgr, depth, d_masks = self.model.tta_alloc(B, H, W, n, depth_imgs is not None)
-            bgr[:B].copy_(torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)))
-            if depth is not None:
-                depth[:B].copy_(torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)))
-            d_masks[:B].copy_(torch.from_numpy(mk))
-            nm = self.model.nms_masks(eng, d_masks, None if sc is None else torch.from_numpy(sc).to(dev), B)
-            pt = self.model.perturb_masks(eng, d_masks, B)
-            logits = self.model.tta_logits(eng, bgr, depth, d_masks)
-        else:
-            d_masks = torch.from_numpy(mk).to(dev)
-            bgr = torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)).to(dev)
-            depth = None if depth_imgs is None else torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)).to(dev)
-            nm = self.model.nms_masks(eng, d_masks, None if sc is None else torch.from_numpy(sc).to(dev), B)
-            pt = self.model.perturb_masks(eng, d_masks, B)
-            offsets = eng.encode(d_masks)
-            logits = eng.forward(bgr, depth, offsets)
-        post = self.model.postprocess(eng, logits)
-        logits, post, it = self.model.refine(eng, bgr, depth, logits, post, B, True)
-        ov = self.model.track(eng, d_masks[:B], post, it)
-        return self.model.results(eng, logits, post, d_masks[:B], [len(m) for m in masks_list], it, ov, pt, nm, (bgr, depth))
+                mk[b, :len(m)] = mask_bytes(m, self.perturb is not None or self.nms is not None, binarise=True)
+        model = self.model
+        eng = model.engine_for(H, W, 2 * B if self.tta else B, n)
+        # uploaded straight into B-frame tensors (tta: the first halves of the 2B-frame buffers)
+        bgr, depth, d_masks = model.batch_buffers(B, H, W, n, depth_imgs is not None)
+        bgr[:B].copy_(torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)))
+        if depth is not None:
+            depth[:B].copy_(torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)))
+        d_masks[:B].copy_(torch.from_numpy(mk))
+        rec = model.device_pass(eng, bgr, depth, d_masks, None if sc is None else torch.from_numpy(sc).to(self.device), B, may_stop=True,
+                                own=[len(m) for m in masks_list])
+        return model.results(rec, (bgr, depth))

@@ -115,7 +115,7 @@ def loop(a):
     cls = (torch.arange(B * H * W, device="cuda:0") // 97 % 4).to(torch.uint8).view(B, H, W)
     ids = (torch.arange(B * H * W, device="cuda:0").view(B, H, W) // 41 % (N + 1)).to(torch.int32)
     hd = model.enqueue_batch(bgr, dep, masks)
-    real_ids = eng.relabel_panoptic(hd["post"])
+    real_ids = eng.relabel_panoptic(hd.post)
     model.collect_batch(hd)
     pair = {}
     for name, fn in (("error_mask_hist", lambda: eng.error_mask_hist(cls, masks, 4)),
