@@ -382,6 +382,56 @@ int quber_zoom_paste(quber_ctx* ctx, const int32_t* dev_crop_ids, const float* d
                      int32_t* dev_out_ids, uint8_t* dev_out_masks, int32_t* dev_source, float* dev_out_scores, float* dev_boxes,
                      int32_t* dev_report, void* stream);
 
+/* Validation losses (csrc/losses.hip): the reference's training targets and the five values of its loss dict, per frame, without leaving
+ * the device - PanopticDeepLabTargetGenerator (maskrefiner/data/dataset_mappers/target_generator.py:8-165) and DeepLabBCE / center_losses
+ * / offset_losses / the two error-head losses (maskrefiner/modeling/mask_refiner/model.py:36-72, 672-687, 766-802).  The numpy / float64
+ * torch statement of what the two calls compute is tests/test_losses_cpu.py: loss_targets_np, losses_ref; INTEGRATION.md "Validation
+ * losses" has it in words, with the deviations.
+ *
+ * quber_loss_targets: dev_gt i32 [B][H][W] (0 = none, 1..n_gt; other values count as 0), n_gt <= 254; every id a thing, none crowd
+ *   sigma 1..20; dev_gauss f32 [(6 sigma + 3)^2]: exp(-((i - x0)^2 + (j - y0)^2) / (2 sigma^2)) in float64 with x0 = y0 = 3 sigma + 1,
+ *     rounded to float32 BY THE CALLER (numpy), so the heat values are numpy's bits whatever the device's exp does
+ *   -> dev_targets f32 [B][6][H][W]: centre heat (the maximum over the instances whose window [x - 3 sigma - 1, x + 3 sigma + 2) x
+ *        [y ...) around the peak (rint(cy), rint(cx)) holds the pixel), off_y = cy - y and off_x = cx - x inside an instance (float64
+ *        rounded once, or all float32 with quber_config.encode_legacy_f32), sem_seg 0 / 1, sem_seg_weights (small_weight inside an
+ *        instance of fewer than small_area pixels, else 1), inst_weights 0 / 1 (the reference's center_weights == offset_weights)
+ *   -> dev_points f64 [B][n_gt][2] = (cy, cx) = (sum y, sum x) / count in float64; dev_area i32 [B][n_gt]; zeros for an id without a pixel
+ * quber_losses: dev_logits f32 [B][n_planes][H][W] (quber_forward's planes), dev_targets as above, dev_explicit u8 [B][2][4][H][W]
+ *   (quber_explicit_error_maps; may be NULL when spec names no head)
+ *   -> dev_out f64 [B][QUBER_LOSS_WORDS], per frame (the reference's value for a batch of that one frame):
+ *        [0] loss_sem_seg = foreground_weight * (sum of the k largest BCEWithLogits(x, sem_seg) * sem_seg_weights) / k, k = int(top_k * H * W)
+ *            (all pixels for top_k == 1.0; k == 0 is an error)   [1] loss_center = center_weight * sum((x - t)^2 w) / sum(w)
+ *        [2] loss_offset = offset_weight * sum over BOTH planes(|x - t| w) / sum over ONE plane(w) (model.py:796-798); [1], [2] = 0 for sum(w) = 0
+ *        [3] loss_eee_mask, [4] loss_eee_boundary (0 for an absent head): dice = mean over classes of 1 - (2 sum(t p) + 1e-5) / (sum(t) +
+ *            sum(p) + 1e-5), p = softmax; cross_entropy = mean over pixels of -sum_c t_c log_softmax(x)_c.  Targets: the stack of
+ *            model.py:186-226 for error_type.  Neither is multiplied by EEE_*_LOSS_WEIGHT (the reference does not either)
+ *        [5] the foreground sum, [6] k, [7] the k-th largest value T and [8] the number of values above it (both 0 for top_k == 1.0),
+ *        [9] centre numerator, [10] sum(w), [11] offset numerator, [12] H * W, [13..25] eee_mask: cross-entropy sum, then per class (4
+ *        slots each) sum(t p), sum(t), sum(p); [26..38] eee_boundary alike; [39] 0
+ *   Per-pixel terms are evaluated in float64 from the float32 inputs and added in a fixed order (no floating-point atomics: two runs give
+ *   the same bits); T is exact (a radix select on the bit patterns).
+ * Every output is overwritten by every call; the inputs are not written.  All launches go to `stream`: no host copy, no synchronisation,
+ * no memset node.  The workspace (moments, centres, block partials, histograms, the float64 foreground plane, sized for max_batch
+ * frames) is not part of quber_create: the FIRST call of either entry allocates it and keeps it (quber_workspace_bytes counts it from
+ * then on), so that call is not capturable into a graph; later calls are.  Both work on a context created with with_network = 0. */
+#define QUBER_LOSS_WORDS 40
+typedef struct quber_loss_spec {
+    double top_k;                    /* INS_EMBED_HEAD.FOREGROUND_LOSS_TOP_K, in (0, 1] */
+    double foreground_weight;        /* INS_EMBED_HEAD.FOREGROUND_LOSS_WEIGHT */
+    double center_weight;            /* INS_EMBED_HEAD.CENTER_LOSS_WEIGHT */
+    double offset_weight;            /* INS_EMBED_HEAD.OFFSET_LOSS_WEIGHT */
+    int32_t error_type;              /* INS_EMBED_HEAD.ERROR_TYPE: 0 e3 (4 classes), 1 e2 (2), 2 e33 (3), 3 e32 (2) */
+    int32_t eee_mask_plane;          /* first logit plane of the region-error head, -1 = no such head */
+    int32_t eee_boundary_plane;      /* ... of the boundary-error head */
+    int32_t eee_mask_loss;           /* 0 dice, 1 cross_entropy */
+    int32_t eee_boundary_loss;
+    int32_t reserved;                /* 0 */
+} quber_loss_spec;
+int quber_loss_targets(quber_ctx* ctx, const int32_t* dev_gt, int32_t batch, int32_t n_gt, int32_t sigma, int32_t small_area,
+                       float small_weight, const float* dev_gauss, float* dev_targets, double* dev_points, int32_t* dev_area, void* stream);
+int quber_losses(quber_ctx* ctx, const float* dev_logits, int32_t n_planes, const float* dev_targets, const uint8_t* dev_explicit,
+                 const quber_loss_spec* spec, int32_t batch, double* dev_out, void* stream);
+
 /* evaluation support - all pairwise overlap counts of two label maps in one pass. Replaces the per-pair
  * np.count_nonzero loops of eval/evaluation.py:180-199 (multilabel_metrics).
  *   dev_pred, dev_gt i32 [n_pixels], label values in 0..65535, at most `cap` (<= 1024) distinct values per map

@@ -72,6 +72,8 @@ SIGNATURES = {
     "quber_zoom_rois": (C.c_int, [_P, _P, _I, _I, C.c_float, _P, _P]),
     "quber_zoom_crop": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "quber_zoom_paste": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "quber_loss_targets": (C.c_int, [_P, _P, _I, _I, _I, _I, C.c_float, _P, _P, _P, _P, _P]),
+    "quber_losses": (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "quber_contingency_workspace_bytes": (C.c_int64, [_I]),
     "quber_label_contingency": (C.c_int, [_P, _P, C.c_int64, _I, _P, _P]),
     "quber_boundary_workspace_bytes": (C.c_int64, [_I, _I, _I]),

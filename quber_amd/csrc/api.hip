@@ -122,6 +122,7 @@ void quber_destroy(quber_ctx* c) {
     if (c->perturb_ws) (void)hipFree(c->perturb_ws);
     if (c->masknms_ws) (void)hipFree(c->masknms_ws);
     if (c->zoom_ws) (void)hipFree(c->zoom_ws);
+    if (c->losses_ws) (void)hipFree(c->losses_ws);
     delete c;
 }
 
@@ -607,6 +608,56 @@ int quber_zoom_paste(quber_ctx* c, const int32_t* crop_ids, const float* crop_sc
     return launch_zoom_paste(crop_ids, crop_scores, table, area, depth_crop, slots, rois, batch, n_ids, n_slots, crop, n_crop_ids, min_overlap,
                              max_inst, c->cfg.height, c->cfg.width, out_ids, out_masks, source, out_scores, boxes, report, c->zoom_ws,
                              c->cfg.max_batch, (hipStream_t)stream);
+}
+
+// ---- validation losses: targets, loss record (losses.hip); usable on a context without a network ----
+static int losses_ws(quber_ctx* c) {         // the only allocation of the two entries: made by the first call, for max_batch frames, and kept
+    if (c->losses_ws) return 0;
+    const size_t need = losses_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width);
+    QB_CHECK(hipMalloc(&c->losses_ws, need));
+    c->alloc_bytes += need;
+    return 0;
+}
+
+int quber_loss_targets(quber_ctx* c, const int32_t* gt, int32_t batch, int32_t n_gt, int32_t sigma, int32_t small_area, float small_weight,
+                       const float* gauss, float* targets, double* points, int32_t* area, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_gt < 0 || n_gt > 254) return fail("loss targets: n_gt outside 0..254");
+    if (sigma < 1 || sigma > 20) return fail("loss targets: sigma outside 1..20");
+    if (small_area < 0) return fail("loss targets: negative small_area");
+    if (!(small_weight == small_weight)) return fail("loss targets: small_weight is not a number");
+    if (!gt || !gauss || !targets || (n_gt > 0 && (!points || !area))) return fail("loss targets: null tensor");
+    if (((uintptr_t)gt | (uintptr_t)gauss | (uintptr_t)targets | (uintptr_t)area) & 3) return fail("loss targets: a 32-bit tensor that is not 4-byte aligned");
+    if ((uintptr_t)points & 7) return fail("loss targets: dev_points is not 8-byte aligned");
+    if (losses_ws(c)) return -1;
+    return launch_loss_targets(gt, batch, n_gt, c->cfg.height, c->cfg.width, sigma, small_area, small_weight, c->cfg.encode_legacy_f32 ? 1 : 0, gauss,
+                               targets, points, area, c->losses_ws, c->cfg.max_batch, (hipStream_t)stream);
+}
+
+int quber_losses(quber_ctx* c, const float* logits, int32_t n_planes, const float* targets, const uint8_t* explicit_maps, const quber_loss_spec* sp,
+                 int32_t batch, double* out, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (!sp || !logits || !targets || !out) return fail("losses: null argument");
+    if (((uintptr_t)logits | (uintptr_t)targets) & 3) return fail("losses: a 32-bit tensor that is not 4-byte aligned");
+    if ((uintptr_t)out & 7) return fail("losses: dev_out is not 8-byte aligned");
+    if (!(sp->top_k > 0.0 && sp->top_k <= 1.0)) return fail("losses: top_k outside (0, 1]");
+    if (sp->error_type < 0 || sp->error_type > 3) return fail("losses: error_type must be 0 (e3), 1 (e2), 2 (e33) or 3 (e32)");
+    static const int classes[4] = {4, 2, 3, 2};
+    const int ncls = classes[sp->error_type];
+    if (n_planes < 4) return fail("losses: fewer than the 4 planes fg, centre, off_y, off_x");
+    const int planes[2] = {sp->eee_mask_plane, sp->eee_boundary_plane}, kinds[2] = {sp->eee_mask_loss, sp->eee_boundary_loss};
+    for (int h = 0; h < 2; ++h) {
+        if (planes[h] < 0) continue;
+        if (planes[h] < 4 || planes[h] + ncls > n_planes) return fail("losses: an error head's planes lie outside 4..n_planes");
+        if (kinds[h] != 0 && kinds[h] != 1) return fail("losses: loss type must be 0 (dice) or 1 (cross_entropy)");
+        if (!explicit_maps) return fail("losses: an error head needs dev_explicit");
+    }
+    const long HW = (long)c->cfg.height * c->cfg.width;
+    const long k = sp->top_k == 1.0 ? HW : (long)(sp->top_k * (double)HW);          // int(top_k * numel): model.py:70
+    if (k < 1) return fail("losses: top_k selects no pixel of this frame (the reference would return NaN)");
+    if (losses_ws(c)) return -1;
+    return launch_losses(logits, n_planes, targets, explicit_maps, *sp, ncls, k, batch, c->cfg.height, c->cfg.width, out, c->losses_ws,
+                         c->cfg.max_batch, (hipStream_t)stream);
 }
 
 int64_t quber_contingency_workspace_bytes(int32_t cap) { return (int64_t)contingency_ws_bytes(cap); }

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <string>
 
+struct quber_loss_spec;      // include/quber_hip.h
+
 namespace quber {
 
 // A strided NHWC view: element (b,y,x,c) lives at p[((b*H + y)*W + x)*cs + c]; `p` already points at
@@ -367,6 +369,13 @@ int launch_zoom_paste(const int* crop_ids, const float* crop_scores, const unsig
                       int* out_ids, uint8_t* out_masks, int* source, float* out_scores, float* boxes, int* report, void* ws, int cap_b,
                       hipStream_t st);
 size_t zoom_ws_bytes(int cap_b, int H, int W);
+// validation losses (losses.hip): the training targets of a ground-truth id map and the per-frame loss record, all on `st`; ws:
+// losses_ws_bytes(cap_b >= B, H, W) bytes.  n <= 254, sigma 1..20; ncls: classes of spec.error_type; k: pixels the foreground term averages over
+int launch_loss_targets(const int* labels, int B, int n, int H, int W, int sigma, int small_area, float small_weight, int legacy_f32,
+                        const float* gauss, float* targets, double* points, int* area, void* ws, int cap_b, hipStream_t st);
+int launch_losses(const float* logits, int P, const float* targets, const uint8_t* expl, const ::quber_loss_spec& sp, int ncls, long k,
+                  int B, int H, int W, double* out, void* ws, int cap_b, hipStream_t st);
+size_t losses_ws_bytes(int cap_b, int H, int W);
 int launch_group_pixels(const float* logits, int nch, int B, int H, int W, int cap, const int* centers, const int* ncenters,
                         uint8_t* idmap, unsigned* area, hipStream_t st);
 

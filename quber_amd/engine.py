@@ -606,6 +606,66 @@ class Engine:
                                                  _ptr(o["boxes"]), _ptr(o["report"]), _stream()))
         return o
 
+    # ---- validation losses: training targets, loss record (csrc/losses.hip; INTEGRATION.md "Validation losses") ----
+    def loss_targets(self, gt_labels, n_gt, spec=None, out=None):
+        """gt_labels i32 [B,H,W] (device; 0 = none, 1..n_gt, anything else counts as 0), spec: a losses.Losses (default: the reference's
+        sigma 10, small area 4096, weight 3) -> {"targets": f32 [B,6,H,W] (losses.TARGET_PLANES: centre heat, off_y, off_x, sem_seg,
+        sem_seg_weights, inst_weights), "points": f64 [B,n_gt,2] (cy, cx), "area": i32 [B,n_gt]}; zeros for an id without a pixel.  out:
+        such a dict to write into.  Nothing is copied to the host; the first call of loss_targets / losses on an engine allocates their
+        workspace and cannot be captured into a graph."""
+        from . import losses as ls
+        spec = ls.Losses() if spec is None else spec
+        B, n, dev = gt_labels.shape[0], int(n_gt), self.device
+        assert gt_labels.dtype == torch.int32 and gt_labels.is_contiguous() and gt_labels.shape == (B, self.H, self.W)
+        key = ("loss_gauss", spec.sigma)
+        cache = self.__dict__.setdefault("_loss_gauss", {})
+        if key not in cache:
+            cache[key] = torch.from_numpy(ls.gauss_table(spec.sigma).copy()).to(dev)
+        shapes = {"targets": ((B, 6, self.H, self.W), torch.float32), "points": ((B, n, 2), torch.float64), "area": ((B, n), torch.int32)}
+        o = {} if out is None else out
+        for k, (shape, dt) in shapes.items():
+            if o.get(k) is None:
+                o[k] = torch.empty(shape, dtype=dt, device=dev)
+            assert o[k].dtype == dt and o[k].is_contiguous() and o[k].shape == shape, k
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_loss_targets(self.h, _ptr(gt_labels), B, n, spec.sigma, spec.small_area, float(spec.small_weight),
+                                                   _ptr(cache[key]), _ptr(o["targets"]), _ptr(o["points"] if n else None),
+                                                   _ptr(o["area"] if n else None), _stream()))
+        return o
+
+    def loss_heads(self, spec):
+        """{head name: first logit plane} of the engine's error heads, for `spec`'s error type."""
+        from . import losses as ls
+        heads = {k: first for k, (first, _) in self.error_heads().items()}
+        if heads and ls.ERROR_CLASSES[spec.error_type] != self.qcfg.error_classes:
+            raise ValueError(f"losses: error_type {spec.error_type!r} has {ls.ERROR_CLASSES[spec.error_type]} classes, the engine's error heads "
+                             f"{self.qcfg.error_classes}")
+        return heads
+
+    def losses(self, logits, targets, explicit, spec=None, out=None, heads=None):
+        """logits f32 [B,P,H,W], targets f32 [B,6,H,W] (loss_targets()["targets"]), explicit u8 [B,2,4,H,W] (error_maps()) or None, all on the
+        device; spec: a losses.Losses; heads: {"eee_mask" | "eee_boundary": first logit plane} (default: the engine's error heads when
+        `explicit` is given, none otherwise) -> f64 [B,losses.LOSS_WORDS], one record per frame (include/quber_hip.h: quber_losses;
+        Losses.unpack reads it).  Nothing is copied to the host."""
+        from . import losses as ls
+        spec = ls.Losses() if spec is None else spec
+        B, P = logits.shape[:2]
+        assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.shape[2:] == (self.H, self.W)
+        assert targets.dtype == torch.float32 and targets.is_contiguous() and targets.shape == (B, 6, self.H, self.W)
+        if heads is None:
+            heads = self.loss_heads(spec) if explicit is not None else {}
+        if heads:
+            assert explicit is not None and explicit.dtype == torch.uint8 and explicit.is_contiguous() and explicit.shape == (B, 2, 4, self.H, self.W)
+        spec.top_k_pixels(self.H * self.W)
+        if out is None:
+            out = torch.empty((B, ls.LOSS_WORDS), dtype=torch.float64, device=self.device)
+        assert out.dtype == torch.float64 and out.is_contiguous() and out.shape == (B, ls.LOSS_WORDS)
+        cs = spec.c_spec(heads)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_losses(self.h, _ptr(logits), P, _ptr(targets), _ptr(explicit if heads else None), C.byref(cs), B, _ptr(out),
+                                             _stream()))
+        return out
+
     def extract_masks(self, post, max_inst, out=None):
         B = post["panoptic"].shape[0]
         if out is None:

@@ -103,6 +103,21 @@ def label_map_from_masks(masks, shape, dtype=np.int32):
     return pred
 
 
+def compact_labels(anno):
+    """An annotation's label image -> i32 ids 0 (label 0: none), 1..n in ascending label order: what gt_labels= takes."""
+    values = np.unique(anno)
+    values = values[values != 0]
+    if len(values) > 254:
+        raise ValueError(f"annotation with {len(values)} labels: at most 254")
+    return np.searchsorted(values, anno).astype(np.int32) + (anno != 0).astype(np.int32) if len(values) else np.zeros(anno.shape, np.int32)
+
+
+def mean_losses(frames):
+    """[{key: float}] -> {key: mean over the frames that have the key}."""
+    keys = sorted({k for f in frames for k in f})
+    return {k: float(np.mean([f[k] for f in frames if k in f])) for k in keys}
+
+
 def resize_shortest_edge_shape(oldh, oldw, short_edge_length=800, max_size=1333):
     """[d2] ResizeShortestEdge.get_output_shape, used by the armbench branch (refiner_model.py:228)."""
     scale = short_edge_length * 1.0 / min(oldh, oldw)
@@ -117,14 +132,15 @@ class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
                  lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
                  decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
-                 nms=None, zoom=None):
-        # tta ... zoom: the predictor's options (maskrefiner/predictor.py: module docstring, RefineOptions), for predict()
+                 nms=None, zoom=None, losses=None):
+        # tta ... losses: the predictor's options (maskrefiner/predictor.py: module docstring, RefineOptions), for predict()
         # and predict_stream(batch=k) alike, except: until_converged stops early in predict() only (the stream always runs the fixed
         # count); cleanup "largest" is the UOIS path's largest_connected_component (4-connected), "holes" the SAM refiner's
         # remove_small_regions(mask, 300, "holes"); nms takes its scores from predict(..., mask_scores=) and a fifth element of
-        # predict_stream's items; zoom is predict() only: predict_stream refuses it
+        # predict_stream's items; zoom is predict() only: predict_stream refuses it; losses (a quber_amd.losses.Losses) acts in
+        # predict(..., gt_labels=) and validation_losses() - the stream carries no ground truth
         options = RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
-                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom)
+                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom, losses=losses)
         self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, options=options)
         self.dataset = dataset
         self.lmffnet = None
@@ -182,13 +198,13 @@ class MaskRefiner:
         return {"rgb": np.ascontiguousarray(rgb), "depth": depth, "masks": initial_masks, "zero_depth": zero_depth, "depth_dev": d_dev,
                 "scores": scores}
 
-    def _refine(self, fr):
+    def _refine(self, fr, gt_labels=None):
         """The reference's timed region and what follows it (eval/refiner_model.py:265-297) on a loaded frame."""
         start = time.time()
         if self.dataset == "armbench":
-            output = self.refiner_predictor.predict(fr["rgb"], None, fr["masks"], fr["scores"])[0]
+            output = self.refiner_predictor.predict(fr["rgb"], None, fr["masks"], fr["scores"], gt_labels=gt_labels)[0]
         else:
-            output = self.refiner_predictor.predict(fr["rgb"], fr["depth"], fr["masks"], fr["scores"])[0]
+            output = self.refiner_predictor.predict(fr["rgb"], fr["depth"], fr["masks"], fr["scores"], gt_labels=gt_labels)[0]
         refined = output["instances"].to("cpu").pred_masks.numpy() if "instances" in output else []
         return self._finish(fr, output, refined, start)
 
@@ -217,8 +233,32 @@ class MaskRefiner:
             refined = np.asarray(out)
         return refined, output, elapsed, fg
 
-    def predict(self, rgb_path, depth_path, initial_masks, fg_mask=None, mask_scores=None):
-        return self._refine(self._load(rgb_path, depth_path, initial_masks, mask_scores))
+    def predict(self, rgb_path, depth_path, initial_masks, fg_mask=None, mask_scores=None, gt_labels=None):
+        return self._refine(self._load(rgb_path, depth_path, initial_masks, mask_scores), gt_labels)
+
+    # -- the reference's validation losses (csrc/losses.hip; INTEGRATION.md "Validation losses") --
+    def validation_losses(self, output_or_items, anno_paths=None):
+        """One frame: `output_or_items` is a dict of predict(..., gt_labels=) -> its `losses` (the five floats under the reference's key
+        names; ValueError when the call carried no ground truth or losses= is off).  A dataset: `output_or_items` is an iterable of
+        predict_stream's items and anno_paths one annotation file (or array) per item, read the way evaluate_stream reads it
+        (load_annotation) and renumbered 1..n in ascending label order -> {"frames": [losses per item], "mean": {key: mean over the
+        frames that have it}, "n": frames}.  Per-frame values: the reference's for a batch of that one frame."""
+        if isinstance(output_or_items, dict):
+            if "losses" not in output_or_items:
+                raise ValueError("validation_losses: the output carries no losses (construct with losses= and pass gt_labels= to predict)")
+            return dict(output_or_items["losses"])
+        if self.refiner_predictor.losses is None:
+            raise ValueError("validation_losses: construct the MaskRefiner with losses=")
+        if anno_paths is None:
+            raise ValueError("validation_losses: anno_paths is required with a list of items")
+        frames = []
+        for item, anno_path in zip(output_or_items, anno_paths):
+            anno = load_annotation(anno_path, item[0], self.dataset, self._resize)
+            if anno.ndim != 2:
+                raise ValueError("annotation must be a single-channel label image")
+            out = self.predict(item[0], item[1], item[2], mask_scores=item[4] if len(item) > 4 else None, gt_labels=compact_labels(anno))[1]
+            frames.append(dict(out["losses"]))
+        return {"frames": frames, "mean": mean_losses(frames), "n": len(frames)}
 
     # -- the predicted error maps of one frame: scored against a ground truth, painted over the image (csrc/errhead.hip) --
     def _error_engine(self, h, w, n_masks=64):

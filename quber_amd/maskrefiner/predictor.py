@@ -44,6 +44,13 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
     gains ``zoom_ids`` (i32 [H,W]), ``zoom_rois`` (i32 [k,4]) and ``zoom_report`` (i64 [4]: crops, kept, kept without a final id, count);
     ``sem_seg``, ``panoptic_seg`` and the error heads stay pass 1's.  ``predict`` and ``predict_batch``; ``enqueue_batch`` /
     ``predict_stream`` refuse it.  Default: none, today's keys, nothing launched or allocated.
+  * ``losses=Losses(...)`` (``Losses.from_cfg(cfg)`` reads the reference's keys) together with a call's ``gt_labels=`` (``predict``,
+    ``predict_batch``, ``enqueue_batch``: the ground-truth label map(s), integer, 0 = none, 1..n <= 254): the reference's training targets
+    and the five values of its loss dict for every frame, on the device (csrc/losses.hip; INTEGRATION.md "Validation losses") - targets
+    from the ground truth, explicit error maps from the initial masks the network actually saw (after ``nms`` / ``perturb``), losses of
+    the pass's final logits (the merged ones under ``tta``).  Every dict gains ``losses`` ({loss_sem_seg, loss_center, loss_offset,
+    loss_eee_*: float}, per frame), ``loss_terms`` (the raw sums) and, with ``keep_targets=True``, ``loss_targets``.  Refused together
+    with ``iterations > 1`` or ``zoom=``.  Default, or a call without ``gt_labels``: nothing launched, today's keys.
 There is no CPU fallback: construction fails if the HIP library or a GPU is missing.
 """
 import os
@@ -58,6 +65,7 @@ from ..cleanup import Cleanup
 from ..masknms import MaskNMS, check_scores
 from ..perturb import Perturb
 from ..structures import Boxes, Instances
+from ..losses import Losses
 from ..zoom import ZoomIn
 
 LABEL_DIVISOR = 1000  # maskrefiner/data/datasets/register_uoais_sim_panoptic.py:177-186
@@ -113,17 +121,23 @@ class RefineOptions:
     perturb: Perturb = None           # the initial masks degraded on the device before anything reads them
     nms: MaskNMS = None               # scored, overlapping initial masks made disjoint on the device before anything else reads them
     zoom: ZoomIn = None               # a second pass on a padded, resized crop of every instance, pasted back on the device
+    losses: Losses = None             # with a call's gt_labels=: the reference's training targets and loss dict of every frame, on the device
 
     @classmethod
     def parse(cls, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
-              nms=None, zoom=None):
+              nms=None, zoom=None, losses=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
+        losses = Losses.parse(losses)
+        if losses is not None and int(iterations) > 1:
+            raise ValueError("losses: not with iterations > 1 (the last pass's input exists only as a label map: left out)")
+        if losses is not None and zoom is not None:
+            raise ValueError("losses: not with zoom= (the crop pass has no ground truth: left out)")
         if perturb is not None and not isinstance(perturb, Perturb):
             raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
         zoom, nms = ZoomIn.parse(zoom), MaskNMS.parse(nms)
         return cls(bool(tta), bool(decode_errors), int(iterations), bool(until_converged), bool(track_initial), Cleanup.parse(cleanup),
-                   perturb, nms, zoom)
+                   perturb, nms, zoom, losses)
 
     def for_crops(self):
         """The crop pass of zoom: the same tta, iterations and cleanup; nothing that concerns the caller's initial masks."""
@@ -149,6 +163,7 @@ class PassResult:
     err: dict = None
     pt: tuple = None
     nm: dict = None
+    ls: dict = None
     masks: object = None
     slots: int = 0
     count: object = None
@@ -215,11 +230,12 @@ class RefinerModel:
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
     def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False, iterations=1, until_converged=False,
-                 track_initial=False, cleanup=None, perturb=None, nms=None, zoom=None, options=None):
-        # options: a RefineOptions in place of the nine keywords.  Its fields become plain attributes, which is what the code below
+                 track_initial=False, cleanup=None, perturb=None, nms=None, zoom=None, losses=None, options=None):
+        # options: a RefineOptions in place of the ten keywords.  Its fields become plain attributes, which is what the code below
         # reads (a test and a tool switch model.decode_errors between calls)
         self.options = options or RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
-                                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom)
+                                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom,
+                                                      losses=losses)
         vars(self).update(vars(self.options))
         self._zoom_model = None   # the crop pass: a RefinerModel on the same cfg and weights, built by the first zoomed call
         self.debug_zoom = None    # tests: a list that receives, per zoomed call, the inputs and outputs of every stage
@@ -399,7 +415,41 @@ class RefinerModel:
         return eng.overlap_masks(d_masks, ids, eng.cap, out=out)
 
     # -- the one sequence predict_one, enqueue_batch and predict_batch run; they differ in who owns the buffers and where the host reads --
-    def device_pass(self, eng, bgr, depth, masks, scores, B, *, may_stop, bufs=None, own=None, slots=None):
+    # -- validation losses (INTEGRATION.md "Validation losses") --
+    def upload_gt(self, gt_labels, B, H, W):
+        """A call's gt_labels= -> None (losses off, or no ground truth with this call) or (labels i32 [B,H,W], the ids' masks u8
+        [B,max(n_gt, 1),H,W], n_gt) on the device.  gt_labels: an integer label map [H,W] / [B,H,W] or a list of B maps, at the network's
+        frame size, 0 = none, 1..n (n <= 254)."""
+        if self.losses is None or gt_labels is None:
+            return None
+        lab = np.stack([np.asarray(g) for g in gt_labels]) if isinstance(gt_labels, (list, tuple)) else np.asarray(gt_labels)
+        if lab.ndim == 2:
+            lab = lab[None]
+        if lab.shape != (B, H, W) or not np.issubdtype(lab.dtype, np.integer):
+            raise ValueError(f"gt_labels: expected {B} integer label map(s) of {(H, W)}, got {lab.dtype} {lab.shape}")
+        n_gt = int(lab.max()) if lab.size else 0
+        if int(lab.min()) < 0 or n_gt > 254:
+            raise ValueError("gt_labels: ids outside 0..254")
+        lab = np.ascontiguousarray(lab, dtype=np.int32)
+        gt_masks = (lab[:, None] == np.arange(1, max(n_gt, 1) + 1, dtype=np.int32)[None, :, None, None]).view(np.uint8)
+        return torch.from_numpy(lab).to(self.device), torch.from_numpy(gt_masks).to(self.device), n_gt
+
+    def loss_stage(self, eng, logits, d_masks, gt, B):
+        """losses: enqueue the targets of the ground-truth ids, the explicit error maps of the initial masks AS THE NETWORK SAW THEM (after
+        nms / perturb) against the ground truth's masks, and the loss record of `logits` (the merged ones under tta).  gt: upload_gt()'s
+        triple.  -> {"rec": f64 [B,LOSS_WORDS], "targets": Engine.loss_targets()'s dict, "heads", "explicit"} or None."""
+        if self.losses is None or gt is None:
+            return None
+        labels, gt_masks, n_gt = gt
+        tg = eng.loss_targets(labels, n_gt, self.losses)
+        heads = eng.loss_heads(self.losses)
+        explicit = None
+        if heads:
+            init = d_masks if d_masks.shape[1] else torch.zeros((B, 1, eng.H, eng.W), dtype=torch.uint8, device=self.device)
+            explicit = eng.error_maps(init, gt_masks)
+        return {"rec": eng.losses(logits, tg["targets"], explicit, self.losses, heads=heads), "targets": tg, "heads": heads, "explicit": explicit}
+
+    def device_pass(self, eng, bgr, depth, masks, scores, B, *, may_stop, bufs=None, own=None, slots=None, gt=None):
         """Enqueues nms -> perturb -> encode (tta: mirror, encode) -> forward -> postprocess -> refine -> track -> decode for B frames on
         the current stream -> PassResult.  bgr / depth (or None) u8 [f*B,H,W,3] and masks u8 [f*B,N,H,W] on the device, f = 2 under tta
         with the frames in the first halves; scores f32 [B,N] (required with nms).  Nothing is read back unless may_stop and
@@ -423,6 +473,7 @@ class RefinerModel:
             rec.slots = min(max(1, slots), eng.cap)
             rec.masks = eng.extract_masks(post, rec.slots)
         rec.err = self.decode(eng, logits, d_masks if it is None else None)    # (a pass >= 2 has no initial masks to attribute to)
+        rec.ls = self.loss_stage(eng, logits, d_masks, gt, B)
         return rec
 
     # -- zoom-in refinement (INTEGRATION.md "Zoom-in refinement") --
@@ -519,6 +570,10 @@ class RefinerModel:
             r["refine_passes"], r["refine_converged_at"] = it["passes"], int(conv)
         if ov is not None:
             r["initial_overlap"], first, iou = match_initial(ov[0][b], ov[1][b], n, k)
+        if rec.ls is not None:                       # "host": the loss records f64 [B,LOSS_WORDS], read back by the caller
+            r["losses"], r["loss_terms"] = self.losses.unpack(rec.ls["host"][b], rec.ls["heads"])
+            if self.losses.keep_targets:
+                r["loss_targets"] = {key: t[b] for key, t in rec.ls["targets"].items()}
         if k > 0:
             labels = post["labels"][b, :k]
             inst = Instances((eng.H, eng.W))
@@ -543,6 +598,8 @@ class RefinerModel:
             rec.own = [int(c) for c in rec.nm["report"][:, 0].cpu().numpy()]
         count = post["count"].cpu().numpy()
         conv = rec.it["conv"].cpu().numpy() if rec.it is not None else np.zeros((B,), np.int32)
+        if rec.ls is not None:
+            rec.ls["host"] = rec.ls["rec"].cpu().numpy()
         kmax = int(count.max()) if B else 0
         masks = eng.extract_masks(post, kmax) if kmax > 0 else None
         outs = [self.frame_dict(rec, b, int(count[b]), masks[b, :int(count[b])].bool() if count[b] > 0 else None, conv[b]) for b in range(B)]
@@ -556,7 +613,7 @@ class RefinerModel:
             outs = self.zoom_pass(rec, images[0], images[1], count, outs)
         return outs
 
-    def predict_one(self, bgr, depth, masks):
+    def predict_one(self, bgr, depth, masks, gt_labels=None):
         """The reference's call path (one frame per call, predictor.py:287-359) with nothing allocated per call but the
         outputs: the inputs go through one pinned block in a few pipelined H2D copies; the instance count comes back through
         a pinned word and exactly `count` masks are extracted."""
@@ -565,7 +622,8 @@ class RefinerModel:
         H, W = bgr.shape[:2]
         n = int(masks.shape[0])
         f = 2 if self.tta else 1                     # frames on the device: the frame [and its mirror]
-        eng = self.engine_for(H, W, f, n)
+        gt = self.upload_gt(gt_labels, 1, H, W)
+        eng = self.engine_for(H, W, f, max(n, gt[2]) if gt is not None else n)
         stg = self.staging_for(eng, n)
         hw = H * W
         two = depth is not None
@@ -594,12 +652,14 @@ class RefinerModel:
         d_bgr = stg.dev_in[:3 * f * hw].view(f, H, W, 3)
         d_dep = stg.dev_in[od:od + 3 * f * hw].view(f, H, W, 3) if two else None
         d_masks = stg.dev_in[om:om + f * n * hw].view(f, n, H, W)
-        rec = self.device_pass(eng, d_bgr, d_dep, d_masks, None, 1, may_stop=True, bufs=stg)
+        rec = self.device_pass(eng, d_bgr, d_dep, d_masks, None, 1, may_stop=True, bufs=stg, gt=gt)
         post = rec.post
         stg.pin_count[:1].copy_(post["count"], non_blocking=True)
         if rec.it is not None:
             stg.pin_count[1:].copy_(rec.it["conv"], non_blocking=True)
         torch.cuda.current_stream().synchronize()
+        if rec.ls is not None:
+            rec.ls["host"] = rec.ls["rec"].cpu().numpy()
         k = int(stg.pin_count[0])
         # the dict owns clones: the staging's tables are the next call's
         rec.post = {key: post[key].clone() for key in ("panoptic", "labels", "scores", "boxes", "cc_report") if key in post}
@@ -611,13 +671,14 @@ class RefinerModel:
         return self.frame_dict(rec, 0, k, masks_b, int(stg.pin_count[1]) if rec.it is not None else 0)
 
     # -- batched form on device-resident frames, split into "enqueue" and "collect" so that a caller can keep one batch in flight --
-    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None, d_scores=None):
+    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None, d_scores=None, gt_labels=None):
         """d_bgr / d_depth: u8 [B,H,W,3] (depth None for single-stream configs), d_masks: u8 [B,N,H,W] on the device.  Enqueues a1 ...
         a11 and the extraction of the first `slots` instance masks of every frame on the current stream WITHOUT synchronising;
         returns a handle for collect_batch().  halves=True (test-time augmentation only): the tensors are 2B-frame buffers
         (tta_alloc) whose first halves hold the B frames.  n_masks: how many of the N masks are each frame's own (the rows of
         `initial_overlap` under track_initial; default: all N).  d_scores (required with nms=): f32 [B,N] on the device, the masks'
-        scores, NaN for a mask that is not there; each frame's own masks are then the NMS's `count` and n_masks is not used."""
+        scores, NaN for a mask that is not there; each frame's own masks are then the NMS's `count` and n_masks is not used.  gt_labels
+        (with losses=): the B frames' ground-truth label maps on the host (upload_gt); every dict then carries `losses`."""
         if self.nms is not None and d_scores is None:
             raise ValueError("nms: d_scores is required when nms= is set")
         if self.zoom is not None:
@@ -627,7 +688,8 @@ class RefinerModel:
         B, H, W = d_bgr.shape[:3]
         B = B // 2 if halves else B
         f = 2 if self.tta else 1                     # test-time augmentation: the engine runs the B frames and their mirrors
-        eng = self.engine_for(H, W, f * max(B, capacity), d_masks.shape[1])      # (`capacity`: the caller's batch size - a short last batch must not rebuild)
+        gt = self.upload_gt(gt_labels, B, H, W)
+        eng = self.engine_for(H, W, f * max(B, capacity), max(d_masks.shape[1], gt[2]) if gt is not None else d_masks.shape[1])      # (`capacity`: the caller's batch size - a short last batch must not rebuild)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         if self.tta and not halves:                       # B-frame tensors: copied into the first halves of 2B-frame buffers
@@ -638,7 +700,7 @@ class RefinerModel:
                     buf[:B].copy_(t)
         # (nms and perturb write the caller's masks, unless they have just been copied); may_stop=False: always the fixed count, nothing
         # is read back here
-        rec = self.device_pass(eng, d_bgr, d_depth, d_masks, d_scores, B, may_stop=False, own=n_masks, slots=slots)
+        rec = self.device_pass(eng, d_bgr, d_depth, d_masks, d_scores, B, may_stop=False, own=n_masks, slots=slots, gt=gt)
         pinned = torch.zeros((2, B), dtype=torch.int32).pin_memory()                   # instance counts, refine_converged_at
         rec.count, rec.conv, rec.e0, rec.e1 = pinned[0], pinned[1], e0, e1
         rec.count.copy_(rec.post["count"], non_blocking=True)
@@ -648,6 +710,10 @@ class RefinerModel:
             rep = torch.zeros((B, 4), dtype=torch.int32).pin_memory()
             rep.copy_(rec.nm["report"], non_blocking=True)
             rec.own = rep[:, 0]
+        if rec.ls is not None:                            # the loss records: valid once e1 has passed
+            pin = torch.zeros(tuple(rec.ls["rec"].shape), dtype=torch.float64).pin_memory()
+            pin.copy_(rec.ls["rec"], non_blocking=True)
+            rec.ls["host"] = pin.numpy()
         e1.record()
         eng._in_flight = getattr(eng, "_in_flight", 0) + 1
         return rec
@@ -739,10 +805,11 @@ class RefinerModel:
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
                  seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False,
-                 cleanup=None, perturb=None, nms=None, zoom=None, options=None):
+                 cleanup=None, perturb=None, nms=None, zoom=None, losses=None, options=None):
         # the options (module docstring), checked before anything is loaded; options: a RefineOptions in their place
         self.options = options or RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
-                                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom)
+                                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom,
+                                                      losses=losses)
         vars(self).update(vars(self.options))
         if config_file is None:
             self.cfg = qconfig.canonical_cfg()
@@ -773,25 +840,27 @@ class MaskRefinerPredictor:
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
     # -- reference signature (predictor.py:287) --
-    def predict(self, rgb_img, depth_img=None, perturbed_masks=None, mask_scores=None):
+    def predict(self, rgb_img, depth_img=None, perturbed_masks=None, mask_scores=None, gt_labels=None):
+        # gt_labels (with losses=): the frame's ground-truth label map, integer [H,W], 0 = none, 1..n; the dict then carries `losses`
         masks = np.zeros((0,) + rgb_img.shape[:2], np.uint8) if perturbed_masks is None else np.asarray(perturbed_masks)
+        gts = None if gt_labels is None else [gt_labels]
         if self.nms is not None:                          # the general path: how many masks there are is known on the device only
-            return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks], [mask_scores])
+            return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks], [mask_scores], gt_labels=gts)
         if self.zoom is not None:                         # the general path: it keeps the frame on the device for the crops
             return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks])
         if not self.fast_path or masks.dtype not in (np.uint8, np.bool_) or masks.ndim != 3:
-            return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks])
+            return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks], gt_labels=gts)
         if self.depth_on and depth_img is None:
             raise ValueError("this config has INPUT.DEPTH_ON: a depth image is required")
         if not self.rgb_on:                               # depth-only: the image IS the depth map (predictor.py:296-298)
             rgb_img, depth_img = depth_img, None
         elif not self.depth_on:
             depth_img = None
-        return [self.model.predict_one(rgb_img, depth_img, mask_bytes(masks, self.perturb is not None))]
+        return [self.model.predict_one(rgb_img, depth_img, mask_bytes(masks, self.perturb is not None), gt_labels)]
 
-    def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None):
+    def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None, gt_labels=None):
         """rgb_imgs/depth_imgs: u8 [B,H,W,3] arrays; masks_list: B arrays u8/bool [N_b,H,W]; scores_list (required with nms=): B arrays
-        [N_b] of finite scores.  -> list of B dicts."""
+        [N_b] of finite scores; gt_labels (with losses=): the B ground-truth label maps, integer [B,H,W] or a list.  -> list of B dicts."""
         B, H, W = rgb_imgs.shape[:3]
         sc = None
         if self.nms is not None:                          # checked before anything is uploaded or launched
@@ -812,7 +881,8 @@ class MaskRefinerPredictor:
             if len(m):
                 mk[b, :len(m)] = mask_bytes(m, self.perturb is not None or self.nms is not None, binarise=True)
         model = self.model
-        eng = model.engine_for(H, W, 2 * B if self.tta else B, n)
+        gt = model.upload_gt(gt_labels, B, H, W)
+        eng = model.engine_for(H, W, 2 * B if self.tta else B, max(n, gt[2]) if gt is not None else n)
         # uploaded straight into B-frame tensors (tta: the first halves of the 2B-frame buffers)
         bgr, depth, d_masks = model.batch_buffers(B, H, W, n, depth_imgs is not None)
         bgr[:B].copy_(torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)))
@@ -820,5 +890,5 @@ class MaskRefinerPredictor:
             depth[:B].copy_(torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)))
         d_masks[:B].copy_(torch.from_numpy(mk))
         rec = model.device_pass(eng, bgr, depth, d_masks, None if sc is None else torch.from_numpy(sc).to(self.device), B, may_stop=True,
-                                own=[len(m) for m in masks_list])
+                                own=[len(m) for m in masks_list], gt=gt)
         return model.results(rec, (bgr, depth))
