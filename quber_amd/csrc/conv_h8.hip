@@ -1541,6 +1541,10 @@ int launch_conv_h8p(ConvP p, int G, hipStream_t st, bool dry = false) {
     if (!vec8) return 1;
     const int ntx = (p.W + P8_TX - 1) / P8_TX, nty = (p.H + P8_TY - 1) / P8_TY;
     const bool wide = p.Cout > 128;       // conv_h8w_kernel: channel tiles of 256
+    // conv_h8w_kernel rotates TWO scale / shift images and requests the next tile's vectors inside its last channel block, behind that tile's barriers.
+    // With one channel block (Cin = 64 halfs) that request would stand at the top of the tile, before any barrier, while late waves of the previous
+    // tile's epilogue still read the image it lands in (profiles/r20_h8_affine_race.md): such a launch goes to conv_h8_kernel (9 K-tiles, three images)
+    if (wide && p.Kpad / (9 * 32) < 2) return 1;
     const int ntn = wide ? (p.Cout + 255) / 256 : 1;
     const long tiles = (long)G * p.B * nty * ntx * ntn;
     const bool norm = p.n_stats != nullptr;     // (a launch that normalises its input has no other kernel to go to: it runs however few its tiles)

@@ -65,7 +65,7 @@ CASES = [
     # the patch kernel (3x3, stride 1, pad 1, <= 128 output channels): 8 x 32-pixel tiles, the 10 x 34 patch of a 64-channel block fetched once
     (3, 37, 45, 128, 128, 3, 1, 1, 1, 1, True, True, True, 0, 1),        # ragged tiles in both directions, residual, two channel blocks
     (2, 20, 24, 320, 128, 3, 1, 1, 1, 1, True, False, False, 32, 1),     # images narrower than a tile, five channel blocks, norm sums in the epilogue
-    (1, 64, 96, 64, 128, 3, 1, 1, 1, 1, True, False, True, 0, 1),        # one channel block per tile: every patch is the NEXT tile's
+    (1, 64, 96, 64, 128, 3, 1, 1, 1, 1, True, False, True, 0, 1),        # one channel block per tile: a patch is requested a whole tile ahead (24 tiles on 24 blocks: no block has a next tile - tests/test_gpu_tile_walks.py walks)
     (2, 33, 70, 128, 64, 3, 1, 1, 1, 1, True, True, False, 16, 1),       # 64 output channels, residual + norm sums
     (2, 40, 52, 128, 32, 3, 1, 1, 1, 1, True, False, True, 0, 1),        # 32 output channels on half-empty 64-channel tiles (the heads' 128 > 32)
     # ... and its 256-channel form (conv_h8w_kernel): four phases, channel tiles of 256; key 38 = 2: the same layers on the DMA-gather kernel
@@ -73,6 +73,9 @@ CASES = [
     (1, 36, 44, 64, 320, 3, 1, 1, 1, 1, True, False, False, 0, 1),       # ragged channel tile
     (3, 37, 45, 128, 512, 3, 1, 1, 1, 1, True, True, True, 0, 1),        # two channel tiles, residual
     (2, 33, 70, 256, 256, 3, 1, 1, 1, 1, True, False, False, 32, 1),     # norm sums in the epilogue
+    # (conv_h8w_kernel takes two channel blocks and more: the 64 > 256 and 64 > 320 cases above run on conv_h8_kernel - launch_conv_h8p; their twins)
+    (2, 40, 52, 128, 256, 3, 1, 1, 1, 1, True, False, True, 0, 1),       # ragged last pixel tile, padded borders
+    (1, 36, 44, 128, 320, 3, 1, 1, 1, 1, True, False, False, 0, 1),      # ragged channel tile
 ]
 
 
