@@ -687,6 +687,47 @@ int quber_op_conv3x3_winograd(const float* dev_x, int32_t batch, int32_t h, int3
                               const float* dev_shift,
                               int32_t relu, float* dev_u_scratch, float* dev_ws, int64_t ws_floats, float* dev_y,
                               void* stream);
+/* The three convolution ops above in the forms the plan launches them - test hooks: arguments -> launch parameters -> launcher.  A view is (pointer
+ * to its first channel, cs = elements between two pixels, gs = elements between two launch groups) over batch x h x w x channels of fp32; arithmetic
+ * per key 12, split-K workspace per key 2, as the dense ops.  No op allocates (but the bf16x3 weight planes) or synchronises.
+ *   quber_op_conv2d_view            G groups: weights OIHW [G][cout][cin][k][k] (packed per group into dev_packed_scratch [G][cout][Kpad]), scale / shift
+ *                                   [G][cout] or null, residual view or null; dev_gn_sums (or null): f64 [G][batch][gn_groups][2], the sums and sums of
+ *                                   squares of the stored outputs are ADDED to it
+ *   quber_op_conv3x3_winograd_view  the same through Winograd F(m x m, 3x3); x_gs may be 0 (the groups share one input); dev_n_stats (or null): the
+ *                                   input is normalised on load, relu?((x - mean) * rstd * gamma + beta), from the sums f64 [G][batch][n_groups][2] of
+ *                                   quber_op_gn_stats, gamma / beta of group g at g * n_param_gs; dev_y may be dev_x where the three-kernel pipeline runs;
+ *                                   dev_u_scratch: G * P * cout * cin floats; the single-kernel form as in the dense op, with a dev_ws that also holds
+ *                                   G * 36 * cout * cin floats
+ *   quber_op_conv1x1_dual_view      G groups of the dual 1x1 GEMM: dense tensors at the group strides given, w [G][cout][mid + cin] at w_gs, shift / ones at ss_gs
+ * quber_debug_*_route: host only - nothing is launched, no device queried.  The launcher itself walks its decisions for the launch the op would make
+ * of these arguments on the current process keys and reports them: out[12] = kernel, sums, rows and channels of a tile, K partitions, log2 pieces of a
+ * split tail, tiles, blocks, K slices, shortest share (the arguments of quber_debug_persistent_segments), packed axis, shared input transform.
+ *   kernel: 1 one tile per block, 2 ... with the split-K reduce, 3 persistent, 4 Winograd pipeline, 5 single Winograd kernel, 6 conv_x8
+ *   sums:   0 none requested; the kernel's number: gathered by it; 7: a separate pass over the output
+ *   x_off / y_off / res_off: element offsets of the views in 16-byte-aligned buffers (res_off < 0: no residual); workspace: as with key 2 set; cus:
+ *   compute units to assume; Winograd: tiles = per image, rows of a tile = tiles per block of the kernel that gathers the sums, K partitions = passes */
+int quber_op_conv2d_view(const float* dev_x, int32_t x_cs, int64_t x_gs, const float* dev_w_oihw, const float* dev_scale, const float* dev_shift,
+                         const float* dev_residual, int32_t res_cs, int64_t res_gs, float* dev_y, int32_t y_cs, int64_t y_gs, int32_t groups_of_launch,
+                         int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t pad, int32_t dil,
+                         int32_t relu, double* dev_gn_sums, int32_t gn_groups, float* dev_packed_scratch, void* stream);
+int quber_debug_conv_route(int32_t x_off, int32_t x_cs, int64_t x_gs, int32_t affine, int32_t res_off, int32_t res_cs, int64_t res_gs, int32_t y_off,
+                           int32_t y_cs, int64_t y_gs, int32_t groups_of_launch, int32_t batch, int32_t h, int32_t w, int32_t cin, int32_t cout,
+                           int32_t ksize, int32_t stride, int32_t pad, int32_t dil, int32_t gn_groups, int32_t workspace, int32_t cus, int32_t* out12);
+int quber_op_conv3x3_winograd_view(const float* dev_x, int32_t x_cs, int64_t x_gs, const float* dev_w_oihw, const float* dev_scale,
+                                   const float* dev_shift, float* dev_y, int32_t y_cs, int64_t y_gs, int32_t groups_of_launch, int32_t batch, int32_t h,
+                                   int32_t w, int32_t cin, int32_t cout, int32_t dil, int32_t m, int32_t relu, double* dev_gn_sums, int32_t gn_groups,
+                                   const double* dev_n_stats, const float* dev_n_gamma, const float* dev_n_beta, int32_t n_param_gs, int32_t n_groups,
+                                   int32_t n_relu, float n_eps, float* dev_u_scratch, float* dev_ws, int64_t ws_floats, void* stream);
+int quber_debug_winograd_route(int32_t x_cs, int64_t x_gs, int32_t y_cs, int64_t y_gs, int32_t in_place, int32_t groups_of_launch, int32_t batch,
+                               int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t dil, int32_t m, int32_t gn_groups, int32_t norm_groups,
+                               int64_t ws_floats, int32_t* out12);
+int quber_op_conv1x1_dual_view(const float* dev_y, int64_t y_gs, const float* dev_x, int64_t x_gs, const float* dev_w, int64_t w_gs,
+                               const float* dev_shift, const float* dev_ones, int32_t ss_gs, float* dev_out, int64_t out_gs, int32_t groups_of_launch,
+                               int32_t batch, int32_t oh, int32_t ow, int32_t mid, int32_t h2, int32_t w2, int32_t cin, int32_t stride, int32_t cout,
+                               int32_t relu, void* stream);
+int quber_debug_dual_route(int64_t y_gs, int64_t x_gs, int64_t w_gs, int32_t ss_gs, int64_t out_gs, int32_t groups_of_launch, int32_t batch, int32_t oh,
+                           int32_t ow, int32_t mid, int32_t h2, int32_t w2, int32_t cin, int32_t stride, int32_t cout, int32_t workspace, int32_t cus,
+                           int32_t* out12);
 int quber_op_groupnorm(const float* dev_x, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t groups,
                        const float* dev_gamma, const float* dev_beta, float eps, int32_t relu,
                        double* dev_stats_scratch, float* dev_y, void* stream);

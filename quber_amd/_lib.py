@@ -105,6 +105,14 @@ SIGNATURES = {
     "quber_op_conv1x1_dual": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
     "quber_op_conv2d": (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P]),
     "quber_op_conv3x3_winograd": (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P, _P, C.c_int64, _P, _P]),
+    # the convolution launchers on explicit views, groups and GroupNorm sums, and the host view of their routing (tests/test_gpu_conv_forms.py)
+    "quber_op_conv2d_view": (C.c_int, [_P, _I, C.c_int64, _P, _P, _P, _P, _I, C.c_int64, _P, _I, C.c_int64] + [_I] * 11 + [_P, _I, _P, _P]),
+    "quber_debug_conv_route": (C.c_int, [_I, _I, C.c_int64, _I, _I, _I, C.c_int64, _I, _I, C.c_int64] + [_I] * 13 + [_P]),
+    "quber_op_conv3x3_winograd_view": (C.c_int, [_P, _I, C.c_int64, _P, _P, _P, _P, _I, C.c_int64] + [_I] * 9 + [_P, _I, _P, _P, _P, _I, _I, _I, C.c_float,
+                                                 _P, _P, C.c_int64, _P]),
+    "quber_debug_winograd_route": (C.c_int, [_I, C.c_int64, _I, C.c_int64] + [_I] * 11 + [C.c_int64, _P]),
+    "quber_op_conv1x1_dual_view": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, _I, _P, C.c_int64] + [_I] * 11 + [_P]),
+    "quber_debug_dual_route": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _I, C.c_int64] + [_I] * 12 + [_P]),
     "quber_op_groupnorm": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, C.c_float, _I, _P, _P, _P]),
     "quber_op_bilinear": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "quber_op_maxpool3x3s2": (C.c_int, [_P, _I, _I, _I, _I, _P, _P]),

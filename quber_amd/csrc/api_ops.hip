@@ -60,6 +60,17 @@ static View mkview(const float* p, int B, int h, int w, int c) {
     return v;
 }
 
+// the single-kernel form where it applies and the workspace also holds its filter order (36 * cout * cin floats per group) in front of the
+// launch's own workspace: q.uf / q.ws / q.ws_floats set accordingly (q.ws, q.ws_floats: the whole workspace on entry)
+static bool op_wino_single(WinoP& q, int B, int G) {
+    const size_t order = (size_t)G * 36 * q.out.C * q.in.C;
+    if (q.m != 4 || !tune().wino_fused || q.out.C % 32 || q.ws_floats < order) return false;
+    q.uf = q.ws;
+    if (!winograd_fused_ok(q, B, G)) { q.uf = nullptr; return false; }
+    q.ws += order; q.ws_floats -= order;
+    return true;
+}
+
 extern "C" {
 
 __global__ void pack_oihw_kernel(const float* __restrict__ w, int O, int I, int k, int Kpad, int kmode, float* __restrict__ out) {
@@ -171,21 +182,187 @@ int quber_op_conv3x3_winograd(const float* x, int32_t B, int32_t h, int32_t w, i
     q.dtype = g_op_bf16;
     q.pack = tune().wino_pack;           // key 51, read per call
     q.ws = ws; q.ws_floats = (size_t)ws_floats;
-    // the single-kernel form where it applies and the workspace also holds its filter order (36 * cout * cin floats)
-    if (m == 4 && tune().wino_fused && cout % 32 == 0 && (size_t)ws_floats >= (size_t)36 * cout * cin) {
-        q.uf = ws;
-        if (winograd_fused_ok(q, B, 1)) {
-            rc = winograd_fused_prepare();
-            if (rc) return rc;
-            rc = g_op_wino_reuse ? 0 : launch_winograd_fused_pack(u, cout, cin, ws, st);
-            if (rc) return rc;
-            q.ws = ws + (size_t)36 * cout * cin; q.ws_floats = (size_t)ws_floats - (size_t)36 * cout * cin;
-        } else {
-            q.uf = nullptr;
-        }
+    if (op_wino_single(q, B, 1)) {
+        rc = winograd_fused_prepare();
+        if (rc) return rc;
+        rc = g_op_wino_reuse ? 0 : launch_winograd_fused_pack(u, cout, cin, ws, st);
+        if (rc) return rc;
     }
     q.splitk_ws = g_op_ws; q.splitk_floats = g_op_ws ? g_op_ws_floats : 0;
     return launch_conv_winograd(q, B, 1, st);
+}
+
+// ---- the convolution launchers on explicit views, groups and GroupNorm sums (tests): arguments -> ConvP / WinoP -> launcher, nothing else ----
+// the ConvP of quber_op_conv2d_view (and of quber_debug_conv_route, whose pointers are stand-ins that nothing dereferences)
+static void conv_view_p(ConvP& p, const float* x, int x_cs, long x_gs, const float* packed, const float* scale, const float* shift, const float* res, int res_cs,
+                        long res_gs, float* y, int y_cs, long y_gs, int B, int h, int w, int cin, int cout, int k, int stride, int pad, int dil, int relu,
+                        double* gn_sums, int gn_groups, float* ws) {
+    const int Kpad = (k * k * cin + 31) / 32 * 32;
+    const bool skip_rows = g_op_skip_rows && k == 3 && stride == 1 && dil > 1 && cin % 32 == 0;
+    p.in = x; p.w = packed; p.scale = scale; p.shift = shift; p.res = res; p.out = y;
+    conv_geometry(p, B, h, w, cin, cout, k, stride, pad, dil);
+    p.in_cs = x_cs; p.out_cs = y_cs; p.res_cs = res_cs; p.Kpad = Kpad; p.relu = relu;
+    p.in_gs = x_gs; p.out_gs = y_gs; p.res_gs = res ? res_gs : 0; p.w_gs = (long)cout * Kpad; p.ss_gs = cout;
+    p.kmode = (k > 1 && cin % 32 == 0 && !skip_rows) ? 1 : 0; p.skip_rows = skip_rows;
+    p.bf16 = g_op_bf16;
+    p.ws = ws; p.ws_floats = ws ? g_op_ws_floats : 0;
+    if (gn_sums) { p.gn_sum = gn_sums; p.gn_groups = gn_groups; p.gn_cpg = cout / gn_groups; }
+}
+
+int quber_op_conv2d_view(const float* x, int32_t x_cs, int64_t x_gs, const float* w_oihw, const float* scale, const float* shift, const float* residual,
+                         int32_t res_cs, int64_t res_gs, float* y, int32_t y_cs, int64_t y_gs, int32_t G, int32_t B, int32_t h, int32_t w, int32_t cin,
+                         int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t dil, int32_t relu, double* gn_sums, int32_t gn_groups, float* packed,
+                         void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (G < 1 || k < 1 || stride < 1 || dil < 1 || pad < 0 || cin < 1 || cout < 1) return fail("conv2d_view: bad geometry");
+    if (gn_sums && (gn_groups < 1 || cout % gn_groups)) return fail("conv2d_view: channels must divide into the norm groups");
+    ConvP p{};
+    conv_view_p(p, x, x_cs, (long)x_gs, packed, scale, shift, residual, res_cs, (long)res_gs, y, y_cs, (long)y_gs, B, h, w, cin, cout, k, stride, pad, dil, relu,
+                gn_sums, gn_groups, g_op_ws);
+    if (p.OH < 1 || p.OW < 1) return fail("conv2d_view: empty output");
+    for (int g = 0; g < G; ++g)
+        hipLaunchKernelGGL(pack_oihw_kernel, dim3(256), dim3(256), 0, st, w_oihw + (size_t)g * cout * cin * k * k, cout, cin, k, p.Kpad, p.kmode, packed + (size_t)g * p.w_gs);
+    if (g_op_bf16 == 3 && k == 1 && tune().x8) {
+        static PlaneScratch scratch;
+        const int rc = scratch.split(packed, (long)G * cout * p.Kpad, p, "conv2d_view", st);
+        if (rc) return rc;
+    }
+    return launch_conv(p, G, st);
+}
+
+static void route_out(const ConvRoute& r, int32_t* out) {
+    const int v[12] = {r.kernel, r.sums, r.BM, r.BN, r.S, r.tail_shift, r.tiles, r.blocks, r.nk, r.min_share, r.packed, r.shared_v};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+}
+static float* const kDryBase = reinterpret_cast<float*>((uintptr_t)1 << 20);      // never dereferenced
+
+// the route launch_conv takes for the launch quber_op_conv2d_view would make of these arguments on the process keys (host only: nothing is launched, no
+// device is queried).  x_off / y_off / res_off: element offsets of the views in 16-byte-aligned buffers (res_off < 0: no residual); workspace != 0: as
+// with key 2 set; cus: the compute units to assume.  out[12]: kernel, sums, BM, BN, S, tail_shift, tiles, blocks, nk, min_share, packed, shared_v (ConvRoute)
+
+int quber_debug_conv_route(int32_t x_off, int32_t x_cs, int64_t x_gs, int32_t affine, int32_t res_off, int32_t res_cs, int64_t res_gs, int32_t y_off, int32_t y_cs,
+                           int64_t y_gs, int32_t G, int32_t B, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t dil,
+                           int32_t gn_groups, int32_t workspace, int32_t cus, int32_t* out) {
+    if (G < 1 || k < 1 || stride < 1 || dil < 1 || pad < 0 || cin < 1 || cout < 1 || !out) return fail("conv_route: bad geometry");
+    if (gn_groups && (gn_groups < 1 || cout % gn_groups)) return fail("conv_route: channels must divide into the norm groups");
+    ConvP p{};
+    float* const b = kDryBase;
+    conv_view_p(p, b + x_off, x_cs, (long)x_gs, b, affine ? b : nullptr, affine ? b : nullptr, res_off >= 0 ? b + res_off : nullptr, res_cs, (long)res_gs, b + y_off, y_cs,
+                (long)y_gs, B, h, w, cin, cout, k, stride, pad, dil, 0, gn_groups ? reinterpret_cast<double*>(b) : nullptr, gn_groups, workspace ? b : nullptr);
+    if (p.OH < 1 || p.OW < 1) return fail("conv_route: empty output");
+    if (g_op_bf16 == 3 && k == 1 && tune().x8) { p.w3 = b; p.w3_plane = (long)G * cout * p.Kpad; }
+    ConvRoute r{};
+    r.cus = cus;
+    const int rc = launch_conv(p, G, nullptr, &r);
+    if (rc) return rc;
+    route_out(r, out);
+    return 0;
+}
+
+// the WinoP of quber_op_conv3x3_winograd_view
+static void wino_view_q(WinoP& q, const float* x, int x_cs, long x_gs, float* y, int y_cs, long y_gs, int B, int h, int w, int cin, int cout, int dil, int m,
+                        const float* scale, const float* shift, int relu, const float* u, float* ws, size_t ws_floats, double* gn_sums, int gn_groups,
+                        const double* n_stats, const float* n_gamma, const float* n_beta, int n_param_gs, int n_groups, int n_relu, float n_eps, float* splitk_ws) {
+    q.in = mkview(x, B, h, w, cin); q.in.cs = x_cs; q.in.gs = x_gs;
+    q.out = mkview(y, B, h, w, cout); q.out.cs = y_cs; q.out.gs = y_gs;
+    q.u = u; q.scale = scale; q.shift = shift; q.ss_gs = cout; q.relu = relu; q.dil = dil; q.m = m;
+    q.dtype = g_op_bf16;
+    q.pack = tune().wino_pack;
+    q.ws = ws; q.ws_floats = ws_floats;
+    q.gn_sum = gn_sums; q.gn_groups = gn_sums ? gn_groups : 0;
+    if (n_stats) q.norm = WinoNorm{n_stats, n_gamma, n_beta, n_groups, 0, n_param_gs, n_relu, 0.0, n_eps};
+    q.splitk_ws = splitk_ws; q.splitk_floats = splitk_ws ? g_op_ws_floats : 0;
+}
+
+int quber_op_conv3x3_winograd_view(const float* x, int32_t x_cs, int64_t x_gs, const float* w_oihw, const float* scale, const float* shift, float* y, int32_t y_cs,
+                                   int64_t y_gs, int32_t G, int32_t B, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t dil, int32_t m, int32_t relu,
+                                   double* gn_sums, int32_t gn_groups, const double* n_stats, const float* n_gamma, const float* n_beta, int32_t n_param_gs,
+                                   int32_t n_groups, int32_t n_relu, float n_eps, float* u, float* ws, int64_t ws_floats, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (G < 1 || !winograd_eligible(3, 1, dil, dil, cin, cout)) return fail("winograd_view: unsupported channel counts");
+    if ((scale == nullptr) != (shift == nullptr)) return fail("winograd_view: scale and shift go together");
+    if (m != 2 && m != 4 && m != 6) return fail("winograd_view: the output tile edge is 2, 4 or 6");
+    if (gn_sums && (gn_groups < 1 || cout % gn_groups)) return fail("winograd_view: channels must divide into the norm groups");
+    const size_t P = (size_t)(m + 2) * (m + 2);
+    for (int g = 0; g < G; ++g) {
+        const int rc = launch_winograd_weights(w_oihw + (size_t)g * cout * cin * 9, cout, cin, m, u + g * P * cout * cin, st);
+        if (rc) return rc;
+    }
+    WinoP q{};
+    wino_view_q(q, x, x_cs, (long)x_gs, y, y_cs, (long)y_gs, B, h, w, cin, cout, dil, m, scale, shift, relu, u, ws, (size_t)ws_floats, gn_sums, gn_groups, n_stats,
+                n_gamma, n_beta, n_param_gs, n_groups, n_relu, n_eps, g_op_ws);
+    if (op_wino_single(q, B, G)) {
+        int rc = winograd_fused_prepare();
+        if (rc) return rc;
+        for (int g = 0; g < G; ++g) {
+            rc = launch_winograd_fused_pack(u + g * P * cout * cin, cout, cin, const_cast<float*>(q.uf) + g * P * cout * cin, st);
+            if (rc) return rc;
+        }
+    }
+    return launch_conv_winograd(q, B, G, st);
+}
+
+// ... and its route (host only); in_place: y is x; norm / gn_groups != 0: an input norm / sums are requested; out[12] as quber_debug_conv_route
+int quber_debug_winograd_route(int32_t x_cs, int64_t x_gs, int32_t y_cs, int64_t y_gs, int32_t in_place, int32_t G, int32_t B, int32_t h, int32_t w, int32_t cin,
+                               int32_t cout, int32_t dil, int32_t m, int32_t gn_groups, int32_t norm_groups, int64_t ws_floats, int32_t* out) {
+    if (G < 1 || !out || !winograd_eligible(3, 1, dil, dil, cin, cout)) return fail("winograd_route: unsupported channel counts");
+    if (m != 2 && m != 4 && m != 6) return fail("winograd_route: the output tile edge is 2, 4 or 6");
+    if (gn_groups && cout % gn_groups) return fail("winograd_route: channels must divide into the norm groups");
+    float* const b = kDryBase;
+    WinoP q{};
+    wino_view_q(q, b, x_cs, (long)x_gs, in_place ? b : b + (1 << 20), y_cs, (long)y_gs, B, h, w, cin, cout, dil, m, nullptr, nullptr, 0, b, b, (size_t)ws_floats,
+                gn_groups ? reinterpret_cast<double*>(b) : nullptr, gn_groups, norm_groups ? reinterpret_cast<const double*>(b) : nullptr, b, b, cin, norm_groups, 1,
+                1e-5f, nullptr);
+    (void)op_wino_single(q, B, G);
+    ConvRoute r{};
+    const int rc = launch_conv_winograd(q, B, G, nullptr, &r);
+    if (rc) return rc;
+    route_out(r, out);
+    return 0;
+}
+
+// the ConvP of the dual op: y [G][B][oh][ow][mid] (gs y_gs), x [G][B][h2][w2][cin] (x_gs), w [G][cout][mid + cin] (w_gs), shift / ones [G][cout] (ss_gs), out (out_gs)
+static void dual_view_p(ConvP& p, const float* y, long y_gs, const float* x, long x_gs, const float* w, long w_gs, const float* shift, const float* ones, int ss_gs,
+                        float* out, long out_gs, int B, int oh, int ow, int mid, int h2, int w2, int cin, int stride, int cout, int relu, float* ws) {
+    p.in = y; p.in2 = x; p.w = w; p.scale = ones; p.shift = shift; p.out = out;
+    conv_geometry(p, B, oh, ow, mid, cout, 1, 1, 0, 1);
+    p.H2 = h2; p.W2 = w2; p.in2_cs = cin; p.stride2 = stride; p.K1 = mid;
+    p.K = mid + cin; p.Kpad = mid + cin; p.relu = relu;
+    p.in_gs = y_gs; p.in2_gs = x_gs; p.w_gs = w_gs; p.ss_gs = ss_gs; p.out_gs = out_gs;
+    p.bf16 = g_op_bf16;
+    p.ws = ws; p.ws_floats = ws ? g_op_ws_floats : 0;
+}
+
+int quber_op_conv1x1_dual_view(const float* y, int64_t y_gs, const float* x, int64_t x_gs, const float* w, int64_t w_gs, const float* shift, const float* ones,
+                               int32_t ss_gs, float* out, int64_t out_gs, int32_t G, int32_t B, int32_t oh, int32_t ow, int32_t mid, int32_t h2, int32_t w2, int32_t cin,
+                               int32_t stride, int32_t cout, int32_t relu, void* stream) {
+    if (G < 1) return fail("conv1x1_dual_view: bad geometry");
+    ConvP p{};
+    dual_view_p(p, y, (long)y_gs, x, (long)x_gs, w, (long)w_gs, shift, ones, ss_gs, out, (long)out_gs, B, oh, ow, mid, h2, w2, cin, stride, cout, relu, g_op_ws);
+    if (g_op_bf16 == 3 && tune().x8) {
+        static PlaneScratch scratch;
+        const int rs = scratch.split(w, (long)(G - 1) * w_gs + (long)cout * p.Kpad, p, "conv1x1_dual_view", (hipStream_t)stream);
+        if (rs) return rs;
+    }
+    const int rc = launch_conv_dual(p, G, (hipStream_t)stream);
+    if (rc == 1) return fail("conv1x1_dual_view: launch not covered by the dual kernel (workspace: tuning key 2)");
+    return rc;
+}
+
+int quber_debug_dual_route(int64_t y_gs, int64_t x_gs, int64_t w_gs, int32_t ss_gs, int64_t out_gs, int32_t G, int32_t B, int32_t oh, int32_t ow, int32_t mid, int32_t h2,
+                           int32_t w2, int32_t cin, int32_t stride, int32_t cout, int32_t workspace, int32_t cus, int32_t* out) {
+    if (G < 1 || !out) return fail("dual_route: bad geometry");
+    float* const b = kDryBase;
+    ConvP p{};
+    dual_view_p(p, b, (long)y_gs, b, (long)x_gs, b, (long)w_gs, b, b, ss_gs, b, (long)out_gs, B, oh, ow, mid, h2, w2, cin, stride, cout, 0, workspace ? b : nullptr);
+    if (g_op_bf16 == 3 && tune().x8) { p.w3 = b; p.w3_plane = (long)(G - 1) * w_gs + (long)cout * p.Kpad; }
+    ConvRoute r{};
+    r.cus = cus;
+    const int rc = launch_conv_dual(p, G, nullptr, &r);
+    if (rc == 1) return fail("dual_route: launch not covered by the dual kernel");
+    if (rc) return rc;
+    route_out(r, out);
+    return 0;
 }
 
 int quber_op_groupnorm(const float* x, int32_t B, int32_t h, int32_t w, int32_t c, int32_t groups, const float* gamma,

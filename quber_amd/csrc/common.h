@@ -133,9 +133,27 @@ struct WinoP {
     size_t splitk_floats;
 };
 
+// The route of a convolution launch.  A launcher handed one (`dry`) walks its own decisions - tile shape, K partitions, persistent or not,
+// where the GroupNorm sums are gathered - fills it in and returns where it would have launched its first kernel: nothing is launched and
+// no device is queried (quber_debug_conv_route / _winograd_route / _dual_route, the tests' host view of the routing).
+enum { ROUTE_TILE = 1, ROUTE_SPLITK = 2, ROUTE_PERSISTENT = 3, ROUTE_WINO = 4, ROUTE_WINO_FUSED = 5, ROUTE_X8 = 6, ROUTE_SEPARATE = 7 };
+struct ConvRoute {
+    int kernel;              // ROUTE_TILE: one tile per block, ROUTE_SPLITK: ... + splitk_reduce_kernel, ROUTE_PERSISTENT, ROUTE_WINO: the three-kernel
+                             //   pipeline, ROUTE_WINO_FUSED: the single kernel, ROUTE_X8
+    int sums;                // 0: no sums requested; the kernel's value: gathered there (ROUTE_SPLITK: by the reduce kernel - and, tail_shift > 0, by
+                             //   the whole tiles' epilogue); ROUTE_SEPARATE: launch_gn_stats over the output
+    int BM, BN;              // tile: rows x channels (Winograd: tiles per block of the kernel that gathers the sums x channels)
+    int S;                   // K partitions (split tail: pieces per remaining tile; Winograd pipeline: passes over the batch)
+    int tail_shift;          // split tail: log2 of the pieces, else 0
+    int tiles, blocks, nk, min_share;      // persistent launch: the arguments of conv_persistent_segments; conv_x8: tiles and blocks;
+                             //   Winograd: tiles per image (`tiles`), single kernel: blocks per group
+    int packed, shared_v;    // Winograd pipeline: an axis is packed (key 51); the groups share one input transform
+    int cus;                 // IN: compute units to assume where a rule counts rounds of tiles (conv_x8, key 35 = 1)
+};
+
 // launchers (all asynchronous on `st`, no allocation, no synchronisation)
-int launch_conv(const ConvP& p, int G, hipStream_t st);
-int launch_conv_winograd(const WinoP& q, int B, int G, hipStream_t st);
+int launch_conv(const ConvP& p, int G, hipStream_t st, ConvRoute* dry = nullptr);
+int launch_conv_winograd(const WinoP& q, int B, int G, hipStream_t st, ConvRoute* dry = nullptr);
 int launch_winograd_weights(const float* w_oihw, int Cout, int Cin, int m, float* u, hipStream_t st);
 void winograd_weights_host(const float* w_oihw, int Cout, int Cin, int m, float* u);
 bool winograd_eligible(int k, int stride, int pad, int dil, int Cin, int Cout);
@@ -145,7 +163,7 @@ double winograd_mac_ratio(int H, int W, int dil, int m);
 double winograd_mac_ratio_run(int H, int W, int dil, int m, bool pack);     // ... of the tiles the three-kernel pipeline runs (key 51)
 // single-kernel F(4x4,3x3) (wino_fused.hip)
 bool winograd_fused_ok(const WinoP& q, int B, int G);
-int launch_conv_winograd_fused(const WinoP& q, int B, int G, hipStream_t st);
+int launch_conv_winograd_fused(const WinoP& q, int B, int G, hipStream_t st, ConvRoute* dry = nullptr);
 void winograd_fused_pack_host(const float* u, int Cout, int Cin, float* uf);
 int launch_winograd_fused_pack(const float* u, int Cout, int Cin, float* uf, hipStream_t st);
 size_t winograd_fused_ws_floats(int B, int Cin, int G);
@@ -211,14 +229,14 @@ struct TuneScope {
 };
 bool tuning_set(Tuning& t, int key, int value);   // false: not a key of Tuning
 // persistent launch of the implicit GEMM (conv_persist.hip); p.mtiles / ntiles / vec_out filled in by the caller
-template <int BM, int BN, int WM, int WN> int launch_conv_persistent(ConvP p, int G, int bpc, hipStream_t st);
+template <int BM, int BN, int WM, int WN> int launch_conv_persistent(ConvP p, int G, int bpc, hipStream_t st, ConvRoute* dry = nullptr);
 size_t conv_persistent_ws_floats(int BM, int BN, int bpc);
 bool conv_persistent_ok(const ConvP& p);
 int conv_persistent_segments(int T, int P, int nk, int min_slices, int bid, int* out4, int cap);
 int conv_persistent_fixup(int T, int P, int nk, int min_slices, int xcd, int j, int* tile, int* slots, int cap);
-int launch_conv_dual(ConvP p, int G, hipStream_t st);   // 0 done, 1 not covered (run the two convolutions), -1 error
+int launch_conv_dual(ConvP p, int G, hipStream_t st, ConvRoute* dry = nullptr);   // 0 done, 1 not covered (run the two convolutions), -1 error
 bool conv_h8_patch_takes(const ConvP& p, int G, bool norm);     // conv_h8.hip: this launch (ConvP as launch_conv receives it) runs on a patch kernel [that can normalise its input]
-int launch_conv_x8(ConvP p, int G, hipStream_t st);     // bf16x3 1x1 / grouped GEMM, 256 x 128 tiles (conv_x8.hip): 0 done, 1 not covered, -1 error
+int launch_conv_x8(ConvP p, int G, hipStream_t st, ConvRoute* dry = nullptr);     // bf16x3 1x1 / grouped GEMM, 256 x 128 tiles (conv_x8.hip): 0 done, 1 not covered, -1 error
 int launch_split_bf16x3(const float* w, long n, void* planes, hipStream_t st);     // w [n] -> bf16 terms [3][n]
 int launch_conv_h8(ConvP p, int G, hipStream_t st);     // fp16 data path, 256 x 256 tiles (conv_h8.hip): 0 done, 1 not covered, -1 error
 #ifdef PK_STAMPS

@@ -1050,8 +1050,22 @@ static bool lean_loader(ConvP& p) {
     return true;
 }
 
+// GroupNorm sums in the epilogue: 16-byte stores, whole float4s inside one norm group, at most 32 groups, and images
+// of at least one tile of rows (a tile then meets at most two images); otherwise a separate pass over the output
+static bool igemm_gn_sep(const ConvP& p, int BM) {
+    return p.gn_sum && !(p.vec_out && p.gn_cpg % 4 == 0 && p.gn_groups <= 32 && p.ohw >= BM && p.ohw >= 8);
+}
+
+// fills the route of a dry run (ConvRoute, common.h); false = a real launch
+static bool routed(ConvRoute* dry, int kernel, bool sums, bool gn_sep, int BM, int BN, int S, int tail_shift) {
+    if (!dry) return false;
+    dry->kernel = kernel; dry->sums = !sums ? 0 : gn_sep ? ROUTE_SEPARATE : kernel;
+    dry->BM = BM; dry->BN = BN; dry->S = S; dry->tail_shift = tail_shift;
+    return true;
+}
+
 template <int BM, int BN, int WM, int WN>
-static int run(ConvP p, int G, int S, hipStream_t st) {
+static int run(ConvP p, int G, int S, hipStream_t st, ConvRoute* dry) {
     p.mtiles = (p.M + BM - 1) / BM;
     p.ntiles = (p.Cout + BN - 1) / BN;
     p.vec_out = (p.Cout % 4 == 0) && (p.out_cs % 4 == 0) && (((uintptr_t)p.out & 15) == 0) && (p.out_gs % 4 == 0) &&
@@ -1061,9 +1075,7 @@ static int run(ConvP p, int G, int S, hipStream_t st) {
     if (p.es == 2 && p.vec_out && p.Cout % 8 == 0 && p.out_cs % 8 == 0 && p.out_gs % 8 == 0 && !p.prelu &&
         (!p.res || (p.res_cs % 8 == 0 && p.res_gs % 8 == 0)) && (!p.scale || (p.ss_gs % 8 == 0 && (((uintptr_t)p.scale & 31) == 0))))
         p.vec_out = 2;        // fp16 tensors: 16-byte accesses of 8 channels
-    // GroupNorm sums in the epilogue: 16-byte stores, whole float4s inside one norm group, at most 32 groups, and images
-    // of at least one tile of rows (a tile then meets at most two images); otherwise a separate pass over the output
-    const bool gn_sep = p.gn_sum && !(p.vec_out && p.gn_cpg % 4 == 0 && p.gn_groups <= 32 && p.ohw >= BM && p.ohw >= 8);
+    const bool gn_sep = igemm_gn_sep(p, BM);
     double* const gn_sum = p.gn_sum;
     if (gn_sep) p.gn_sum = nullptr;
     auto gn_separate = [&]() {
@@ -1116,6 +1128,7 @@ static int run(ConvP p, int G, int S, hipStream_t st) {
         ProfScope prof(tag, conv_bytes, conv_flops, st);
         const dim3 grid(p.mtiles * p.ntiles, 1, G);
         const bool lean = lean_loader(p);
+        if (routed(dry, ROUTE_TILE, gn_sum, gn_sep, BM, BN, 1, 0)) return 0;
         if (skip) launch_igemm<BM, BN, WM, WN, 3, 4>(lean, grid, block, st, p);
         else launch_igemm<BM, BN, WM, WN, 0, 4>(lean, grid, block, st, p);
         QB_CHECK(hipGetLastError());
@@ -1134,13 +1147,14 @@ static int run(ConvP p, int G, int S, hipStream_t st) {
         if (p.bf16 == 3 && (BM == 256 || (BM == 64 && nk <= 8))) exact_fallback();
         const int bpc = p.es == 2 ? 3 : BM == 64 ? 5 : 2;          // conv_persist.hip: pk_occupancy()
         if (p.ws_floats >= conv_persistent_ws_floats(BM, BN, bpc)) {
+            (void)routed(dry, ROUTE_PERSISTENT, gn_sum, gn_sep, BM, BN, 1, 0);
             {
                 ProfScope prof(tag, conv_bytes, conv_flops, st);
                 int rc = 0;
-                if constexpr (BM == BN || BM == 256) rc = launch_conv_persistent<BM, BN, WM, WN>(p, G, bpc, st);
+                if constexpr (BM == BN || BM == 256) rc = launch_conv_persistent<BM, BN, WM, WN>(p, G, bpc, st, dry);
                 if (rc) return rc;
             }
-            return gn_separate();
+            return dry ? 0 : gn_separate();
         }
     }
     // Split tail: with more than one round of tiles, cut the tiles of the ragged last round into 2^shift K-pieces that
@@ -1165,6 +1179,7 @@ static int run(ConvP p, int G, int S, hipStream_t st) {
                 p.ws_row0 = (int)row0;
                 p.ws_rows = p.M - (int)row0;
                 // every piece owns at least one K-slice: (2^shift - 1) * kchunk < nk because nk >= 8 * 2^shift
+                if (routed(dry, ROUTE_SPLITK, gn_sum, gn_sep, BM, BN, 1 << shift, shift)) return 0;
                 {
                     ProfScope prof(tag, conv_bytes, conv_flops, st);
                     launch_igemm<BM, BN, WM, WN, 2, 0>(lean, dim3((unsigned)(nfull + (rem << shift)), 1, G), block, st, p);
@@ -1181,6 +1196,7 @@ static int run(ConvP p, int G, int S, hipStream_t st) {
     // (so does the dilated layer that skips padded filter rows on 64x64 tiles - ASPP d = 18 on a 30-row map: 1.49 ms as bf16x3 against 1.03 ms
     //  exact at batch 16, profiles/r12_final_conv_layers_dtype{0,3}.md)
     if (p.bf16 == 3 && (BM == 256 || (BM == 64 && (nk <= 8 || skip)))) exact_fallback();
+    if (routed(dry, S > 1 ? ROUTE_SPLITK : ROUTE_TILE, gn_sum, gn_sep, BM, BN, S, 0)) return 0;
     if (p.bf16) {
         {
             ProfScope prof(tag, conv_bytes, conv_flops, st);
@@ -1231,7 +1247,7 @@ static int run(ConvP p, int G, int S, hipStream_t st) {
 }
 
 
-int launch_conv(const ConvP& p0, int G, hipStream_t st) {
+int launch_conv(const ConvP& p0, int G, hipStream_t st, ConvRoute* dry) {
     ConvP p = p0;
     p.acc_chunk = tune().acc_chunk;
     if (p.es != 2) p.es = 4;
@@ -1254,6 +1270,7 @@ int launch_conv(const ConvP& p0, int G, hipStream_t st) {
     if (p.kmode && (p.Cin % BK || p.K != p.Kpad)) return fail("conv: slice-major weights need Cin % 32 == 0");
     if ((p.scale == nullptr) != (p.shift == nullptr)) return fail("conv: scale and shift go together");
     if (p.es == 2 && tune().force_tile == 0) {      // the wide layers of the fp16 data path: 256 x 256 tiles, LDS-DMA pipeline (conv_h8.hip)
+        if (dry) return fail("conv: no dry run of the fp16 data path");
         const int rc = launch_conv_h8(p, G, st);
         if (rc != 1) return rc;
     }
@@ -1271,46 +1288,46 @@ int launch_conv(const ConvP& p0, int G, hipStream_t st) {
             if (p0.res) q.res = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p0.res) + (long)g * p0.res_gs * es);
             if (p0.scale) { q.scale = p0.scale + (long)g * p0.ss_gs; q.shift = p0.shift + (long)g * p0.ss_gs; }
             if (p0.gn_sum) q.gn_sum = p0.gn_sum + (long)g * p0.B * p0.gn_groups * 2;
-            const int rc = launch_conv(q, 1, st);
+            const int rc = launch_conv(q, 1, st, dry);
             if (rc) return rc;
         }
         return 0;
     }
     if (p.es == 4 && p.bf16 == 3 && tune().force_tile == 0 && tune().force_split == 0) {      // bf16x3: the wide 1x1 launches, pre-split weights, LDS-DMA pipeline (conv_x8.hip)
-        const int rc = launch_conv_x8(p, G, st);
+        const int rc = launch_conv_x8(p, G, st, dry);
         if (rc != 1) return rc;
     }
     switch (tune().force_tile) {
-        case 1: return run<64, 64, 2, 2>(p, G, 1, st);
-        case 2: return run<128, 128, 2, 2>(p, G, 1, st);
-        case 4: return run<256, 32, 4, 1>(p, G, 1, st);
-        case 3: return run<128, 64, 2, 2>(p, G, 1, st);
+        case 1: return run<64, 64, 2, 2>(p, G, 1, st, dry);
+        case 2: return run<128, 128, 2, 2>(p, G, 1, st, dry);
+        case 4: return run<256, 32, 4, 1>(p, G, 1, st, dry);
+        case 3: return run<128, 64, 2, 2>(p, G, 1, st, dry);
         default: break;
     }
     // Tile shape (sweep: profiles/r01i_conv_sweep_*.md).  <= 32 output channels: 256x32.  <= 64 channels, and the
     // memory-bound residual 1x1 layers with a short K (res2-4 conv3): 64x64, whose 7 resident blocks per CU keep more
     // loads in flight.  Otherwise 128x128, split when the model says so; 64x64 again for launches too small for that.
     const int nk = p.Kpad / BK;
-    if (p.Cout <= 32) return run<256, 32, 4, 1>(p, G, choose_split(p, G, 256, 32, igemm_occupancy(256, 32)), st);
+    if (p.Cout <= 32) return run<256, 32, 4, 1>(p, G, choose_split(p, G, 256, 32, igemm_occupancy(256, 32)), st, dry);
     // 33-64 output channels without a residual, at least a round of tiles: 128x64 (each wave 64x32: the weight fragments
     // are read from LDS half as often as with 64x64 tiles; +3-5 % on stem.conv3 / res2 conv1, conv2 - tools/tile_ab.py)
-    if (tune().tile_128x64 && p.Cout <= 64 && p.Cout > 32 && !p.res && (long)((p.M + 127) / 128) * G >= 1024) return run<128, 64, 2, 2>(p, G, 1, st);
+    if (tune().tile_128x64 && p.Cout <= 64 && p.Cout > 32 && !p.res && (long)((p.M + 127) / 128) * G >= 1024) return run<128, 64, 2, 2>(p, G, 1, st, dry);
     // (64 x 256 tiles for the residual 1x1 layers - input rows read once, 512-byte row segments - measured 30-50 % SLOWER than
     // 64x64 in both the fp32 and the fp16 path, profiles/r03x_tile_64x256_rejected.txt: those layers live on blocks in flight)
-    if (p.Cout <= 64 || (p.res && nk <= 8 && p.Cout >= 128)) return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st);
+    if (p.Cout <= 64 || (p.res && nk <= 8 && p.Cout >= 128)) return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st, dry);
     // dilated layers that skip the filter rows lying in the padding (ASPP d = 18 on a 30-row map): 64-row tiles span 2-3 map rows
     // instead of 4-5, so more of them see a filter row entirely in the padding - 1.28 -> 1.07 ms on that layer (tools/aspp_d18_ab.py)
     if (p.skip_rows && p.es != 2 && p.kmode == 0 && p.kh > 1 && p.dil * 5 >= p.H * 2)
-        return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st);
+        return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st, dry);
     const long tiles128 = (long)((p.M + 127) / 128) * ((p.Cout + 127) / 128) * G;
     const int s128 = choose_split(p, G, 128, 128, igemm_occupancy(128, 128));
-    if (tiles128 < 64 || (tiles128 < 384 && s128 == 1)) return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st);
+    if (tiles128 < 64 || (tiles128 < 384 && s128 == 1)) return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st, dry);
     // 1x1 layers whose 128 x 128 tiling is at most ~5 tiles per CU (res4 / res5 conv1, the ASPP 1x1 and res3 conv1 at batch 16; every wide 1x1 layer
     // at batches 1-4): 64 x 64 tiles, one per block - five to seven resident blocks per CU hide what two 128 x 128 blocks (split-K or persistent) cannot.
     // tools/conv_sweep.py at 1 / 2 / 4 / 8 / 16 frames, round 6: 0.211 -> 0.176 ms on res4 conv1 and 0.357 -> 0.322 on res5.0 conv1 at batch 16,
     // 0.134 -> 0.107 on res5 conv3 at batch 2; the batch-1 step 3.71 -> 3.50 ms, 1280x720 7.40 -> 6.96 ms (profiles/r14d_tile_rule.md)
     if (tune().small_n_64 && p.es != 2 && p.kh == 1 && p.kw == 1 && !p.in2 && nk >= 16 && tiles128 <= 1280)
-        return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st);
+        return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st, dry);
     // ... and, exact fp32, every 1x1 GEMM of K <= 1024 however large the launch - the Winograd position GEMMs of the 256- / 512-channel layers
     // (fusion_res2 / res3, res4 / res5 conv2), the fusion 1x1 convolutions of res2 / res3, res5 conv3: a K loop of 8-32 slices is over before a
     // 128 x 128 block has amortised its prologue and epilogue, and only two of those fit a CU.  Per layer at batch 16 (rocprofv3, forced tiles):
@@ -1318,8 +1335,8 @@ int launch_conv(const ConvP& p0, int G, hipStream_t st) {
     // on 64 x 64 tiles and keep the persistent 128 x 128 launch (profiles/r14d_tile_rule.md)
     // (128 x 64 tiles for fusion_res5.conv, K = 4096: 2.42 against 2.49 ms in the layer table, nothing in the step - not kept)
     if (tune().small_n_64 == 1 && p.es != 2 && p.bf16 == 0 && p.kh == 1 && p.kw == 1 && !p.in2 && nk <= 32)
-        return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st);
-    return run<128, 128, 2, 2>(p, G, s128, st);
+        return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st, dry);
+    return run<128, 128, 2, 2>(p, G, s128, st, dry);
 }
 
 }  // namespace quber

@@ -795,7 +795,7 @@ __global__ __launch_bounds__(256) void pk_fixup_kernel(const ConvP p, int P) {
 // Eligibility beyond conv_persistent_ok() is decided by the caller (conv_igemm.hip: run<>): no skipped filter rows, a
 // workspace of 2 * P tiles.  p.mtiles / p.ntiles / p.vec_out are filled in.  Returns 0 on success.
 template <int BM, int BN, int WM, int WN>
-int launch_conv_persistent(ConvP p, int G, int bpc, hipStream_t st) {
+int launch_conv_persistent(ConvP p, int G, int bpc, hipStream_t st, ConvRoute* dry) {
     const int nk = p.Kpad / BK;
     p.pk_tpg = p.mtiles * p.ntiles;
     p.pk_T = p.pk_tpg * G;
@@ -808,6 +808,10 @@ int launch_conv_persistent(ConvP p, int G, int bpc, hipStream_t st) {
         // never more blocks than there are shares of pk_min K-slices
         const long shares = (long)p.pk_T * nk / p.pk_min;
         if (shares < P) P = (int)(shares < 8 ? 8 : shares / 8 * 8);
+    }
+    if (dry) {      // the work list is conv_persistent_segments(tiles, blocks, nk, min_share, block)
+        dry->tiles = p.pk_T; dry->blocks = P; dry->nk = nk; dry->min_share = p.pk_min;
+        return 0;
     }
     const dim3 block(WM * WN * 64);
     p.pk_in_bytes = (int)((long)p.B * p.H * p.W * p.in_cs * 4);
@@ -906,7 +910,7 @@ bool conv_persistent_ok(const ConvP& p) {
 
 // conv3 + projection shortcut of a bottleneck as one 1x1 GEMM over two inputs (kernel: EPI 3).  Returns 1 when the
 // launch is not covered (the caller then runs the two convolutions separately), 0 on success, -1 on a launch error.
-int launch_conv_dual(ConvP p, int G, hipStream_t st) {
+int launch_conv_dual(ConvP p, int G, hipStream_t st, ConvRoute* dry) {
     if (!tune().persist || !p.in2 || !p.ws) return 1;
     p.acc_chunk = tune().acc_chunk;
     if (p.es == 2) {        // fp16 data path: K-side quantities in 4-byte units (two halfs), as launch_conv hands them over
@@ -922,7 +926,7 @@ int launch_conv_dual(ConvP p, int G, hipStream_t st) {
         p.es = 4;
         if (p.bf16 == 3 && p.w3 && p.kh == 1 && p.kw == 1 && p.pad == 0 && p.stride == 1 && !p.kmode && p.K == p.Kpad) {      // bf16x3: 256 x 128 tiles, LDS-DMA pipeline (conv_x8.hip)
             p.ohw = p.OH * p.OW;
-            const int rc = launch_conv_x8(p, G, st);
+            const int rc = launch_conv_x8(p, G, st, dry);
             if (rc != 1) return rc;
         }
     }
@@ -953,13 +957,14 @@ int launch_conv_dual(ConvP p, int G, hipStream_t st) {
     p.ntiles = (p.Cout + BMs - 1) / BMs;
     const double out_bytes = 4.0 * G * (double)p.M * p.Cout;
     const double bytes = 4.0 * G * ((double)p.M * p.Kpad + (double)p.Cout * p.Kpad) + out_bytes;
+    if (dry) { dry->kernel = ROUTE_PERSISTENT; dry->sums = 0; dry->BM = dry->BN = BMs; dry->S = 1; dry->tail_shift = 0; }
     ProfScope prof(tag, bytes, 2.0 * G * (double)p.M * p.Kpad * p.Cout, st);
-    const int rc = big ? launch_conv_persistent<128, 128, 2, 2>(p, G, bpc, st) : launch_conv_persistent<64, 64, 2, 2>(p, G, bpc, st);
+    const int rc = big ? launch_conv_persistent<128, 128, 2, 2>(p, G, bpc, st, dry) : launch_conv_persistent<64, 64, 2, 2>(p, G, bpc, st, dry);
     return rc ? -1 : 0;
 }
 
-template int launch_conv_persistent<64, 64, 2, 2>(ConvP, int, int, hipStream_t);
-template int launch_conv_persistent<128, 128, 2, 2>(ConvP, int, int, hipStream_t);
-template int launch_conv_persistent<256, 32, 4, 1>(ConvP, int, int, hipStream_t);
+template int launch_conv_persistent<64, 64, 2, 2>(ConvP, int, int, hipStream_t, ConvRoute*);
+template int launch_conv_persistent<128, 128, 2, 2>(ConvP, int, int, hipStream_t, ConvRoute*);
+template int launch_conv_persistent<256, 32, 4, 1>(ConvP, int, int, hipStream_t, ConvRoute*);
 
 }  // namespace quber

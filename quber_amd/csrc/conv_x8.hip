@@ -437,7 +437,10 @@ int launch_split_bf16x3(const float* w, long n, void* planes, hipStream_t st) {
 
 // bf16x3 mode, 1x1 / pad 0, K a multiple of 32, pre-split weight planes present, one input, 16-byte epilogue accesses, a tile count that
 // fills the chip's one-block-per-CU grid a few times.  returns 0 = launched, 1 = not covered, -1 = error
-int launch_conv_x8(ConvP p, int G, hipStream_t st) {
+// GroupNorm sums in the epilogue as in conv_igemm.hip (igemm_gn_sep; 16-byte stores are a condition of the launch itself)
+static bool x8_gn_sep(const ConvP& p) { return p.gn_sum && !(p.gn_cpg % 4 == 0 && p.gn_groups <= 32 && p.ohw >= X8_BM); }
+
+int launch_conv_x8(ConvP p, int G, hipStream_t st, ConvRoute* dry) {
     if (!tune().x8 || p.es != 4 || p.bf16 != 3 || !p.w3 || p.prelu || p.acc_chunk < 0) return 1;
     const bool dual = p.in2 != nullptr;          // launch_conv_dual: K = K1 channels of `in`, then the channels of `in2` sampled at stride2
     if (p.kh != 1 || p.kw != 1 || p.pad != 0 || p.Cin % 32 || p.K != p.Kpad || p.Cin != (dual ? p.K1 : p.K) || p.Kpad / 32 < 2) return 1;
@@ -461,7 +464,7 @@ int launch_conv_x8(ConvP p, int G, hipStream_t st) {
     p.ntiles = (p.Cout + X8_BN - 1) / X8_BN;
     const long tiles = (long)p.mtiles * p.ntiles * G;
     if (tiles > 0x3fffffff) return 1;
-    const int cus = device_cus();          // per device: a process may drive several
+    const int cus = dry ? dry->cus : device_cus();          // per device: a process may drive several (a dry run: the caller's figure, no device query)
     if (cus <= 0) return fail("conv_x8: cannot query the device");
     if (tune().x8 < 2) {         // (key 35 = 2: every covered launch - the tests)
         if (p.Kpad / 32 < tune().x8_min_nk || p.Cout < X8_BN) return 1;      // short K: the HBM-bound residual layers keep conv_igemm.hip's 64 x 64 tiles
@@ -479,9 +482,14 @@ int launch_conv_x8(ConvP p, int G, hipStream_t st) {
     x8_magic((unsigned)(p.gn_sum && p.gn_cpg > 0 ? p.gn_cpg : 1), p.dv_m[4], p.dv_s[4]);
     p.h8_ss_bytes = ((G - 1) * p.ss_gs + p.Cout) * 4;
     if (p.acc_chunk == 0) p.acc_chunk = 0x7fffffff;       // 0 = one chain over the whole K
-    const bool gn_sep = p.gn_sum && !(p.gn_cpg % 4 == 0 && p.gn_groups <= 32 && p.ohw >= X8_BM);
+    const bool gn_sep = x8_gn_sep(p);
     double* const gn_sum = p.gn_sum;
     if (gn_sep) p.gn_sum = nullptr;
+    if (dry) {
+        dry->kernel = ROUTE_X8; dry->sums = !gn_sum ? 0 : gn_sep ? ROUTE_SEPARATE : ROUTE_X8;
+        dry->BM = X8_BM; dry->BN = X8_BN; dry->S = 1; dry->tail_shift = 0; dry->tiles = p.pk_T; dry->blocks = (int)std::min<long>(tiles, cus);
+        return 0;
+    }
     {
         const double out_bytes = 4.0 * G * (double)p.M * p.Cout;
         const double conv_bytes = 4.0 * G * ((double)p.B * p.H * p.W * p.Cin + (double)p.Cout * p.K) + out_bytes * (p.res ? 2.0 : 1.0);

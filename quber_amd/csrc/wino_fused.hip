@@ -60,10 +60,12 @@ using f32x2 = __attribute__((ext_vector_type(2))) float;
 #define WF_SKIP 0                               // diagnostic builds of the 32 x 32 kernel only (tools/wino_fused_ablate.sh): bit 0 no patch loads, 1 no filter loads, 2 no transforms, 4 no MFMA, 5 no epilogue, 6 no K loop
 #endif
 #ifndef WF_OPT
-#define WF_OPT 7                                // A/B switches of the round-4 diet (profiles/r09d_wino_fused_diet.md): bit 0 = no transform work for rounds that do not
+#define WF_OPT 3                                // A/B switches of the round-4 diet (profiles/r09d_wino_fused_diet.md): bit 0 = no transform work for rounds that do not
 #endif                                          // exist (the last two rounds of the K loop; 16 x 64 kernel only: in the 32 x 32 kernel the branches cost 20 %), bit 1 = MFMA operands
                                                 // swapped (filters as A): a lane's result registers are 4 consecutive CHANNELS of one tile, the epilogue stores them to LDS 16 bytes
                                                 // at a time (36 instead of 144 stores), bit 2 = GroupNorm sums of a thread's 64 outputs in packed fp32, converted to double once
+                                                // (bit 2 is off since the kernel-level sums test, tests/test_gpu_conv_forms.py: the fp32 partial sums were 1e-8 relative off the
+                                                // sums of the stored outputs, every other kernel's are exact to 2 n 2^-53; the step time is the same - profiles/conv_forms.md)
 #ifdef WF_STAMPS
 // diagnostic build (make WFX=-DWF_STAMPS, tools/wf_stamps.py): s_memtime at the phase boundaries of the first blocks
 constexpr int WF_STAMP_BLOCKS = 512, WF_STAMP_N = 16;
@@ -444,7 +446,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const float lo = a.relu ? 0.f : -__builtin_inff();
     const int b0 = (int)(((long)tb * FT) / a.per_img);
     double sa = 0.0, sq = 0.0;
+#if (WF_OPT & 4)
     f32x2 psa = {0.f, 0.f}, psq = {0.f, 0.f};          // WF_OPT & 4: the thread's 64 outputs summed in packed fp32 first
+#endif
     // the 16 pixels of the tile through a buffer descriptor, as the loader's patch: row + column offsets, and the pixels outside
     // the map (ragged last tiles, short phases, tiles past the end) are dropped by the range check instead of branches
     const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(a.out + (long)g * a.out_gs, a.out_bytes);
@@ -795,7 +799,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const float lo = a.relu ? 0.f : -__builtin_inff();
     const int b0 = (int)(((long)tb * FT) / a.per_img);
     double sa = 0.0, sq = 0.0;
+#if (WF_OPT & 4)
     f32x2 psa = {0.f, 0.f}, psq = {0.f, 0.f};          // WF_OPT & 4: the thread's 64 outputs summed in packed fp32 first
+#endif
     // the 16 pixels of the tile through a buffer descriptor, as the loader's patch: row + column offsets, and the pixels outside
     // the map (ragged last tiles, short phases, tiles past the end) are dropped by the range check instead of branches
     const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(a.out + (long)g * a.out_gs, a.out_bytes);
@@ -937,7 +943,12 @@ int wf_read_stamps(unsigned long long* dst, int n) {
 }
 #endif
 
-int launch_conv_winograd_fused(const WinoP& q, int Ball, int G, hipStream_t st) {
+// GroupNorm sums in the kernel's epilogue when a block's tiles (ft of them) meet at most two images and vectors stay inside a group
+static bool fused_gn_here(const WinoP& q, int Cout, long tiles_per_image, int ft) {
+    return q.gn_sum && q.gn_groups > 0 && q.gn_groups <= 32 && (Cout / q.gn_groups) % 4 == 0 && tiles_per_image >= ft;
+}
+
+int launch_conv_winograd_fused(const WinoP& q, int Ball, int G, hipStream_t st, ConvRoute* dry) {
     const View& in = q.in;
     const View& out = q.out;
     const int H = in.H, W = in.W, d = q.dil;
@@ -958,7 +969,12 @@ int launch_conv_winograd_fused(const WinoP& q, int Ball, int G, hipStream_t st) 
     const long tblocks = (a.tiles + ft - 1) / ft;
     if (tblocks * a.NC >= (1L << 31) || a.tiles + 64 >= (1L << 31)) return fail("winograd (fused): too many blocks");
     a.NB = (int)(tblocks * a.NC);
-    const bool gn_here = q.gn_sum && q.gn_groups > 0 && q.gn_groups <= 32 && (out.C / q.gn_groups) % 4 == 0 && a.per_img >= ft;
+    const bool gn_here = fused_gn_here(q, out.C, a.per_img, ft);
+    if (dry) {
+        dry->kernel = ROUTE_WINO_FUSED; dry->sums = !q.gn_sum ? 0 : gn_here ? ROUTE_WINO_FUSED : ROUTE_SEPARATE;
+        dry->BM = ft; dry->BN = wide ? w64::FC : FC; dry->S = 1; dry->tail_shift = 0; dry->tiles = (int)a.per_img; dry->blocks = a.NB;
+        return 0;
+    }
     a.gn_sum = gn_here ? q.gn_sum : nullptr; a.gn_groups = q.gn_groups; a.gn_cpg = q.gn_groups ? out.C / q.gn_groups : 1;
     const bool norm = q.norm.stats != nullptr;
     if (norm) {

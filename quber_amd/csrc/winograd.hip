@@ -364,8 +364,13 @@ double winograd_mac_ratio_run(int H, int W, int dil, int m, bool pack) {
 }
 
 
+// GroupNorm sums in the output transform when a block's tiles (per_block of them) meet at most two images and vectors stay inside a group
+static bool wino_gn_here(const WinoP& q, int Cout, long tiles_per_image, long per_block) {
+    return q.gn_sum && q.gn_groups > 0 && q.gn_groups <= 32 && (Cout / q.gn_groups) % 4 == 0 && tiles_per_image >= per_block;
+}
+
 template <int O, int V>     // V: channels per thread in the transforms
-static int run_winograd(const WinoP& q, int Ball, int G, hipStream_t st) {
+static int run_winograd(const WinoP& q, int Ball, int G, hipStream_t st, ConvRoute* dry) {
     constexpr int P = (O + 2) * (O + 2);
     const View& in = q.in;
     const View& out = q.out;
@@ -394,7 +399,6 @@ static int run_winograd(const WinoP& q, int Ball, int G, hipStream_t st) {
         np.cpg = Cin / np.groups;
         np.n = (double)H * W * np.cpg;
     }
-    // GroupNorm sums in the output transform when a block's tiles meet at most two images and vectors stay inside a group
     const int CVo = Cout / V, per_iter = CVo <= 256 ? 256 / CVo : 1;
     // groups of tiles per block of the output transform: 4, fewer while the grid would stay below ~8 blocks per CU
     int iters = OUT_ITERS;
@@ -402,8 +406,13 @@ static int run_winograd(const WinoP& q, int Ball, int G, hipStream_t st) {
         const long groups = CVo <= 256 ? ((long)Ball * tiles_pf + per_iter - 1) / per_iter : (long)Ball * tiles_pf * (CVo / 256);
         while (iters > 1 && groups * G / iters < 2048) iters >>= 1;
     }
-    const bool gn_here = q.gn_sum && q.gn_groups > 0 && q.gn_groups <= 32 && (Cout / q.gn_groups) % 4 == 0 &&
-                         tiles_pf >= (long)per_iter * iters;
+    const bool gn_here = wino_gn_here(q, Cout, tiles_pf, (long)per_iter * iters);
+    if (dry) {
+        dry->kernel = ROUTE_WINO; dry->sums = !q.gn_sum ? 0 : gn_here ? ROUTE_WINO : ROUTE_SEPARATE;
+        dry->BM = per_iter * iters; dry->BN = Cout; dry->S = (Ball + cb - 1) / cb; dry->tail_shift = 0;
+        dry->tiles = (int)tiles_pf; dry->packed = pk ? 1 : 0; dry->shared_v = (G > 1 && in.gs == 0 && !np.stats) ? 1 : 0;
+        return 0;
+    }
     for (int b0 = 0; b0 < Ball; b0 += cb) {
         const int B = Ball - b0 < cb ? Ball - b0 : cb;
         const long tiles = (long)B * tiles_pf;
@@ -471,7 +480,7 @@ static int run_winograd(const WinoP& q, int Ball, int G, hipStream_t st) {
     return 0;
 }
 
-int launch_conv_winograd(const WinoP& q, int B, int G, hipStream_t st) {
+int launch_conv_winograd(const WinoP& q, int B, int G, hipStream_t st, ConvRoute* dry) {
     const View& in = q.in;
     const View& out = q.out;
     if (!winograd_eligible(3, 1, q.dil, q.dil, in.C, out.C) || out.H != in.H || out.W != in.W || (q.m != 2 && q.m != 4 && q.m != 6))
@@ -479,9 +488,9 @@ int launch_conv_winograd(const WinoP& q, int B, int G, hipStream_t st) {
     if (q.m == 6 && !winograd_m6_channels_ok(in.C, out.C)) return fail("winograd: channel counts unsupported by the 6x6 variant");
     if (in.cs % 4 || out.cs % 4 || ((uintptr_t)in.p & 15) || ((uintptr_t)out.p & 15) || (in.gs & 3) || (out.gs & 3))
         return fail("winograd: operands must be 16-byte aligned");
-    if (q.algo == 2 || (q.algo == 0 && winograd_fused_ok(q, B, G))) return launch_conv_winograd_fused(q, B, G, st);
-    if (q.m == 4 && tune().wino_pairs && winograd_m6_channels_ok(in.C, out.C)) return run_winograd<4, 2>(q, B, G, st);
-    return q.m == 6 ? run_winograd<6, 2>(q, B, G, st) : q.m == 4 ? run_winograd<4, 4>(q, B, G, st) : run_winograd<2, 4>(q, B, G, st);
+    if (q.algo == 2 || (q.algo == 0 && winograd_fused_ok(q, B, G))) return launch_conv_winograd_fused(q, B, G, st, dry);
+    if (q.m == 4 && tune().wino_pairs && winograd_m6_channels_ok(in.C, out.C)) return run_winograd<4, 2>(q, B, G, st, dry);
+    return q.m == 6 ? run_winograd<6, 2>(q, B, G, st, dry) : q.m == 4 ? run_winograd<4, 4>(q, B, G, st, dry) : run_winograd<2, 4>(q, B, G, st, dry);
 }
 
 }  // namespace quber
