@@ -336,6 +336,51 @@ int quber_mask_nms(quber_ctx* ctx, const uint8_t* dev_masks, const float* dev_sc
                    int32_t on_top, uint8_t* dev_out_masks, int32_t* dev_ids, int32_t* dev_source, float* dev_out_scores,
                    int32_t* dev_report, void* stream);
 
+/* Mean-shift clustering of pixel embeddings into initial masks (csrc/meanshift.hip): the UCN base model's clustering_features ->
+ * mean_shift_smart_init (select_smart_seeds, seed_hill_climbing_ball, connected_components) and filter_labels_depth of the reference
+ * (eval/base_model.py:622-840 and :34-47, cosine metric), which it runs as torch and Python loops per frame.  The numpy statement of
+ * what these calls compute is tests/test_meanshift_cpu.py: meanshift_np, filter_depth_np; INTEGRATION.md "Initial masks from pixel
+ * embeddings" has it in words.  dot(a, b) below is accumulated in float32 in channel order 0..63, multiply and add rounded separately;
+ * dist(a, b) = 0.5 * (1 - dot(a, b)).
+ *   dev_emb f32 [B][channels][H][W], channels == 64 (anything else is an error); X[p] = the 64 values of pixel p.
+ * quber_meanshift_seeds: dev_first i32 [B], the first seed of every frame (clamped to the frame)
+ *   -> dev_indices i32 [B][num_seeds]: farthest-first - seed k + 1 is the FIRST index of the maximum over p of
+ *      min over j <= k of dist(X[p], X[seed j]).  One launch per seed.  1 <= num_seeds <= min(128, H * W).
+ * quber_meanshift_climb: dev_seeds f32 [B][num_seeds][64] in and out; with dev_indices (may be NULL) it is first set to the pixels they
+ *   name.  iters times: Z = normalize(exp(kappa Z X^T) X), on the float32 matrix pipe with float32 accumulation in a fixed order; the
+ *   partial sums of the blocks are added in float64 in block order (no floating-point atomics: two calls give the same bits, and a
+ *   frame's result does not depend on the batch it is in).  0 <= iters <= 1000, 0 <= kappa <= 64: the weights exp(kappa cos) are summed in
+ *   float32 (as in the reference), and exp(64) over a frame of 2^24 pixels is the most that stays finite.
+ * quber_meanshift_link -> dev_seed_labels i32 [B][num_seeds]: connected_components as written - in seed order, an unlabelled seed i
+ *   labels every seed j with dist(Z[j], Z[i]) <= epsilon: with the mode of the labels already there (the smallest among equal counts)
+ *   if there is one, else with the next new label.  A seed outside its own ball (a zero vector) stays -1 and uses up a label.
+ * quber_meanshift_assign: every pixel takes the label of the first seed at minimum dist; num = distinct seed labels, the first largest
+ *   of the labels 0 .. num - 1 swaps with label 0; with dev_depth_z (f32 [B][H][W], may be NULL = no filter) a label > 0 is dropped
+ *   when float32(its pixels with z > 0) / float32(its pixels) < depth_threshold; the survivors are numbered 1..count by ascending label,
+ *   those behind n_masks are dropped.  A pixel whose label is -1 belongs to no mask.
+ *   -> dev_ids i32 [B][H][W] (0, 1..count), dev_masks u8 [B][n_masks][H][W] (ids == k + 1 as 0 / 255, zero planes behind count; may be
+ *      NULL when n_masks == 0), dev_report i32 [B][4]: count, clusters before the filter, dropped by depth, 1 if truncated to n_masks.
+ *      n_masks <= 254.
+ * quber_meanshift_cluster: seeds -> climb -> link -> assign on `stream`, with every intermediate result as an output.
+ * Every output is overwritten by every call.  H * W <= 2^24.  No host copy, no synchronisation, no memset node, no cooperative launch.
+ * The workspace (seed slots, histograms, running minimum, raw labels, block partials: up to 8 MB + 8 H W bytes per frame of max_batch)
+ * is not part of quber_create: the FIRST call of any of these entries (quber_meanshift_link excepted, which needs none) allocates it and
+ * keeps it (quber_workspace_bytes counts it from then on), so that call is not capturable into a graph; later calls are.  Works on a
+ * context created with with_network = 0. */
+int quber_meanshift_seeds(quber_ctx* ctx, const float* dev_emb, int32_t batch, int32_t channels, const int32_t* dev_first, int32_t num_seeds,
+                          int32_t* dev_indices, void* stream);
+int quber_meanshift_climb(quber_ctx* ctx, const float* dev_emb, int32_t batch, int32_t channels, const int32_t* dev_indices, int32_t num_seeds,
+                          float kappa, int32_t iters, float* dev_seeds, void* stream);
+int quber_meanshift_link(quber_ctx* ctx, const float* dev_seeds, int32_t batch, int32_t num_seeds, float epsilon, int32_t* dev_seed_labels,
+                         void* stream);
+int quber_meanshift_assign(quber_ctx* ctx, const float* dev_emb, int32_t batch, int32_t channels, const float* dev_seeds,
+                           const int32_t* dev_seed_labels, int32_t num_seeds, const float* dev_depth_z, float depth_threshold, int32_t n_masks,
+                           int32_t* dev_ids, uint8_t* dev_masks, int32_t* dev_report, void* stream);
+int quber_meanshift_cluster(quber_ctx* ctx, const float* dev_emb, int32_t batch, int32_t channels, const int32_t* dev_first, int32_t num_seeds,
+                            float kappa, int32_t iters, float epsilon, const float* dev_depth_z, float depth_threshold, int32_t n_masks,
+                            int32_t* dev_indices, float* dev_seeds, int32_t* dev_seed_labels, int32_t* dev_ids, uint8_t* dev_masks,
+                            int32_t* dev_report, void* stream);
+
 /* Zoom-in refinement (csrc/zoom.hip): the gather / scatter around a second pass that shows the network every first-pass instance as
  * a padded crop resized to a fixed square - the reference's crop_rois and match_label_crop (eval/base_model.py:843-961, copies at :1088
  * and :1192), which run one mask at a time with torch.unique, nonzero and a .cpu() per paste.  The numpy statement of what the three

@@ -121,6 +121,7 @@ void quber_destroy(quber_ctx* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->perturb_ws) (void)hipFree(c->perturb_ws);
     if (c->masknms_ws) (void)hipFree(c->masknms_ws);
+    if (c->meanshift_ws) (void)hipFree(c->meanshift_ws);
     if (c->zoom_ws) (void)hipFree(c->zoom_ws);
     if (c->losses_ws) (void)hipFree(c->losses_ws);
     delete c;
@@ -548,6 +549,89 @@ int quber_mask_nms(quber_ctx* c, const uint8_t* masks, const float* scores, int3
     }
     return launch_mask_nms(masks, scores, batch, n_masks, H, W, thresh, on_top, out_masks, ids, source, out_scores, report, c->masknms_ws,
                            (hipStream_t)stream);
+}
+
+// ---- mean-shift clustering of pixel embeddings into initial masks (meanshift.hip); usable on a context without a network ----
+static int meanshift_ws(quber_ctx* c) {      // the only allocation of the five entries: made by the first call, for max_batch frames, and kept
+    if (c->meanshift_ws) return 0;
+    const size_t need = meanshift_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width);
+    QB_CHECK(hipMalloc(&c->meanshift_ws, need));
+    c->alloc_bytes += need;
+    return 0;
+}
+
+static int meanshift_args(quber_ctx* c, const char* what, int32_t batch, int32_t channels, int32_t num_seeds) {
+    if (check_batch(c, batch)) return -1;
+    if (channels != 64) return fail(std::string(what) + ": the embedding must have 64 channels (NUM_UNITS of every UCN config)");
+    if (num_seeds < 1 || num_seeds > 128) return fail(std::string(what) + ": num_seeds outside 1..128");
+    const long n = (long)c->cfg.height * c->cfg.width;
+    if (n > (1L << 24)) return fail(std::string(what) + ": a frame of more than 2^24 pixels (the pixel counts are compared in float32)");
+    if (num_seeds > n) return fail(std::string(what) + ": more seeds than the frame has pixels");
+    return 0;
+}
+
+int quber_meanshift_seeds(quber_ctx* c, const float* emb, int32_t batch, int32_t channels, const int32_t* first, int32_t num_seeds, int32_t* indices,
+                          void* stream) {
+    if (meanshift_args(c, "meanshift seeds", batch, channels, num_seeds)) return -1;
+    if (!emb || !first || !indices) return fail("meanshift seeds: null tensor");
+    if (meanshift_ws(c)) return -1;
+    return launch_meanshift_seeds(emb, first, batch, num_seeds, c->cfg.height, c->cfg.width, indices, c->meanshift_ws, c->cfg.max_batch,
+                                  (hipStream_t)stream);
+}
+
+int quber_meanshift_climb(quber_ctx* c, const float* emb, int32_t batch, int32_t channels, const int32_t* indices, int32_t num_seeds, float kappa,
+                          int32_t iters, float* seeds, void* stream) {
+    if (meanshift_args(c, "meanshift climb", batch, channels, num_seeds)) return -1;
+    if (!emb || !seeds) return fail("meanshift climb: null tensor");
+    if (iters < 0 || iters > 1000) return fail("meanshift climb: iters outside 0..1000");
+    if (!(kappa >= 0.f) || kappa > 64.f) return fail("meanshift climb: kappa outside 0..64");
+    if (meanshift_ws(c)) return -1;
+    return launch_meanshift_climb(emb, indices, seeds, batch, num_seeds, c->cfg.height, c->cfg.width, kappa, iters, c->meanshift_ws,
+                                  c->cfg.max_batch, (hipStream_t)stream);
+}
+
+int quber_meanshift_link(quber_ctx* c, const float* seeds, int32_t batch, int32_t num_seeds, float epsilon, int32_t* seed_labels, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    return launch_meanshift_link(seeds, batch, num_seeds, epsilon, seed_labels, (hipStream_t)stream);
+}
+
+static int meanshift_assign_args(const char* what, int32_t n_masks, const float* depth_z, float thresh) {
+    if (n_masks < 0 || n_masks > 254) return fail(std::string(what) + ": n_masks outside 0..254");
+    if (depth_z && !(thresh >= 0.f && thresh <= 1.f)) return fail(std::string(what) + ": depth threshold outside 0..1");
+    return 0;
+}
+
+int quber_meanshift_assign(quber_ctx* c, const float* emb, int32_t batch, int32_t channels, const float* seeds, const int32_t* seed_labels,
+                           int32_t num_seeds, const float* depth_z, float depth_threshold, int32_t n_masks, int32_t* ids, uint8_t* masks,
+                           int32_t* report, void* stream) {
+    if (meanshift_args(c, "meanshift assign", batch, channels, num_seeds)) return -1;
+    if (meanshift_assign_args("meanshift assign", n_masks, depth_z, depth_threshold)) return -1;
+    if (!emb || !seeds || !seed_labels || !ids || !report || (n_masks > 0 && !masks)) return fail("meanshift assign: null tensor");
+    if (meanshift_ws(c)) return -1;
+    return launch_meanshift_assign(emb, seeds, seed_labels, depth_z, depth_threshold, batch, num_seeds, n_masks, c->cfg.height, c->cfg.width, ids,
+                                   masks, report, c->meanshift_ws, c->cfg.max_batch, (hipStream_t)stream);
+}
+
+int quber_meanshift_cluster(quber_ctx* c, const float* emb, int32_t batch, int32_t channels, const int32_t* first, int32_t num_seeds, float kappa,
+                            int32_t iters, float epsilon, const float* depth_z, float depth_threshold, int32_t n_masks, int32_t* indices,
+                            float* seeds, int32_t* seed_labels, int32_t* ids, uint8_t* masks, int32_t* report, void* stream) {
+    if (meanshift_args(c, "meanshift", batch, channels, num_seeds)) return -1;
+    if (meanshift_assign_args("meanshift", n_masks, depth_z, depth_threshold)) return -1;
+    if (iters < 0 || iters > 1000) return fail("meanshift: iters outside 0..1000");
+    if (!(kappa >= 0.f) || kappa > 64.f) return fail("meanshift: kappa outside 0..64");
+    if (!(epsilon >= 0.f)) return fail("meanshift: epsilon is negative or not a number");
+    if (!emb || !first || !indices || !seeds || !seed_labels || !ids || !report || (n_masks > 0 && !masks)) return fail("meanshift: null tensor");
+    for (const void* p : {(const void*)emb, (const void*)first, (const void*)indices, (const void*)seeds, (const void*)seed_labels, (const void*)ids,
+                          (const void*)report, (const void*)depth_z})
+        if ((uintptr_t)p & 3) return fail("meanshift: a 32-bit tensor that is not 4-byte aligned");
+    if (meanshift_ws(c)) return -1;
+    const int H = c->cfg.height, W = c->cfg.width, cap = c->cfg.max_batch;
+    hipStream_t st = (hipStream_t)stream;
+    if (launch_meanshift_seeds(emb, first, batch, num_seeds, H, W, indices, c->meanshift_ws, cap, st)) return -1;
+    if (launch_meanshift_climb(emb, indices, seeds, batch, num_seeds, H, W, kappa, iters, c->meanshift_ws, cap, st)) return -1;
+    if (launch_meanshift_link(seeds, batch, num_seeds, epsilon, seed_labels, st)) return -1;
+    return launch_meanshift_assign(emb, seeds, seed_labels, depth_z, depth_threshold, batch, num_seeds, n_masks, H, W, ids, masks, report,
+                                   c->meanshift_ws, cap, st);
 }
 
 // ---- zoom-in refinement: rois, crops, paste (zoom.hip); usable on a context without a network ----

@@ -377,6 +377,15 @@ int launch_mask_nms(const uint8_t* masks, const float* scores, int B, int N, int
                     int* ids, int* source, float* out_scores, int* report, void* ws, hipStream_t st);
 size_t mask_nms_ws_bytes(int B, int N, int H, int W);
 int mask_nms_max();
+// mean-shift clustering of an embedding map f32 [B][64][H][W] into masks (meanshift.hip), all on `st`; ws: meanshift_ws_bytes(cap_b >= B, H, W)
+// bytes.  S seeds <= 128 and <= H W; Z f32 [B][S][64]; N planes <= 254; depth_z f32 [B][H][W] or null (no depth filter)
+int launch_meanshift_seeds(const float* X, const int* first, int B, int S, int H, int W, int* idx, void* ws, int cap_b, hipStream_t st);
+int launch_meanshift_climb(const float* X, const int* idx, float* Z, int B, int S, int H, int W, float kappa, int iters, void* ws, int cap_b,
+                           hipStream_t st);
+int launch_meanshift_link(const float* Z, int B, int S, float eps, int* labels, hipStream_t st);
+int launch_meanshift_assign(const float* X, const float* Z, const int* seed_labels, const float* depth_z, float thresh, int B, int S, int N, int H,
+                            int W, int* ids, uint8_t* planes, int* report, void* ws, int cap_b, hipStream_t st);
+size_t meanshift_ws_bytes(int cap_b, int H, int W);
 // zoom-in refinement (zoom.hip): the gather / scatter between the two passes, all on `st`; ws: zoom_ws_bytes(cap_b >= B, H, W) bytes.
 // T slots <= cap_b * 254, 2 <= S <= 512, C crop-pass ids <= 254, max_inst 1..254.
 int launch_zoom_rois(const int* ids, int B, int n_ids, int H, int W, float padding, int* rois, void* ws, int cap_b, hipStream_t st);

@@ -539,6 +539,96 @@ class Engine:
                                                _ptr(out_scores), _ptr(report), _stream()))
         return {"masks": out, "ids": ids, "source": source, "scores": out_scores, "report": report}
 
+    # ---- mean-shift clustering of pixel embeddings (csrc/meanshift.hip; INTEGRATION.md "Initial masks from pixel embeddings") ----
+    def _ms_tensor(self, t, dtype, shape, what):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape), what
+        return t
+
+    def _ms_emb(self, emb):
+        assert emb.dtype == torch.float32 and emb.is_contiguous() and emb.dim() == 4 and emb.shape[2:] == (self.H, self.W)
+        return emb.shape[0], emb.shape[1]
+
+    def meanshift_seeds(self, emb, first, num_seeds=100, out=None):
+        """emb f32 [B,64,H,W], first i32 [B] (device) -> indices i32 [B,num_seeds]: the seeds picked farthest-first from `first`."""
+        B, C = self._ms_emb(emb)
+        assert first.dtype == torch.int32 and first.is_contiguous() and first.shape == (B,)
+        out = self._ms_tensor(out, torch.int32, (B, int(num_seeds)), "indices")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_meanshift_seeds(self.h, _ptr(emb), B, C, _ptr(first), int(num_seeds), _ptr(out), _stream()))
+        return out
+
+    def meanshift_climb(self, emb, seeds=None, indices=None, kappa=20.0, iters=10):
+        """emb f32 [B,64,H,W]; seeds f32 [B,S,64] climbed IN PLACE, or indices i32 [B,S]: the pixels to start from (then seeds may be
+        None or the tensor to write into) -> seeds: `iters` rounds of Z = normalize(exp(kappa Z X^T) X)."""
+        B, C = self._ms_emb(emb)
+        assert seeds is not None or indices is not None
+        S = indices.shape[1] if indices is not None else seeds.shape[1]
+        assert indices is None or (indices.dtype == torch.int32 and indices.is_contiguous() and indices.shape == (B, S))
+        seeds = self._ms_tensor(seeds, torch.float32, (B, S, 64), "seeds")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_meanshift_climb(self.h, _ptr(emb), B, C, _ptr(indices), S, float(kappa), int(iters), _ptr(seeds), _stream()))
+        return seeds
+
+    def meanshift_link(self, seeds, epsilon=0.04, out=None):
+        """seeds f32 [B,S,64] -> seed labels i32 [B,S]: the reference's connected_components over the seeds."""
+        B, S = seeds.shape[:2]
+        assert seeds.dtype == torch.float32 and seeds.is_contiguous() and seeds.shape == (B, S, 64)
+        out = self._ms_tensor(out, torch.int32, (B, S), "seed labels")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_meanshift_link(self.h, _ptr(seeds), B, S, float(epsilon), _ptr(out), _stream()))
+        return out
+
+    def meanshift_assign(self, emb, seeds, seed_labels, n_masks, depth_z=None, depth_threshold=None, ids=None, masks=None, report=None):
+        """Every pixel to its nearest seed's label, the largest cluster to 0, the depth filter (depth_z f32 [B,H,W] and a threshold, or
+        neither), the survivors numbered 1..count -> {"ids": i32 [B,H,W], "masks": u8 [B,n_masks,H,W] of 0 / 255, "report": i32 [B,4] =
+        count, clusters before the filter, dropped by depth, truncated}."""
+        B, C = self._ms_emb(emb)
+        S, N = seeds.shape[1], int(n_masks)
+        assert seeds.dtype == torch.float32 and seeds.is_contiguous() and seeds.shape == (B, S, 64)
+        assert seed_labels.dtype == torch.int32 and seed_labels.is_contiguous() and seed_labels.shape == (B, S)
+        assert (depth_z is None) == (depth_threshold is None), "the depth filter needs both the plane and the threshold"
+        assert depth_z is None or (depth_z.dtype == torch.float32 and depth_z.is_contiguous() and depth_z.shape == (B, self.H, self.W))
+        ids = self._ms_tensor(ids, torch.int32, (B, self.H, self.W), "ids")
+        masks = self._ms_tensor(masks, torch.uint8, (B, N, self.H, self.W), "masks")
+        report = self._ms_tensor(report, torch.int32, (B, 4), "report")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_meanshift_assign(self.h, _ptr(emb), B, C, _ptr(seeds), _ptr(seed_labels), S, _ptr(depth_z),
+                                                       float(depth_threshold or 0.0), N, _ptr(ids), _ptr(masks) if N else None, _ptr(report),
+                                                       _stream()))
+        return {"ids": ids, "masks": masks, "report": report}
+
+    def meanshift(self, emb, first, ms=None, n_masks=None, depth_z=None, out=None):
+        """The chain seeds -> climb -> link -> assign under `ms` (a meanshift.MeanShift; default: the reference's): emb f32 [B,64,H,W],
+        first i32 [B], depth_z f32 [B,H,W] (read only when ms.depth_threshold is set) -> {"indices": i32 [B,S], "seeds": f32 [B,S,64],
+        "seed_labels": i32 [B,S], "ids", "masks", "report" as meanshift_assign}.  out: such a dict to write into.  Nothing is copied to
+        the host; the first call on an engine allocates the workspace and cannot be captured into a graph."""
+        from .meanshift import MeanShift
+        ms = MeanShift() if ms is None else ms
+        B, C = self._ms_emb(emb)
+        S = ms.num_seeds
+        N = min(self.cap, 254) if n_masks is None else int(n_masks)
+        assert first.dtype == torch.int32 and first.is_contiguous() and first.shape == (B,)
+        if ms.depth_threshold is None:
+            depth_z = None
+        elif depth_z is None:
+            raise ValueError("cluster: depth_z is required when depth_threshold is set")
+        assert depth_z is None or (depth_z.dtype == torch.float32 and depth_z.is_contiguous() and depth_z.shape == (B, self.H, self.W))
+        o = dict(out or {})
+        o["indices"] = self._ms_tensor(o.get("indices"), torch.int32, (B, S), "indices")
+        o["seeds"] = self._ms_tensor(o.get("seeds"), torch.float32, (B, S, 64), "seeds")
+        o["seed_labels"] = self._ms_tensor(o.get("seed_labels"), torch.int32, (B, S), "seed labels")
+        o["ids"] = self._ms_tensor(o.get("ids"), torch.int32, (B, self.H, self.W), "ids")
+        o["masks"] = self._ms_tensor(o.get("masks"), torch.uint8, (B, N, self.H, self.W), "masks")
+        o["report"] = self._ms_tensor(o.get("report"), torch.int32, (B, 4), "report")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_meanshift_cluster(self.h, _ptr(emb), B, C, _ptr(first), S, ms.kappa, ms.iters, ms.epsilon, _ptr(depth_z),
+                                                        float(ms.depth_threshold or 0.0), N, _ptr(o["indices"]), _ptr(o["seeds"]),
+                                                        _ptr(o["seed_labels"]), _ptr(o["ids"]), _ptr(o["masks"]) if N else None, _ptr(o["report"]),
+                                                        _stream()))
+        return o
+
     # ---- zoom-in refinement: rois, crops, paste (csrc/zoom.hip; INTEGRATION.md "Zoom-in refinement") ----
     def zoom_rois(self, ids, n_ids, padding=0.25, out=None):
         """ids i32 [B,H,W] (device; compact: 0 none, 1..n_ids) -> rois i32 [B,n_ids,4] = (x0, y0, x1, y1) inclusive: the tight extent of

@@ -34,6 +34,15 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
     (``predict(..., mask_scores=)``, ``predict_batch(..., scores_list=)``, ``enqueue_batch(..., d_scores=)``).  Every dict gains
     ``nms_masks`` (u8 [count,H,W], 0 / 255, disjoint), ``nms_source`` (i64 [count]: the input index of each), ``nms_scores`` (f32 [count])
     and ``nms_report`` (i64 [2]: count, kept = survivors of the NMS before hidden ones drop out).  Default: none, today's keys.
+  * ``cluster=MeanShift(num_seeds=100, kappa=20, iters=10, alpha=0.02, depth_threshold=None, seed=0)``: there are no initial masks yet,
+    only the UCN base model's 64-channel pixel embeddings; its mean-shift clustering (``clustering_features``, ``filter_labels_depth``,
+    eval/base_model.py:622-840 and :34-47) makes the initial masks on the device (csrc/meanshift.hip; INTEGRATION.md "Initial masks from
+    pixel embeddings") and everything downstream - ``perturb``, the encoding, ``tta``, ``iterations``, ``track_initial`` - sees them as
+    THE initial masks.  ``predict`` / ``predict_batch`` then take ``embeddings=`` (f32 [64,H,W] per frame) in place of masks and an
+    optional ``depth_z=`` (f32 [H,W], required when ``depth_threshold`` is set).  Every dict gains ``cluster_masks`` (u8 [count,H,W], 0 /
+    255, disjoint), ``cluster_ids`` (i32 [H,W]), ``cluster_seeds`` (f32 [num_seeds,64]: the climbed modes) and ``cluster_report`` (i64
+    [4]: count, clusters before the depth filter, dropped by it, truncated).  Refused together with ``nms=``, with initial masks, and in
+    ``enqueue_batch`` / ``predict_stream``.  Default: none, today's keys, nothing launched or allocated.
   * ``zoom=ZoomIn(crop=224, padding=0.25, min_overlap=0.5)``: the second, zoomed-in pass of the reference's base models (``crop_rois`` /
     ``match_label_crop``, eval/base_model.py:843-961) without leaving the device (csrc/zoom.hip; INTEGRATION.md "Zoom-in refinement"):
     every instance of pass 1 - run with all configured options, through post-processing and ``cleanup`` - is cropped with a padded box,
@@ -63,6 +72,7 @@ import torch
 from .. import arch, config as qconfig, engine as qengine
 from ..cleanup import Cleanup
 from ..masknms import MaskNMS, check_scores
+from ..meanshift import CHANNELS as CLUSTER_CHANNELS, MeanShift
 from ..perturb import Perturb
 from ..structures import Boxes, Instances
 from ..losses import Losses
@@ -122,10 +132,11 @@ class RefineOptions:
     nms: MaskNMS = None               # scored, overlapping initial masks made disjoint on the device before anything else reads them
     zoom: ZoomIn = None               # a second pass on a padded, resized crop of every instance, pasted back on the device
     losses: Losses = None             # with a call's gt_labels=: the reference's training targets and loss dict of every frame, on the device
+    cluster: MeanShift = None         # the initial masks come from mean-shift clustering of pixel embeddings on the device, before anything else
 
     @classmethod
     def parse(cls, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
-              nms=None, zoom=None, losses=None):
+              nms=None, zoom=None, losses=None, cluster=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
         losses = Losses.parse(losses)
@@ -135,9 +146,11 @@ class RefineOptions:
             raise ValueError("losses: not with zoom= (the crop pass has no ground truth: left out)")
         if perturb is not None and not isinstance(perturb, Perturb):
             raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
-        zoom, nms = ZoomIn.parse(zoom), MaskNMS.parse(nms)
+        zoom, nms, cluster = ZoomIn.parse(zoom), MaskNMS.parse(nms), MeanShift.parse(cluster)
+        if cluster is not None and nms is not None:
+            raise ValueError("cluster: not with nms= (the clustering's masks are disjoint and have no scores)")
         return cls(bool(tta), bool(decode_errors), int(iterations), bool(until_converged), bool(track_initial), Cleanup.parse(cleanup),
-                   perturb, nms, zoom, losses)
+                   perturb, nms, zoom, losses, cluster)
 
     def for_crops(self):
         """The crop pass of zoom: the same tta, iterations and cleanup; nothing that concerns the caller's initial masks."""
@@ -163,6 +176,7 @@ class PassResult:
     err: dict = None
     pt: tuple = None
     nm: dict = None
+    cl: dict = None
     ls: dict = None
     masks: object = None
     slots: int = 0
@@ -230,12 +244,12 @@ class RefinerModel:
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
     def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False, iterations=1, until_converged=False,
-                 track_initial=False, cleanup=None, perturb=None, nms=None, zoom=None, losses=None, options=None):
-        # options: a RefineOptions in place of the ten keywords.  Its fields become plain attributes, which is what the code below
+                 track_initial=False, cleanup=None, perturb=None, nms=None, zoom=None, losses=None, cluster=None, options=None):
+        # options: a RefineOptions in place of the eleven keywords.  Its fields become plain attributes, which is what the code below
         # reads (a test and a tool switch model.decode_errors between calls)
         self.options = options or RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
                                                       track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom,
-                                                      losses=losses)
+                                                      losses=losses, cluster=cluster)
         vars(self).update(vars(self.options))
         self._zoom_model = None   # the crop pass: a RefinerModel on the same cfg and weights, built by the first zoomed call
         self.debug_zoom = None    # tests: a list that receives, per zoomed call, the inputs and outputs of every stage
@@ -310,6 +324,19 @@ class RefinerModel:
         nm = eng.mask_nms(src, d_scores, self.nms)
         src.copy_(nm["masks"])
         return nm
+
+    def cluster_masks(self, eng, d_masks, cluster_in, B):
+        """cluster: the first B frames of d_masks u8 [>= B,N,H,W] (device) are FILLED with the masks the mean-shift clustering makes of
+        cluster_in = (embeddings f32 [B,64,H,W], first seeds i32 [B], depth_z f32 [B,H,W] or None), all on the device (the kernels write
+        a fresh tensor, which is copied in and kept for the output dicts).  -> what Engine.meanshift returns, or None."""
+        if self.cluster is None:
+            return None
+        if cluster_in is None:
+            raise ValueError("cluster: this call path has no embeddings (predict and predict_batch take embeddings=)")
+        emb, first, z = cluster_in
+        cl = eng.meanshift(emb, first, self.cluster, d_masks.shape[1], z)
+        d_masks[:B].copy_(cl["masks"])
+        return cl
 
     def perturb_masks(self, eng, d_masks, B):
         """perturb: the first B frames of d_masks u8 [>= B,N,H,W] (device) are replaced by their perturbed versions, in place as far as
@@ -449,14 +476,15 @@ class RefinerModel:
             explicit = eng.error_maps(init, gt_masks)
         return {"rec": eng.losses(logits, tg["targets"], explicit, self.losses, heads=heads), "targets": tg, "heads": heads, "explicit": explicit}
 
-    def device_pass(self, eng, bgr, depth, masks, scores, B, *, may_stop, bufs=None, own=None, slots=None, gt=None):
-        """Enqueues nms -> perturb -> encode (tta: mirror, encode) -> forward -> postprocess -> refine -> track -> decode for B frames on
-        the current stream -> PassResult.  bgr / depth (or None) u8 [f*B,H,W,3] and masks u8 [f*B,N,H,W] on the device, f = 2 under tta
+    def device_pass(self, eng, bgr, depth, masks, scores, B, *, may_stop, bufs=None, own=None, slots=None, gt=None, cluster_in=None):
+        """Enqueues cluster (cluster_in: see cluster_masks) -> nms -> perturb -> encode (tta: mirror, encode) -> forward -> postprocess ->
+        refine -> track -> decode for B frames on the current stream -> PassResult.  bgr / depth (or None) u8 [f*B,H,W,3] and masks u8 [f*B,N,H,W] on the device, f = 2 under tta
         with the frames in the first halves; scores f32 [B,N] (required with nms).  Nothing is read back unless may_stop and
         until_converged (refine()).  bufs: predict_one's _FrameStaging - its offsets, post tables, iteration buffers and overlap tables
         are written instead of fresh tensors.  own: see PassResult; default all N rows.  slots (the stream): the first `slots` masks
         of every frame are extracted between track and decode, where the stream has always launched that."""
         N = masks.shape[1]
+        cl = self.cluster_masks(eng, masks, cluster_in, B)
         nm = self.nms_masks(eng, masks, scores, B)
         pt = self.perturb_masks(eng, masks, B)            # before the mirror, the encoding and everything else that reads the masks
         offsets = bufs.offsets if bufs is not None else None
@@ -468,7 +496,7 @@ class RefinerModel:
         logits, post, it = self.refine(eng, bgr, depth, logits, post, B, may_stop, bufs.iter_bufs if bufs is not None else None)
         d_masks = masks[:B]
         ov = self.track(eng, d_masks, post, it, (bufs.overlap[0][:, :N], bufs.overlap[1]) if bufs is not None and self.track_initial else None)
-        rec = PassResult(eng, B, logits, post, d_masks=d_masks, own=[N] * B if own is None else own, it=it, ov=ov, pt=pt, nm=nm)
+        rec = PassResult(eng, B, logits, post, d_masks=d_masks, own=[N] * B if own is None else own, it=it, ov=ov, pt=pt, nm=nm, cl=cl)
         if slots is not None:
             rec.slots = min(max(1, slots), eng.cap)
             rec.masks = eng.extract_masks(post, rec.slots)
@@ -564,6 +592,10 @@ class RefinerModel:
         if nm is not None:
             r["nms_masks"], r["nms_source"], r["nms_scores"] = nm["masks"][b, :n], nm["source"][b, :n].to(torch.int64), nm["scores"][b, :n]
             r["nms_report"] = nm["report"][b, :2].to(torch.int64)
+        if rec.cl is not None:
+            cl = rec.cl
+            r["cluster_masks"], r["cluster_ids"], r["cluster_seeds"] = cl["masks"][b, :n], cl["ids"][b], cl["seeds"][b]
+            r["cluster_report"] = cl["report"][b].to(torch.int64)
         if pt is not None:
             r["perturbed_masks"], r["perturb_report"] = pt[0][b, :n], pt[1][b, :n].to(torch.int64)
         if it is not None:
@@ -596,6 +628,8 @@ class RefinerModel:
         eng, post, B = rec.eng, rec.post, rec.B
         if rec.nm is not None:
             rec.own = [int(c) for c in rec.nm["report"][:, 0].cpu().numpy()]
+        if rec.cl is not None:
+            rec.own = [int(c) for c in rec.cl["report"][:, 0].cpu().numpy()]
         count = post["count"].cpu().numpy()
         conv = rec.it["conv"].cpu().numpy() if rec.it is not None else np.zeros((B,), np.int32)
         if rec.ls is not None:
@@ -619,6 +653,8 @@ class RefinerModel:
         a pinned word and exactly `count` masks are extracted."""
         if self.zoom is not None:
             raise ValueError("zoom: predict_one has no zoomed form; MaskRefinerPredictor.predict takes the batched path")
+        if self.cluster is not None:
+            raise ValueError("cluster: predict_one has no clustering form; MaskRefinerPredictor.predict takes the batched path")
         H, W = bgr.shape[:2]
         n = int(masks.shape[0])
         f = 2 if self.tta else 1                     # frames on the device: the frame [and its mirror]
@@ -683,6 +719,8 @@ class RefinerModel:
             raise ValueError("nms: d_scores is required when nms= is set")
         if self.zoom is not None:
             raise ValueError("zoom: enqueue_batch / predict_stream have no zoomed form; use predict or predict_batch")
+        if self.cluster is not None:
+            raise ValueError("cluster: enqueue_batch / predict_stream have no clustering form; use predict or predict_batch")
         if halves:
             assert self.tta and d_bgr.shape[0] % 2 == 0
         B, H, W = d_bgr.shape[:3]
@@ -805,11 +843,11 @@ class RefinerModel:
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
                  seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False,
-                 cleanup=None, perturb=None, nms=None, zoom=None, losses=None, options=None):
+                 cleanup=None, perturb=None, nms=None, zoom=None, losses=None, cluster=None, options=None):
         # the options (module docstring), checked before anything is loaded; options: a RefineOptions in their place
         self.options = options or RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
                                                       track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom,
-                                                      losses=losses)
+                                                      losses=losses, cluster=cluster)
         vars(self).update(vars(self.options))
         if config_file is None:
             self.cfg = qconfig.canonical_cfg()
@@ -840,8 +878,17 @@ class MaskRefinerPredictor:
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
     # -- reference signature (predictor.py:287) --
-    def predict(self, rgb_img, depth_img=None, perturbed_masks=None, mask_scores=None, gt_labels=None):
+    def predict(self, rgb_img, depth_img=None, perturbed_masks=None, mask_scores=None, gt_labels=None, embeddings=None, depth_z=None):
         # gt_labels (with losses=): the frame's ground-truth label map, integer [H,W], 0 = none, 1..n; the dict then carries `losses`
+        # embeddings (with cluster=, in place of perturbed_masks): f32 [64,H,W]; depth_z: f32 [H,W], the depth filter's plane
+        if self.cluster is not None or embeddings is not None or depth_z is not None:
+            if perturbed_masks is not None:
+                raise ValueError("cluster: embeddings= takes the place of the initial masks; both were given")
+            if mask_scores is not None:
+                raise ValueError("cluster: the clustering's masks have no scores; mask_scores= was given")
+            return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], None,
+                                      gt_labels=None if gt_labels is None else [gt_labels],
+                                      embeddings=None if embeddings is None else [embeddings], depth_z=None if depth_z is None else [depth_z])
         masks = np.zeros((0,) + rgb_img.shape[:2], np.uint8) if perturbed_masks is None else np.asarray(perturbed_masks)
         gts = None if gt_labels is None else [gt_labels]
         if self.nms is not None:                          # the general path: how many masks there are is known on the device only
@@ -858,10 +905,42 @@ class MaskRefinerPredictor:
             depth_img = None
         return [self.model.predict_one(rgb_img, depth_img, mask_bytes(masks, self.perturb is not None), gt_labels)]
 
-    def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None, gt_labels=None):
+    def _cluster_inputs(self, B, H, W, masks_list, scores_list, embeddings, depth_z):
+        """cluster=: the checked host arrays (embeddings f32 [B,64,H,W], depth_z f32 [B,H,W] or None) of a call, before anything is
+        uploaded or launched; None without cluster=.  The first seeds are drawn by the caller once every other check has passed."""
+        ms = self.cluster
+        if ms is None:
+            if embeddings is not None or depth_z is not None:
+                raise ValueError("embeddings= / depth_z= need cluster= (a quber_amd.meanshift.MeanShift)")
+            return None
+        if masks_list is not None:
+            raise ValueError("cluster: embeddings= takes the place of the initial masks; both were given")
+        if scores_list is not None:
+            raise ValueError("cluster: the clustering's masks have no scores; scores_list= was given")
+        if embeddings is None or len(embeddings) != B:
+            raise ValueError("cluster: the embeddings of every frame are required when cluster= is set")
+        emb = np.ascontiguousarray(np.stack([np.asarray(e) for e in embeddings]), dtype=np.float32)
+        if emb.shape != (B, CLUSTER_CHANNELS, H, W):
+            raise ValueError(f"cluster: embeddings of shape {emb.shape[1:]} per frame, expected ({CLUSTER_CHANNELS}, {H}, {W})")
+        if ms.num_seeds > H * W:
+            raise ValueError("cluster: more seeds than the frame has pixels")
+        z = None
+        if ms.depth_threshold is not None:
+            if depth_z is None or len(depth_z) != B:
+                raise ValueError("cluster: depth_z of every frame is required when depth_threshold is set")
+            z = np.ascontiguousarray(np.stack([np.asarray(d) for d in depth_z]), dtype=np.float32)
+            if z.shape != (B, H, W):
+                raise ValueError(f"cluster: depth_z of shape {z.shape[1:]} per frame, expected ({H}, {W})")
+        return emb, z
+
+    def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None, gt_labels=None, embeddings=None, depth_z=None):
         """rgb_imgs/depth_imgs: u8 [B,H,W,3] arrays; masks_list: B arrays u8/bool [N_b,H,W]; scores_list (required with nms=): B arrays
-        [N_b] of finite scores; gt_labels (with losses=): the B ground-truth label maps, integer [B,H,W] or a list.  -> list of B dicts."""
+        [N_b] of finite scores; gt_labels (with losses=): the B ground-truth label maps, integer [B,H,W] or a list.  With cluster=:
+        masks_list is None, embeddings: B arrays f32 [64,H,W], depth_z: B arrays f32 [H,W] (with depth_threshold).  -> list of B dicts."""
         B, H, W = rgb_imgs.shape[:3]
+        cluster_in = self._cluster_inputs(B, H, W, masks_list, scores_list, embeddings, depth_z)
+        # rows of the mask tensor per frame; with cluster=: one plane per cluster there can be - the seeds' labels but the largest
+        counts = [len(m) for m in masks_list] if cluster_in is None else [min(max(self.cluster.num_seeds - 1, 1), 254)] * B
         sc = None
         if self.nms is not None:                          # checked before anything is uploaded or launched
             if scores_list is None or len(scores_list) != len(masks_list):
@@ -875,9 +954,9 @@ class MaskRefinerPredictor:
             rgb_imgs, depth_imgs = depth_imgs, None
         elif not self.depth_on:
             depth_imgs = None
-        n = max([len(m) for m in masks_list] + [1])
-        mk = np.zeros((B, n, H, W), np.uint8)
-        for b, m in enumerate(masks_list):
+        n = max(counts + [1])
+        mk = np.zeros((B, n, H, W) if cluster_in is None else (0,), np.uint8)
+        for b, m in enumerate(masks_list if cluster_in is None else ()):
             if len(m):
                 mk[b, :len(m)] = mask_bytes(m, self.perturb is not None or self.nms is not None, binarise=True)
         model = self.model
@@ -888,7 +967,11 @@ class MaskRefinerPredictor:
         bgr[:B].copy_(torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)))
         if depth is not None:
             depth[:B].copy_(torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)))
-        d_masks[:B].copy_(torch.from_numpy(mk))
+        if cluster_in is None:
+            d_masks[:B].copy_(torch.from_numpy(mk))
+        else:                                             # the first seeds: drawn last, so that a call that raised above has drawn nothing
+            cluster_in = (cluster_in[0], self.cluster.first_seeds(B, H * W), cluster_in[1])
+            cluster_in = tuple(None if a is None else torch.from_numpy(a).to(self.device) for a in cluster_in)
         rec = model.device_pass(eng, bgr, depth, d_masks, None if sc is None else torch.from_numpy(sc).to(self.device), B, may_stop=True,
-                                own=[len(m) for m in masks_list], gt=gt)
+                                own=counts, gt=gt, cluster_in=cluster_in)
         return model.results(rec, (bgr, depth))
