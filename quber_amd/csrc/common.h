@@ -229,7 +229,12 @@ struct TuneScope {
 };
 bool tuning_set(Tuning& t, int key, int value);   // false: not a key of Tuning
 // persistent launch of the implicit GEMM (conv_persist.hip); p.mtiles / ntiles / vec_out filled in by the caller
-template <int BM, int BN, int WM, int WN> int launch_conv_persistent(ConvP p, int G, int bpc, hipStream_t st, ConvRoute* dry = nullptr);
+template <int BM, int BN, int WM, int WN> int launch_conv_persistent(ConvP p, int G, int bpc, hipStream_t st);
+struct PkGrid {      // the arguments of conv_persistent_segments: tiles over all groups, blocks launched, K-slices per tile, shortest K share (0: remainder tiles whole)
+    int tiles, blocks, nk, min_share;
+    void report(ConvRoute* r) const { r->tiles = tiles; r->blocks = blocks; r->nk = nk; r->min_share = min_share; }
+};
+PkGrid conv_persistent_grid(const ConvP& p, int G, int bpc);
 size_t conv_persistent_ws_floats(int BM, int BN, int bpc);
 bool conv_persistent_ok(const ConvP& p);
 int conv_persistent_segments(int T, int P, int nk, int min_slices, int bid, int* out4, int cap);

@@ -1056,16 +1056,26 @@ static bool igemm_gn_sep(const ConvP& p, int BM) {
     return p.gn_sum && !(p.vec_out && p.gn_cpg % 4 == 0 && p.gn_groups <= 32 && p.ohw >= BM && p.ohw >= 8);
 }
 
-// fills the route of a dry run (ConvRoute, common.h); false = a real launch
-static bool routed(ConvRoute* dry, int kernel, bool sums, bool gn_sep, int BM, int BN, int S, int tail_shift) {
-    if (!dry) return false;
-    dry->kernel = kernel; dry->sums = !sums ? 0 : gn_sep ? ROUTE_SEPARATE : kernel;
-    dry->BM = BM; dry->BN = BN; dry->S = S; dry->tail_shift = tail_shift;
-    return true;
-}
+// Everything decided about one launch, as a value: decide() fills it without a HIP call, execute() launches what it says and nothing else, and a
+// dry run copies it into the ConvRoute - the route reported is the record the launch executes.
+struct IgemmPlan {
+    ConvP p;                     // as the kernel receives it
+    int kernel;                  // ROUTE_TILE: one tile per block, ROUTE_SPLITK: split-K - p.tail_shift > 0: the split tail -, ROUTE_PERSISTENT
+    int mode, dt;                // conv_igemm_f32<MODE, DT, LEAN> (the persistent kernel's are selected from p by launch_conv_persistent)
+    bool lean;
+    int S;                       // K partitions of the route = partial tiles splitk_reduce_kernel sums (split tail: pieces per remaining tile); 1: no reduce pass
+    dim3 grid;
+    int bpc;                     // persistent launch: resident blocks per CU
+    bool gn_sep;                 // the GroupNorm sums by a separate pass over the output, into gn_sum (p.gn_sum is null then)
+    double* gn_sum;              // the caller's sums
+    const char* tag;             // stage profile of the convolution kernel
+    double bytes, flops;
+};
 
-template <int BM, int BN, int WM, int WN>
-static int run(ConvP p, int G, int S, hipStream_t st, ConvRoute* dry) {
+// tile shape BM x BN and S K partitions proposed by the tile rule (tile_rule below)
+static IgemmPlan decide(const ConvP& p0, int G, int BM, int BN, int S) {
+    IgemmPlan d{p0};
+    ConvP& p = d.p;
     p.mtiles = (p.M + BM - 1) / BM;
     p.ntiles = (p.Cout + BN - 1) / BN;
     p.vec_out = (p.Cout % 4 == 0) && (p.out_cs % 4 == 0) && (((uintptr_t)p.out & 15) == 0) && (p.out_gs % 4 == 0) &&
@@ -1075,15 +1085,9 @@ static int run(ConvP p, int G, int S, hipStream_t st, ConvRoute* dry) {
     if (p.es == 2 && p.vec_out && p.Cout % 8 == 0 && p.out_cs % 8 == 0 && p.out_gs % 8 == 0 && !p.prelu &&
         (!p.res || (p.res_cs % 8 == 0 && p.res_gs % 8 == 0)) && (!p.scale || (p.ss_gs % 8 == 0 && (((uintptr_t)p.scale & 31) == 0))))
         p.vec_out = 2;        // fp16 tensors: 16-byte accesses of 8 channels
-    const bool gn_sep = igemm_gn_sep(p, BM);
-    double* const gn_sum = p.gn_sum;
-    if (gn_sep) p.gn_sum = nullptr;
-    auto gn_separate = [&]() {
-        if (!gn_sep) return 0;
-        View o;
-        o.p = p.out; o.B = p.B; o.H = p.OH; o.W = p.OW; o.C = p.Cout; o.cs = p.out_cs; o.gs = p.out_gs; o.es = p.es;
-        return launch_gn_stats(o, p.B, G, p.gn_groups, gn_sum, st, false);
-    };
+    d.gn_sum = p.gn_sum;
+    d.gn_sep = igemm_gn_sep(p, BM);
+    if (d.gn_sep) p.gn_sum = nullptr;
     const int nk = p.Kpad / BK;
     if (p.ws && tune().force_split > 0) S = tune().force_split;
     if (!p.ws || S < 1 || p.es == 2) S = 1;
@@ -1096,71 +1100,43 @@ static int run(ConvP p, int G, int S, hipStream_t st, ConvRoute* dry) {
     p.ws_row0 = 0;
     p.nfull = p.mtiles * p.ntiles;
     p.tail_shift = 0;
-    const dim3 block(WM * WN * 64);
     // stage profile: algorithmic traffic = the input tensor, the weights and the output (+ residual) once each
     // (fp16 data path: Cin / K are in 4-byte units here - two halfs each - so the input and weight bytes come out right)
     const double out_bytes = (double)p.es * G * (double)p.M * p.Cout;
-    const double conv_bytes = 4.0 * G * ((double)p.B * p.H * p.W * p.Cin + (double)p.Cout * p.K) + out_bytes * (p.res ? 2.0 : 1.0);
-    const double conv_flops = 2.0 * G * (double)p.M * p.K * p.Cout * (p.es == 2 ? 2.0 : 1.0);
-    const char* tag = p.tag ? p.tag : "conv_gemm";
-    // a launch of the bf16x3 mode that keeps the exact fp32 MFMA kernel is profiled under its own stage, so that the
-    // bench prices each matrix pipe with the work it actually executed
-    auto exact_fallback = [&]() { p.bf16 = 0; tag = "conv_gemm_f32pipe"; };
-    auto reduce = [&](int parts) {
-        const long MN = (long)p.ws_rows * p.Cout;
-        ProfScope prof("splitk_reduce", 4.0 * G * (double)MN * (parts + 1.0), 0.0, st);
-        const int V = p.vec_out ? 4 : 1;
-        long chunk = (MN + 2047) / 2048;                       // at most 2048 blocks ...
-        if (chunk < 256L * V * 4) chunk = 256L * V * 4;        // ... of at least 4 elements-vectors per thread
-        chunk = (chunk + V - 1) / V * V;
-        if (p.gn_sum && chunk / p.Cout + 2 > p.ohw) chunk = (long)(p.ohw - 2) * p.Cout / V * V;   // at most two images per block
-        const int blocks = (int)((MN + chunk - 1) / chunk);
-        if (p.vec_out)
-            hipLaunchKernelGGL(splitk_reduce_kernel<4>, dim3(blocks, G), dim3(256), 0, st, p, parts, G, chunk);
-        else
-            hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3(blocks, G), dim3(256), 0, st, p, parts, G, chunk);
-    };
+    d.bytes = 4.0 * G * ((double)p.B * p.H * p.W * p.Cin + (double)p.Cout * p.K) + out_bytes * (p.res ? 2.0 : 1.0);
+    d.flops = 2.0 * G * (double)p.M * p.K * p.Cout * (p.es == 2 ? 2.0 : 1.0);
+    d.tag = p.tag ? p.tag : "conv_gemm";
     const bool skip = BM != 256 && p.skip_rows && p.kmode == 0 && p.kh > 1 && p.Cin % BK == 0 && p.K == p.Kpad && p.ohw > 0;
-    if (p.es == 2) {        // fp16 data path: one K pass (the loop is 16x shorter than the fp32 one), padded filter rows skipped; never
-                            // persistent (below), split or on the fp32 pipe
-                            // (128x256 tiles - wave tiles of 64x128, 25 % fewer LDS fragment reads per MFMA - measured level with
-                            // 128x128: 15.84 against 15.79 ms of convolutions, profiles/r10b_h16_loader.md)
-        ProfScope prof(tag, conv_bytes, conv_flops, st);
-        const dim3 grid(p.mtiles * p.ntiles, 1, G);
-        const bool lean = lean_loader(p);
-        if (routed(dry, ROUTE_TILE, gn_sum, gn_sep, BM, BN, 1, 0)) return 0;
-        if (skip) launch_igemm<BM, BN, WM, WN, 3, 4>(lean, grid, block, st, p);
-        else launch_igemm<BM, BN, WM, WN, 0, 4>(lean, grid, block, st, p);
-        QB_CHECK(hipGetLastError());
-        return gn_separate();
-    }
-    const bool lean = lean_loader(p);
+    d.lean = lean_loader(p);
+    // bf16x3 pays where the matrix pipe is the limit.  The HBM-bound short-K launches on 64x64 tiles (bottleneck conv3 +
+    // residual) and the 32-column head layers on 256x32 tiles lose occupancy to its three LDS planes and gain nothing
+    // (profiles/r02j_conv_layers_dtype{0,3}.md): they keep the exact fp32 MFMA kernel, which is at least as accurate.
+    // (so does the dilated layer that skips padded filter rows on 64x64 tiles - ASPP d = 18 on a 30-row map: 1.49 ms as bf16x3 against 1.03 ms
+    //  exact at batch 16, profiles/r12_final_conv_layers_dtype{0,3}.md)
+    // Such a launch is profiled under its own stage, so that the bench prices each matrix pipe with the work it actually executed.
+    // (Taken here, ahead of every form, once.  It used to be taken inside the persistent gate - without `skip`, which that gate excludes - and again
+    // in front of the one-tile / split-K launch.  The same launches get it: nothing between here and those two places tells bf16 3 from 0 -
+    // conv_persistent_ok admits both alike - except the split tail's `!p.bf16`, and that gate wants 128-row tiles, which this rule never touches.)
+    if (p.bf16 == 3 && (BM == 256 || (BM == 64 && (nk <= 8 || skip)))) { p.bf16 = 0; d.tag = "conv_gemm_f32pipe"; }
+    const int BPC = igemm_occupancy(BM, BN);
+    const long slots = 256L * BPC, tiles = (long)p.mtiles * p.ntiles, blocks_all = tiles * G;
     // Persistent launch (conv_persist.hip): one block per resident slot walks whole tiles and an equal share of the
     // K-slices of the remainder
     // (launches of a few dozen tiles - small batches - keep the one-tile-per-block kernel and its fitted split-K model:
     // sharing every tile's K between all resident blocks writes more partial tiles than that model's 2-8 partitions)
     // (fp16 data path: only the fused projection shortcuts - launch_conv_dual - go persistent: with 16x the matrix rate the
     // persistent kernel's per-slice tap arithmetic costs the 3x3 layers 30 %, profiles/r04a_f16_persistent_all_rejected.md)
+    d.bpc = BM == 64 ? 5 : 2;          // conv_persist.hip: pk_occupancy() of the fp32 / bf16x3 kernels
     if (tune().persist && p.es != 2 && ((BM == 128 && BN == 128) || (tune().persist == 2 && (BM == BN || BM == 256))) && BN <= 128 && !skip && p.ws && conv_persistent_ok(p) &&
-        (long)p.mtiles * p.ntiles * G >= tune().persist_min_tiles &&
-        ((long)p.mtiles * p.ntiles * G >= 256L * (p.es == 2 ? 3 : BM == 64 ? 5 : 2) || nk >= tune().persist_min_nk)) {      // several tiles per block, or K worth sharing
-        if (p.bf16 == 3 && (BM == 256 || (BM == 64 && nk <= 8))) exact_fallback();
-        const int bpc = p.es == 2 ? 3 : BM == 64 ? 5 : 2;          // conv_persist.hip: pk_occupancy()
-        if (p.ws_floats >= conv_persistent_ws_floats(BM, BN, bpc)) {
-            (void)routed(dry, ROUTE_PERSISTENT, gn_sum, gn_sep, BM, BN, 1, 0);
-            {
-                ProfScope prof(tag, conv_bytes, conv_flops, st);
-                int rc = 0;
-                if constexpr (BM == BN || BM == 256) rc = launch_conv_persistent<BM, BN, WM, WN>(p, G, bpc, st, dry);
-                if (rc) return rc;
-            }
-            return dry ? 0 : gn_separate();
-        }
+        blocks_all >= tune().persist_min_tiles &&
+        (blocks_all >= 256L * d.bpc || nk >= tune().persist_min_nk) &&      // several tiles per block, or K worth sharing
+        p.ws_floats >= conv_persistent_ws_floats(BM, BN, d.bpc)) {
+        d.kernel = ROUTE_PERSISTENT;
+        d.S = 1;
+        return d;
     }
     // Split tail: with more than one round of tiles, cut the tiles of the ragged last round into 2^shift K-pieces that
     // together fill about one more (short) round; taken when the model prices it below the launch chosen so far.
-    constexpr int BPC = igemm_occupancy(BM, BN);
-    const long slots = 256L * BPC, tiles = (long)p.mtiles * p.ntiles, blocks_all = tiles * G;
     if (p.ws && !p.bf16 && tune().tail_split && tune().force_split == 0 && BM == 128 && blocks_all > slots && nk >= 32) {
         const long nfull = (blocks_all / slots) * slots / G / p.ntiles * p.ntiles;    // per group, whole tile rows
         const long rem = tiles - nfull;
@@ -1179,45 +1155,28 @@ static int run(ConvP p, int G, int S, hipStream_t st, ConvRoute* dry) {
                 p.ws_row0 = (int)row0;
                 p.ws_rows = p.M - (int)row0;
                 // every piece owns at least one K-slice: (2^shift - 1) * kchunk < nk because nk >= 8 * 2^shift
-                if (routed(dry, ROUTE_SPLITK, gn_sum, gn_sep, BM, BN, 1 << shift, shift)) return 0;
-                {
-                    ProfScope prof(tag, conv_bytes, conv_flops, st);
-                    launch_igemm<BM, BN, WM, WN, 2, 0>(lean, dim3((unsigned)(nfull + (rem << shift)), 1, G), block, st, p);
-                }
-                reduce(1 << shift);
-                QB_CHECK(hipGetLastError());
-                return gn_separate();
+                d.kernel = ROUTE_SPLITK;
+                d.S = 1 << shift;
+                d.mode = 2;         // DT 0: the gate admits exact fp32 only
+                d.grid = dim3((unsigned)(nfull + (rem << shift)), 1, G);
+                return d;
             }
         }
     }
-    // bf16x3 pays where the matrix pipe is the limit.  The HBM-bound short-K launches on 64x64 tiles (bottleneck conv3 +
-    // residual) and the 32-column head layers on 256x32 tiles lose occupancy to its three LDS planes and gain nothing
-    // (profiles/r02j_conv_layers_dtype{0,3}.md): they keep the exact fp32 MFMA kernel, which is at least as accurate.
-    // (so does the dilated layer that skips padded filter rows on 64x64 tiles - ASPP d = 18 on a 30-row map: 1.49 ms as bf16x3 against 1.03 ms
-    //  exact at batch 16, profiles/r12_final_conv_layers_dtype{0,3}.md)
-    if (p.bf16 == 3 && (BM == 256 || (BM == 64 && (nk <= 8 || skip)))) exact_fallback();
-    if (routed(dry, S > 1 ? ROUTE_SPLITK : ROUTE_TILE, gn_sum, gn_sep, BM, BN, S, 0)) return 0;
-    if (p.bf16) {
-        {
-            ProfScope prof(tag, conv_bytes, conv_flops, st);
-            const dim3 grid(p.mtiles * p.ntiles, S, G);
-            if (p.bf16 == 3) {
-                if (S > 1) launch_igemm<BM, BN, WM, WN, 1, 3>(lean, grid, block, st, p);
-                else launch_igemm<BM, BN, WM, WN, 0, 3>(lean, grid, block, st, p);
-            } else if (p.bf16 == 2) {
-                if (S > 1) launch_igemm<BM, BN, WM, WN, 1, 2>(lean, grid, block, st, p);
-                else launch_igemm<BM, BN, WM, WN, 0, 2>(lean, grid, block, st, p);
-            } else {
-                if (S > 1) launch_igemm<BM, BN, WM, WN, 1, 1>(lean, grid, block, st, p);
-                else launch_igemm<BM, BN, WM, WN, 0, 1>(lean, grid, block, st, p);
-            }
-        }
-        if (S > 1) reduce(S);
-        QB_CHECK(hipGetLastError());
-        return gn_separate();
-    }
+    // One tile per block, S K partitions.
+    // fp16 data path (DT 4): one K pass (the loop is 16x shorter than the fp32 one), padded filter rows skipped; never persistent (above), split
+    // (S = 1) or on the fp32 pipe
+    // (128x256 tiles - wave tiles of 64x128, 25 % fewer LDS fragment reads per MFMA - measured level with
+    // 128x128: 15.84 against 15.79 ms of convolutions, profiles/r10b_h16_loader.md)
+    d.kernel = S > 1 ? ROUTE_SPLITK : ROUTE_TILE;
+    d.S = S;
+    d.grid = dim3(p.mtiles * p.ntiles, S, G);
+    d.dt = p.es == 2 ? 4 : p.bf16;
+    const bool rows = skip && (d.dt == 4 || d.dt == 0);       // the bf16 / fp16-operand / bf16x3 kernels multiply every filter row
+    d.mode = S > 1 ? (rows ? 4 : 1) : (rows ? 3 : 0);
+    if (d.dt) return d;
     p.zones = 0;
-    if (skip && tune().zone_cols && lean && BM == 64 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad == p.dil && p.OH == p.H && p.OW == p.W) {
+    if (skip && tune().zone_cols && d.lean && BM == 64 && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad == p.dil && p.OH == p.H && p.OW == p.W) {
         // filter columns skipped as well (ConvP::zones): 3x3, stride 1, pad = dil, the LEAN kernel on 64-row tiles (a 128-row tile of an
         // 18-column zone spans 7 map rows and loses in filter rows what it gains in columns), at least a quarter of the columns without
         // one of their taps.  The split-K form too: its partial tiles go to the workspace in GEMM row order, the reduce kernel maps them.
@@ -1230,22 +1189,107 @@ static int run(ConvP p, int G, int S, hipStream_t st, ConvRoute* dry) {
         // - two frames, or one of 45 x 80 - the shorter average wins: 210 -> 186 us, 318 -> 283 us)
         if (S > 1 && p.mtiles < 32) p.zones = 0;
     }
-    if (S > 1) {
-        {
-            ProfScope prof(tag, conv_bytes, conv_flops, st);
-            if (skip) launch_igemm<BM, BN, WM, WN, 4, 0>(lean, dim3(p.mtiles * p.ntiles, S, G), block, st, p);
-            else launch_igemm<BM, BN, WM, WN, 1, 0>(lean, dim3(p.mtiles * p.ntiles, S, G), block, st, p);
-        }
-        reduce(S);
-    } else {
-        ProfScope prof(tag, conv_bytes, conv_flops, st);
-        if (skip) launch_igemm<BM, BN, WM, WN, 3, 0>(lean, dim3(p.mtiles * p.ntiles, 1, G), block, st, p);
-        else launch_igemm<BM, BN, WM, WN, 0, 0>(lean, dim3(p.mtiles * p.ntiles, 1, G), block, st, p);
-    }
-    QB_CHECK(hipGetLastError());
-    return gn_separate();
+    return d;
 }
 
+static void launch_splitk_reduce(const ConvP& p, int parts, int G, hipStream_t st) {
+    const long MN = (long)p.ws_rows * p.Cout;
+    ProfScope prof("splitk_reduce", 4.0 * G * (double)MN * (parts + 1.0), 0.0, st);
+    const int V = p.vec_out ? 4 : 1;
+    long chunk = (MN + 2047) / 2048;                       // at most 2048 blocks ...
+    if (chunk < 256L * V * 4) chunk = 256L * V * 4;        // ... of at least 4 elements-vectors per thread
+    chunk = (chunk + V - 1) / V * V;
+    if (p.gn_sum && chunk / p.Cout + 2 > p.ohw) chunk = (long)(p.ohw - 2) * p.Cout / V * V;   // at most two images per block
+    const int blocks = (int)((MN + chunk - 1) / chunk);
+    if (p.vec_out)
+        hipLaunchKernelGGL(splitk_reduce_kernel<4>, dim3(blocks, G), dim3(256), 0, st, p, parts, G, chunk);
+    else
+        hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3(blocks, G), dim3(256), 0, st, p, parts, G, chunk);
+}
+
+// launches what the record says: the convolution kernel under its stage, the reduce pass under its own (scopes do not nest), the separate sums
+template <int BM, int BN, int WM, int WN>
+static int execute(const IgemmPlan& d, int G, hipStream_t st) {
+    const ConvP& p = d.p;
+    if (d.kernel == ROUTE_PERSISTENT) {
+        if constexpr (BM == BN || BM == 256) {        // the tile shapes conv_persist.hip instantiates
+            ProfScope prof(d.tag, d.bytes, d.flops, st);
+            const int rc = launch_conv_persistent<BM, BN, WM, WN>(p, G, d.bpc, st);
+            if (rc) return rc;
+        }
+    } else {
+        {
+            ProfScope prof(d.tag, d.bytes, d.flops, st);
+            const dim3 block(WM * WN * 64);
+#define IGEMM_CASE(MODE, DT) case DT * 8 + MODE: launch_igemm<BM, BN, WM, WN, MODE, DT>(d.lean, d.grid, block, st, p); break;
+            switch (d.dt * 8 + d.mode) {
+                IGEMM_CASE(3, 4) IGEMM_CASE(0, 4)
+                IGEMM_CASE(2, 0)
+                IGEMM_CASE(1, 3) IGEMM_CASE(0, 3) IGEMM_CASE(1, 2) IGEMM_CASE(0, 2) IGEMM_CASE(1, 1) IGEMM_CASE(0, 1)
+                IGEMM_CASE(4, 0) IGEMM_CASE(1, 0) IGEMM_CASE(3, 0) IGEMM_CASE(0, 0)
+                default: return fail("conv: no kernel for this (MODE, DT)");
+            }
+#undef IGEMM_CASE
+        }
+        if (d.S > 1) launch_splitk_reduce(p, d.S, G, st);
+        QB_CHECK(hipGetLastError());
+    }
+    if (!d.gn_sep) return 0;
+    View o;
+    o.p = p.out; o.B = p.B; o.H = p.OH; o.W = p.OW; o.C = p.Cout; o.cs = p.out_cs; o.gs = p.out_gs; o.es = p.es;
+    return launch_gn_stats(o, p.B, G, p.gn_groups, d.gn_sum, st, false);
+}
+
+template <int BM, int BN, int WM, int WN>
+static int run(const ConvP& p, int G, int S, hipStream_t st, ConvRoute* dry) {
+    const IgemmPlan d = decide(p, G, BM, BN, S);
+    if (!dry) return execute<BM, BN, WM, WN>(d, G, st);
+    dry->kernel = d.kernel; dry->sums = !d.gn_sum ? 0 : d.gn_sep ? ROUTE_SEPARATE : d.kernel;
+    dry->BM = BM; dry->BN = BN; dry->S = d.S; dry->tail_shift = d.p.tail_shift;
+    if (d.kernel == ROUTE_PERSISTENT) conv_persistent_grid(d.p, G, d.bpc).report(dry);
+    return 0;
+}
+
+
+// The tile rule: the tile shape of a launch, as key 4 numbers them (1 = 64x64, 2 = 128x128, 3 = 128x64, 4 = 256x32), and the K partitions proposed for it
+struct TileChoice { int tile, S; };
+static TileChoice tile_rule(const ConvP& p, int G) {
+    if (tune().force_tile >= 1 && tune().force_tile <= 4) return {tune().force_tile, 1};
+    auto t64 = [&]() { return TileChoice{1, choose_split(p, G, 64, 64, igemm_occupancy(64, 64))}; };
+    // Tile shape (sweep: profiles/r01i_conv_sweep_*.md).  <= 32 output channels: 256x32.  <= 64 channels, and the
+    // memory-bound residual 1x1 layers with a short K (res2-4 conv3): 64x64, whose 7 resident blocks per CU keep more
+    // loads in flight.  Otherwise 128x128, split when the model says so; 64x64 again for launches too small for that.
+    const int nk = p.Kpad / BK;
+    if (p.Cout <= 32) return {4, choose_split(p, G, 256, 32, igemm_occupancy(256, 32))};
+    // 33-64 output channels without a residual, at least a round of tiles: 128x64 (each wave 64x32: the weight fragments
+    // are read from LDS half as often as with 64x64 tiles; +3-5 % on stem.conv3 / res2 conv1, conv2 - tools/tile_ab.py)
+    if (tune().tile_128x64 && p.Cout <= 64 && p.Cout > 32 && !p.res && (long)((p.M + 127) / 128) * G >= 1024) return {3, 1};
+    // (64 x 256 tiles for the residual 1x1 layers - input rows read once, 512-byte row segments - measured 30-50 % SLOWER than
+    // 64x64 in both the fp32 and the fp16 path, profiles/r03x_tile_64x256_rejected.txt: those layers live on blocks in flight)
+    if (p.Cout <= 64 || (p.res && nk <= 8 && p.Cout >= 128)) return t64();
+    // dilated layers that skip the filter rows lying in the padding (ASPP d = 18 on a 30-row map): 64-row tiles span 2-3 map rows
+    // instead of 4-5, so more of them see a filter row entirely in the padding - 1.28 -> 1.07 ms on that layer (tools/aspp_d18_ab.py)
+    if (p.skip_rows && p.es != 2 && p.kmode == 0 && p.kh > 1 && p.dil * 5 >= p.H * 2)
+        return t64();
+    const long tiles128 = (long)((p.M + 127) / 128) * ((p.Cout + 127) / 128) * G;
+    const int s128 = choose_split(p, G, 128, 128, igemm_occupancy(128, 128));
+    if (tiles128 < 64 || (tiles128 < 384 && s128 == 1)) return t64();
+    // 1x1 layers whose 128 x 128 tiling is at most ~5 tiles per CU (res4 / res5 conv1, the ASPP 1x1 and res3 conv1 at batch 16; every wide 1x1 layer
+    // at batches 1-4): 64 x 64 tiles, one per block - five to seven resident blocks per CU hide what two 128 x 128 blocks (split-K or persistent) cannot.
+    // tools/conv_sweep.py at 1 / 2 / 4 / 8 / 16 frames, round 6: 0.211 -> 0.176 ms on res4 conv1 and 0.357 -> 0.322 on res5.0 conv1 at batch 16,
+    // 0.134 -> 0.107 on res5 conv3 at batch 2; the batch-1 step 3.71 -> 3.50 ms, 1280x720 7.40 -> 6.96 ms (profiles/r14d_tile_rule.md)
+    if (tune().small_n_64 && p.es != 2 && p.kh == 1 && p.kw == 1 && !p.in2 && nk >= 16 && tiles128 <= 1280)
+        return t64();
+    // ... and, exact fp32, every 1x1 GEMM of K <= 1024 however large the launch - the Winograd position GEMMs of the 256- / 512-channel layers
+    // (fusion_res2 / res3, res4 / res5 conv2), the fusion 1x1 convolutions of res2 / res3, res5 conv3: a K loop of 8-32 slices is over before a
+    // 128 x 128 block has amortised its prologue and epilogue, and only two of those fit a CU.  Per layer at batch 16 (rocprofv3, forced tiles):
+    // fusion_res3 conv0 0.992 -> 0.936 ms, res4 conv2 0.170 -> 0.154, res5.1 conv3 0.685 -> 0.639; K = 2048 / 4096 (ASPP, fusion_res5) lose 1-3 %
+    // on 64 x 64 tiles and keep the persistent 128 x 128 launch (profiles/r14d_tile_rule.md)
+    // (128 x 64 tiles for fusion_res5.conv, K = 4096: 2.42 against 2.49 ms in the layer table, nothing in the step - not kept)
+    if (tune().small_n_64 == 1 && p.es != 2 && p.bf16 == 0 && p.kh == 1 && p.kw == 1 && !p.in2 && nk <= 32)
+        return t64();
+    return {2, s128};
+}
 
 int launch_conv(const ConvP& p0, int G, hipStream_t st, ConvRoute* dry) {
     ConvP p = p0;
@@ -1297,46 +1341,13 @@ int launch_conv(const ConvP& p0, int G, hipStream_t st, ConvRoute* dry) {
         const int rc = launch_conv_x8(p, G, st, dry);
         if (rc != 1) return rc;
     }
-    switch (tune().force_tile) {
-        case 1: return run<64, 64, 2, 2>(p, G, 1, st, dry);
-        case 2: return run<128, 128, 2, 2>(p, G, 1, st, dry);
-        case 4: return run<256, 32, 4, 1>(p, G, 1, st, dry);
-        case 3: return run<128, 64, 2, 2>(p, G, 1, st, dry);
-        default: break;
+    const TileChoice t = tile_rule(p, G);
+    switch (t.tile) {
+        case 1: return run<64, 64, 2, 2>(p, G, t.S, st, dry);
+        case 2: return run<128, 128, 2, 2>(p, G, t.S, st, dry);
+        case 4: return run<256, 32, 4, 1>(p, G, t.S, st, dry);
+        default: return run<128, 64, 2, 2>(p, G, t.S, st, dry);      // 3
     }
-    // Tile shape (sweep: profiles/r01i_conv_sweep_*.md).  <= 32 output channels: 256x32.  <= 64 channels, and the
-    // memory-bound residual 1x1 layers with a short K (res2-4 conv3): 64x64, whose 7 resident blocks per CU keep more
-    // loads in flight.  Otherwise 128x128, split when the model says so; 64x64 again for launches too small for that.
-    const int nk = p.Kpad / BK;
-    if (p.Cout <= 32) return run<256, 32, 4, 1>(p, G, choose_split(p, G, 256, 32, igemm_occupancy(256, 32)), st, dry);
-    // 33-64 output channels without a residual, at least a round of tiles: 128x64 (each wave 64x32: the weight fragments
-    // are read from LDS half as often as with 64x64 tiles; +3-5 % on stem.conv3 / res2 conv1, conv2 - tools/tile_ab.py)
-    if (tune().tile_128x64 && p.Cout <= 64 && p.Cout > 32 && !p.res && (long)((p.M + 127) / 128) * G >= 1024) return run<128, 64, 2, 2>(p, G, 1, st, dry);
-    // (64 x 256 tiles for the residual 1x1 layers - input rows read once, 512-byte row segments - measured 30-50 % SLOWER than
-    // 64x64 in both the fp32 and the fp16 path, profiles/r03x_tile_64x256_rejected.txt: those layers live on blocks in flight)
-    if (p.Cout <= 64 || (p.res && nk <= 8 && p.Cout >= 128)) return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st, dry);
-    // dilated layers that skip the filter rows lying in the padding (ASPP d = 18 on a 30-row map): 64-row tiles span 2-3 map rows
-    // instead of 4-5, so more of them see a filter row entirely in the padding - 1.28 -> 1.07 ms on that layer (tools/aspp_d18_ab.py)
-    if (p.skip_rows && p.es != 2 && p.kmode == 0 && p.kh > 1 && p.dil * 5 >= p.H * 2)
-        return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st, dry);
-    const long tiles128 = (long)((p.M + 127) / 128) * ((p.Cout + 127) / 128) * G;
-    const int s128 = choose_split(p, G, 128, 128, igemm_occupancy(128, 128));
-    if (tiles128 < 64 || (tiles128 < 384 && s128 == 1)) return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st, dry);
-    // 1x1 layers whose 128 x 128 tiling is at most ~5 tiles per CU (res4 / res5 conv1, the ASPP 1x1 and res3 conv1 at batch 16; every wide 1x1 layer
-    // at batches 1-4): 64 x 64 tiles, one per block - five to seven resident blocks per CU hide what two 128 x 128 blocks (split-K or persistent) cannot.
-    // tools/conv_sweep.py at 1 / 2 / 4 / 8 / 16 frames, round 6: 0.211 -> 0.176 ms on res4 conv1 and 0.357 -> 0.322 on res5.0 conv1 at batch 16,
-    // 0.134 -> 0.107 on res5 conv3 at batch 2; the batch-1 step 3.71 -> 3.50 ms, 1280x720 7.40 -> 6.96 ms (profiles/r14d_tile_rule.md)
-    if (tune().small_n_64 && p.es != 2 && p.kh == 1 && p.kw == 1 && !p.in2 && nk >= 16 && tiles128 <= 1280)
-        return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st, dry);
-    // ... and, exact fp32, every 1x1 GEMM of K <= 1024 however large the launch - the Winograd position GEMMs of the 256- / 512-channel layers
-    // (fusion_res2 / res3, res4 / res5 conv2), the fusion 1x1 convolutions of res2 / res3, res5 conv3: a K loop of 8-32 slices is over before a
-    // 128 x 128 block has amortised its prologue and epilogue, and only two of those fit a CU.  Per layer at batch 16 (rocprofv3, forced tiles):
-    // fusion_res3 conv0 0.992 -> 0.936 ms, res4 conv2 0.170 -> 0.154, res5.1 conv3 0.685 -> 0.639; K = 2048 / 4096 (ASPP, fusion_res5) lose 1-3 %
-    // on 64 x 64 tiles and keep the persistent 128 x 128 launch (profiles/r14d_tile_rule.md)
-    // (128 x 64 tiles for fusion_res5.conv, K = 4096: 2.42 against 2.49 ms in the layer table, nothing in the step - not kept)
-    if (tune().small_n_64 == 1 && p.es != 2 && p.bf16 == 0 && p.kh == 1 && p.kw == 1 && !p.in2 && nk <= 32)
-        return run<64, 64, 2, 2>(p, G, choose_split(p, G, 64, 64, igemm_occupancy(64, 64)), st, dry);
-    return run<128, 128, 2, 2>(p, G, s128, st, dry);
 }
 
 }  // namespace quber

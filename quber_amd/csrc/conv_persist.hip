@@ -792,27 +792,34 @@ __global__ __launch_bounds__(256) void pk_fixup_kernel(const ConvP p, int P) {
 }  // namespace
 
 
-// Eligibility beyond conv_persistent_ok() is decided by the caller (conv_igemm.hip: run<>): no skipped filter rows, a
-// workspace of 2 * P tiles.  p.mtiles / p.ntiles / p.vec_out are filled in.  Returns 0 on success.
-template <int BM, int BN, int WM, int WN>
-int launch_conv_persistent(ConvP p, int G, int bpc, hipStream_t st, ConvRoute* dry) {
-    const int nk = p.Kpad / BK;
-    p.pk_tpg = p.mtiles * p.ntiles;
-    p.pk_T = p.pk_tpg * G;
-    int P = 256 * bpc;
+// Blocks and shortest K share of a persistent launch of `bpc` resident blocks per CU (p.mtiles / p.ntiles filled in): what the launch hands its
+// kernel and what a dry run reports - the arguments of conv_persistent_segments, the work list
+PkGrid conv_persistent_grid(const ConvP& p, int G, int bpc) {
+    PkGrid g;
+    g.nk = p.Kpad / BK;
+    g.tiles = p.mtiles * p.ntiles * G;
+    g.blocks = 256 * bpc;
     // The remainder (tiles beyond whole rounds of P) is shared out in K only when a share is long enough to pay for
     // the two partial tiles a block then writes and the fix-up pass re-reads (key 14: shortest K, default 32 slices),
     // or when the launch cannot give every block a tile; otherwise the remainder tiles are computed whole.
-    p.pk_min = (nk >= tune().persist_min_nk || p.pk_T < P) ? 4 : 0;
-    if (p.pk_min) {
+    g.min_share = (g.nk >= tune().persist_min_nk || g.tiles < g.blocks) ? 4 : 0;
+    if (g.min_share) {
         // never more blocks than there are shares of pk_min K-slices
-        const long shares = (long)p.pk_T * nk / p.pk_min;
-        if (shares < P) P = (int)(shares < 8 ? 8 : shares / 8 * 8);
+        const long shares = (long)g.tiles * g.nk / g.min_share;
+        if (shares < g.blocks) g.blocks = (int)(shares < 8 ? 8 : shares / 8 * 8);
     }
-    if (dry) {      // the work list is conv_persistent_segments(tiles, blocks, nk, min_share, block)
-        dry->tiles = p.pk_T; dry->blocks = P; dry->nk = nk; dry->min_share = p.pk_min;
-        return 0;
-    }
+    return g;
+}
+
+// Eligibility beyond conv_persistent_ok() is decided by the caller (conv_igemm.hip: decide()): no skipped filter rows, a
+// workspace of 2 * P tiles.  p.mtiles / p.ntiles / p.vec_out are filled in.  Returns 0 on success.
+template <int BM, int BN, int WM, int WN>
+int launch_conv_persistent(ConvP p, int G, int bpc, hipStream_t st) {
+    const PkGrid pg = conv_persistent_grid(p, G, bpc);
+    const int nk = pg.nk, P = pg.blocks;
+    p.pk_tpg = p.mtiles * p.ntiles;
+    p.pk_T = pg.tiles;
+    p.pk_min = pg.min_share;
     const dim3 block(WM * WN * 64);
     p.pk_in_bytes = (int)((long)p.B * p.H * p.W * p.in_cs * 4);
     p.pk_debug = tune().persist_debug;
@@ -957,14 +964,18 @@ int launch_conv_dual(ConvP p, int G, hipStream_t st, ConvRoute* dry) {
     p.ntiles = (p.Cout + BMs - 1) / BMs;
     const double out_bytes = 4.0 * G * (double)p.M * p.Cout;
     const double bytes = 4.0 * G * ((double)p.M * p.Kpad + (double)p.Cout * p.Kpad) + out_bytes;
-    if (dry) { dry->kernel = ROUTE_PERSISTENT; dry->sums = 0; dry->BM = dry->BN = BMs; dry->S = 1; dry->tail_shift = 0; }
+    if (dry) {
+        dry->kernel = ROUTE_PERSISTENT; dry->sums = 0; dry->BM = dry->BN = BMs; dry->S = 1; dry->tail_shift = 0;
+        conv_persistent_grid(p, G, bpc).report(dry);
+        return 0;
+    }
     ProfScope prof(tag, bytes, 2.0 * G * (double)p.M * p.Kpad * p.Cout, st);
-    const int rc = big ? launch_conv_persistent<128, 128, 2, 2>(p, G, bpc, st, dry) : launch_conv_persistent<64, 64, 2, 2>(p, G, bpc, st, dry);
+    const int rc = big ? launch_conv_persistent<128, 128, 2, 2>(p, G, bpc, st) : launch_conv_persistent<64, 64, 2, 2>(p, G, bpc, st);
     return rc ? -1 : 0;
 }
 
-template int launch_conv_persistent<64, 64, 2, 2>(ConvP, int, int, hipStream_t, ConvRoute*);
-template int launch_conv_persistent<128, 128, 2, 2>(ConvP, int, int, hipStream_t, ConvRoute*);
-template int launch_conv_persistent<256, 32, 4, 1>(ConvP, int, int, hipStream_t, ConvRoute*);
+template int launch_conv_persistent<64, 64, 2, 2>(ConvP, int, int, hipStream_t);
+template int launch_conv_persistent<128, 128, 2, 2>(ConvP, int, int, hipStream_t);
+template int launch_conv_persistent<256, 32, 4, 1>(ConvP, int, int, hipStream_t);
 
 }  // namespace quber
