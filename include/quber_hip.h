@@ -381,6 +381,68 @@ int quber_meanshift_cluster(quber_ctx* ctx, const float* dev_emb, int32_t batch,
                             int32_t* dev_indices, float* dev_seeds, int32_t* dev_seed_labels, int32_t* dev_ids, uint8_t* dev_masks,
                             int32_t* dev_report, void* stream);
 
+/* Gaussian mean shift of 3-D centre votes into initial masks, and the initial mask processing (csrc/gms.hip): the UOIS-Net-3D base
+ * model's DSNWrapper.cluster -> GaussianMeanShift.mean_shift_smart_init (uois/src/segmentation.py:129-187, uois/src/cluster.py) and
+ * UOISNet3D.process_initial_masks (segmentation.py:425-491), which the reference runs as torch, numpy and OpenCV loops per frame on the
+ * host.  The numpy statement of what these calls compute is tests/test_gms_cpu.py: gms_np, imp_np; INTEGRATION.md "Initial masks from
+ * centre votes" has it in words.  dist(a, b) = sqrt((dx dx + dy dy) + dz dz) in float32, every operation rounded separately, the
+ * square root correctly rounded.
+ *   dev_votes f32 [B][3][H][W]: xyz + offsets, finite (the caller's duty: nothing on the device checks it); dev_fg u8 [B][H][W]: non-zero
+ *   marks an object pixel.  P = the fg pixels in row-major order, n = |P|; Xs = P[::subsample], n_sub = ceil(n / subsample);
+ *   S = min(num_seeds, n_sub): the seeds the frame really has.  1 <= num_seeds <= 256, 1 <= subsample <= 64.
+ *   dev_info i32 [B][3] = n, n_sub, S: written by quber_gms_seeds; read by climb / link / assign, where NULL means S = num_seeds.
+ * quber_gms_seeds: dev_first i32 [B] (clamped to 0..n_sub - 1), dev_draws u32 [B][num_seeds] (32-bit draws r_k; entry 0 is not read)
+ *   -> dev_indices i32 [B][num_seeds] into Xs, -1 behind S.  Seed 0 is first.  For k >= 1, with mind[p] = min over j < k of
+ *      dist(Xs[p], Xs[seed j]), q[p] = min(floor(float64(mind[p]) * 2^20), 2^31 - 1), total = sum q (exact in 64 bits) and
+ *      t = floor(r_k * total / 2^32): seed k is the first p whose inclusive prefix sum of q exceeds t; index 0 when total == 0.  This is
+ *      torch.multinomial(distance_to_nearest_seed, 1) quantised to about 1 um and stated in integers.  One launch, one workgroup per frame.
+ * quber_gms_climb: dev_seeds f32 [B][num_seeds][3] in and out; with dev_indices (may be NULL) it is first set to the points of Xs they
+ *   name (zero where the index is -1).  iters times, for the rows below S: W = exp(-0.5 / sigma^2 |Z - Xs|^2), Z = (W Xs) / sum W, in
+ *   float32 as a shift of Z (sum W (Xs - Z) / sum W), with a fixed reduction order: block partials are added in float64 in block order,
+ *   no floating-point atomics - two calls give the same bits, and a frame's result does not depend on the batch it is in.  A seed whose
+ *   weights sum to 0 keeps its position (the reference would make it NaN).  0 <= iters <= 1000, sigma > 0.
+ * quber_gms_link -> dev_seed_labels i32 [B][num_seeds] (-1 behind S): connected_components as written - in seed order, an unlabelled
+ *   seed i labels every seed j with dist(Z[j], Z[i]) <= epsilon: with the mode of the labels already there (the smallest among equal
+ *   counts) if there is one, else with the next new label.  A seed is inside its own ball, so the labels are 0..K-1 without gaps.
+ * quber_gms_assign: every fg pixel (all of P) takes the label of the first seed at minimum dist; labels with fewer than min_pixels
+ *   pixels are dropped, the survivors are numbered 1..count by ascending label, those behind n_masks (1..254) are dropped.
+ *   -> dev_ids i32 [B][H][W] (0, 1..count), dev_masks u8 [B][n_masks][H][W] (ids == k + 1 as 0 / 255, zero planes behind count; may be
+ *      NULL), dev_centers f32 [B][n_masks][3] (the mean of the climbed seeds that carry the label: a float32 sum in seed order, divided
+ *      by their number; zero rows behind count), dev_report i32 [B][6]: count, clusters found (K), dropped by min_pixels, 1 if truncated
+ *      to n_masks, 0 (ids emptied by the IMP), fg pixels.
+ * quber_gms_imp, on ANY id map: dev_ids i32 [B][H][W] in place, 0 = none, 1..n_ids (<= 254; a value outside counts as 0 and is written
+ *   back as 0).  For o = 1..n_ids in ascending order on the CURRENT map: mask = ids == o is opened, then closed, with
+ *   cv2.getStructuringElement(MORPH_ELLIPSE, (ksize, ksize)) (ksize odd, 1..15) and OpenCV's default constant border (beyond the frame
+ *   reads as 1 for an erosion, as 0 for a dilation); ids[mask] = 0, ids[result] = o.  Then, if largest, the largest 4-connected component
+ *   of every id (quber_cleanup_ids with keep_largest = 1, connectivity = 4).  Ids left empty are dropped, the rest renumbered 1..count'.
+ *   -> dev_masks u8 [B][n_masks][H][W] (may be NULL with n_masks = 0), dev_centers f32 [B][n_ids][3] (may be NULL) in and out: the rows
+ *      of the ids that stay, moved up, zero behind them; dev_report i32 [B][6] (may be NULL): entry 0 = count', entry 4 = ids that were
+ *      present and are empty now; the other entries are not touched.  One workgroup per frame with both bit planes in LDS: a frame with
+ *      2 * H * ceil(W / 32) * 4 > 152 KiB is an error (no global-memory fallback).
+ * quber_gms_cluster: seeds -> climb -> link -> assign -> (imp_ksize != 0: imp) on `stream`, with every intermediate result as an
+ *   output: dev_raw_ids is the id map before the IMP, dev_ids the one after it (equal without); masks, centers and report describe dev_ids.
+ * Every output is overwritten by every call.  H * W <= 2^24.  No host copy, no synchronisation, no memset node, no cooperative launch.
+ * The workspace (block counts, compacted points, running minimum, raw labels, tables, block partials: 1 MB + 20 H W bytes per frame of
+ * max_batch) is not part of quber_create: the FIRST call of any of these entries (quber_gms_link excepted, which needs none) allocates it
+ * and keeps it (quber_workspace_bytes counts it from then on), so that call is not capturable into a graph; later calls are.  Works on a
+ * context created with with_network = 0. */
+int quber_gms_seeds(quber_ctx* ctx, const float* dev_votes, const uint8_t* dev_fg, int32_t batch, int32_t subsample, const int32_t* dev_first,
+                    const uint32_t* dev_draws, int32_t num_seeds, int32_t* dev_indices, int32_t* dev_info, void* stream);
+int quber_gms_climb(quber_ctx* ctx, const float* dev_votes, const uint8_t* dev_fg, int32_t batch, int32_t subsample, const int32_t* dev_indices,
+                    const int32_t* dev_info, int32_t num_seeds, float sigma, int32_t iters, float* dev_seeds, void* stream);
+int quber_gms_link(quber_ctx* ctx, const float* dev_seeds, int32_t batch, int32_t num_seeds, const int32_t* dev_info, float epsilon,
+                   int32_t* dev_seed_labels, void* stream);
+int quber_gms_assign(quber_ctx* ctx, const float* dev_votes, const uint8_t* dev_fg, int32_t batch, const float* dev_seeds,
+                     const int32_t* dev_seed_labels, const int32_t* dev_info, int32_t num_seeds, int32_t min_pixels, int32_t n_masks,
+                     int32_t* dev_ids, uint8_t* dev_masks, float* dev_centers, int32_t* dev_report, void* stream);
+int quber_gms_imp(quber_ctx* ctx, int32_t* dev_ids, int32_t batch, int32_t n_ids, int32_t ksize, int32_t largest, int32_t n_masks,
+                  uint8_t* dev_masks, float* dev_centers, int32_t* dev_report, void* stream);
+int quber_gms_cluster(quber_ctx* ctx, const float* dev_votes, const uint8_t* dev_fg, int32_t batch, const int32_t* dev_first,
+                      const uint32_t* dev_draws, int32_t num_seeds, float sigma, int32_t iters, float epsilon, int32_t subsample,
+                      int32_t min_pixels, int32_t imp_ksize, int32_t imp_largest, int32_t n_masks, int32_t* dev_indices, float* dev_seeds,
+                      int32_t* dev_seed_labels, int32_t* dev_info, int32_t* dev_raw_ids, int32_t* dev_ids, uint8_t* dev_masks,
+                      float* dev_centers, int32_t* dev_report, void* stream);
+
 /* Zoom-in refinement (csrc/zoom.hip): the gather / scatter around a second pass that shows the network every first-pass instance as
  * a padded crop resized to a fixed square - the reference's crop_rois and match_label_crop (eval/base_model.py:843-961, copies at :1088
  * and :1192), which run one mask at a time with torch.unique, nonzero and a .cpu() per paste.  The numpy statement of what the three

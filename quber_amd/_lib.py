@@ -74,6 +74,12 @@ SIGNATURES = {
     "quber_meanshift_link": (C.c_int, [_P, _P, _I, _I, C.c_float, _P, _P]),
     "quber_meanshift_assign": (C.c_int, [_P, _P, _I, _I, _P, _P, _I, _P, C.c_float, _I, _P, _P, _P, _P]),
     "quber_meanshift_cluster": (C.c_int, [_P, _P, _I, _I, _P, _I, C.c_float, _I, C.c_float, _P, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "quber_gms_seeds": (C.c_int, [_P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "quber_gms_climb": (C.c_int, [_P, _P, _P, _I, _I, _P, _P, _I, C.c_float, _I, _P, _P]),
+    "quber_gms_link": (C.c_int, [_P, _P, _I, _I, _P, C.c_float, _P, _P]),
+    "quber_gms_assign": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "quber_gms_imp": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "quber_gms_cluster": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, C.c_float, _I, C.c_float, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "quber_zoom_rois": (C.c_int, [_P, _P, _I, _I, C.c_float, _P, _P]),
     "quber_zoom_crop": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "quber_zoom_paste": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, _P, _P, _P, _P, _P, _P, _P]),

@@ -122,6 +122,7 @@ void quber_destroy(quber_ctx* c) {
     if (c->perturb_ws) (void)hipFree(c->perturb_ws);
     if (c->masknms_ws) (void)hipFree(c->masknms_ws);
     if (c->meanshift_ws) (void)hipFree(c->meanshift_ws);
+    if (c->gms_ws) (void)hipFree(c->gms_ws);
     if (c->zoom_ws) (void)hipFree(c->zoom_ws);
     if (c->losses_ws) (void)hipFree(c->losses_ws);
     delete c;
@@ -632,6 +633,93 @@ int quber_meanshift_cluster(quber_ctx* c, const float* emb, int32_t batch, int32
     if (launch_meanshift_link(seeds, batch, num_seeds, epsilon, seed_labels, st)) return -1;
     return launch_meanshift_assign(emb, seeds, seed_labels, depth_z, depth_threshold, batch, num_seeds, n_masks, H, W, ids, masks, report,
                                    c->meanshift_ws, cap, st);
+}
+
+// ---- Gaussian mean shift of centre votes into initial masks, and the IMP (gms.hip); usable on a context without a network ----
+static int gms_ws(quber_ctx* c) {            // the only allocation of the six entries: made by the first call, for max_batch frames, and kept
+    if (c->gms_ws) return 0;
+    if (gms_prepare()) return -1;
+    const size_t need = gms_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width);
+    QB_CHECK(hipMalloc(&c->gms_ws, need));
+    c->alloc_bytes += need;
+    return 0;
+}
+
+static int gms_args(quber_ctx* c, const char* what, int32_t batch, int32_t num_seeds) {
+    if (check_batch(c, batch)) return -1;
+    if (num_seeds < 1 || num_seeds > 256) return fail(std::string(what) + ": num_seeds outside 1..256");
+    if ((long)c->cfg.height * c->cfg.width > (1L << 24)) return fail(std::string(what) + ": a frame of more than 2^24 pixels");
+    return 0;
+}
+
+int quber_gms_seeds(quber_ctx* c, const float* votes, const uint8_t* fg, int32_t batch, int32_t subsample, const int32_t* first,
+                    const uint32_t* draws, int32_t num_seeds, int32_t* indices, int32_t* info, void* stream) {
+    if (gms_args(c, "gms seeds", batch, num_seeds)) return -1;
+    if (!votes || !fg || !first || !draws || !indices) return fail("gms seeds: null tensor");
+    if (gms_ws(c)) return -1;
+    return launch_gms_seeds(votes, fg, first, draws, batch, num_seeds, subsample, c->cfg.height, c->cfg.width, indices, info, c->gms_ws,
+                            c->cfg.max_batch, (hipStream_t)stream);
+}
+
+int quber_gms_climb(quber_ctx* c, const float* votes, const uint8_t* fg, int32_t batch, int32_t subsample, const int32_t* indices,
+                    const int32_t* info, int32_t num_seeds, float sigma, int32_t iters, float* seeds, void* stream) {
+    if (gms_args(c, "gms climb", batch, num_seeds)) return -1;
+    if (!votes || !fg || !seeds) return fail("gms climb: null tensor");
+    if (gms_ws(c)) return -1;
+    return launch_gms_climb(votes, fg, indices, info, seeds, batch, num_seeds, subsample, c->cfg.height, c->cfg.width, sigma, iters, true,
+                            c->gms_ws, c->cfg.max_batch, (hipStream_t)stream);
+}
+
+int quber_gms_link(quber_ctx* c, const float* seeds, int32_t batch, int32_t num_seeds, const int32_t* info, float epsilon, int32_t* seed_labels,
+                   void* stream) {
+    if (check_batch(c, batch)) return -1;
+    return launch_gms_link(seeds, info, batch, num_seeds, epsilon, seed_labels, (hipStream_t)stream);
+}
+
+int quber_gms_assign(quber_ctx* c, const float* votes, const uint8_t* fg, int32_t batch, const float* seeds, const int32_t* seed_labels,
+                     const int32_t* info, int32_t num_seeds, int32_t min_pixels, int32_t n_masks, int32_t* ids, uint8_t* masks, float* centers,
+                     int32_t* report, void* stream) {
+    if (gms_args(c, "gms assign", batch, num_seeds)) return -1;
+    if (!votes || !fg || !seeds || !seed_labels || !ids || !centers || !report) return fail("gms assign: null tensor");
+    if (gms_ws(c)) return -1;
+    return launch_gms_assign(votes, fg, seeds, seed_labels, info, batch, num_seeds, n_masks, min_pixels, c->cfg.height, c->cfg.width, ids, masks,
+                             centers, report, c->gms_ws, c->cfg.max_batch, (hipStream_t)stream);
+}
+
+int quber_gms_imp(quber_ctx* c, int32_t* ids, int32_t batch, int32_t n_ids, int32_t ksize, int32_t largest, int32_t n_masks, uint8_t* masks,
+                  float* centers, int32_t* report, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (!ids) return fail("gms imp: null tensor");
+    if (gms_ws(c)) return -1;
+    return launch_gms_imp(ids, batch, n_ids, ksize, largest, n_masks, c->cfg.height, c->cfg.width, masks, centers, report, c->gms_ws,
+                          c->cfg.max_batch, c->cleanup_ws, (hipStream_t)stream);
+}
+
+int quber_gms_cluster(quber_ctx* c, const float* votes, const uint8_t* fg, int32_t batch, const int32_t* first, const uint32_t* draws,
+                      int32_t num_seeds, float sigma, int32_t iters, float epsilon, int32_t subsample, int32_t min_pixels, int32_t imp_ksize,
+                      int32_t imp_largest, int32_t n_masks, int32_t* indices, float* seeds, int32_t* seed_labels, int32_t* info, int32_t* raw_ids,
+                      int32_t* ids, uint8_t* masks, float* centers, int32_t* report, void* stream) {
+    if (gms_args(c, "gms", batch, num_seeds)) return -1;
+    if (!votes || !fg || !first || !draws || !indices || !seeds || !seed_labels || !info || !raw_ids || !ids || !masks || !centers || !report)
+        return fail("gms: null tensor");
+    if (!(epsilon >= 0.f)) return fail("gms: epsilon is negative or not a number");
+    if (n_masks < 1 || n_masks > 254) return fail("gms: n_masks outside 1..254");
+    const int H = c->cfg.height, W = c->cfg.width, cap = c->cfg.max_batch;
+    if (imp_ksize != 0) {                    // refused before anything is launched
+        if (imp_ksize < 1 || imp_ksize > 15 || !(imp_ksize & 1)) return fail("gms imp: ksize must be odd and lie in 1..15");
+        if (gms_imp_lds_bytes(H, W) > 152 * 1024) return fail("gms imp: the two bit planes of a frame do not fit the LDS (2 * H * ceil(W / 32) * 4 bytes > 152 KiB)");
+    }
+    if (gms_ws(c)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (launch_gms_seeds(votes, fg, first, draws, batch, num_seeds, subsample, H, W, indices, info, c->gms_ws, cap, st)) return -1;
+    if (launch_gms_climb(votes, fg, indices, info, seeds, batch, num_seeds, subsample, H, W, sigma, iters, false, c->gms_ws, cap, st)) return -1;
+    if (launch_gms_link(seeds, info, batch, num_seeds, epsilon, seed_labels, st)) return -1;
+    if (launch_gms_assign(votes, fg, seeds, seed_labels, info, batch, num_seeds, n_masks, min_pixels, H, W, raw_ids, imp_ksize ? nullptr : masks,
+                          centers, report, c->gms_ws, cap, st))
+        return -1;
+    if (launch_gms_copy_ids(raw_ids, ids, (size_t)batch * H * W, st)) return -1;
+    if (!imp_ksize) return 0;
+    return launch_gms_imp(ids, batch, n_masks, imp_ksize, imp_largest, n_masks, H, W, masks, centers, report, c->gms_ws, cap, c->cleanup_ws, st);
 }
 
 // ---- zoom-in refinement: rois, crops, paste (zoom.hip); usable on a context without a network ----

@@ -391,6 +391,22 @@ int launch_meanshift_link(const float* Z, int B, int S, float eps, int* labels, 
 int launch_meanshift_assign(const float* X, const float* Z, const int* seed_labels, const float* depth_z, float thresh, int B, int S, int N, int H,
                             int W, int* ids, uint8_t* planes, int* report, void* ws, int cap_b, hipStream_t st);
 size_t meanshift_ws_bytes(int cap_b, int H, int W);
+// Gaussian mean shift of centre votes f32 [B][3][H][W] under fg u8 [B][H][W] into masks, and the IMP (gms.hip), all on `st`; ws:
+// gms_ws_bytes(cap_b >= B, H, W) bytes.  S seeds <= 256; Z f32 [B][S][3]; counts i32 [B][3] = n, n_sub, seeds of the frame, or null
+// (every frame has S); N planes <= 254.  compact = false: the workspace still holds this batch's compaction (the chain).
+int launch_gms_seeds(const float* votes, const uint8_t* fg, const int* first, const unsigned* draws, int B, int S, int sub, int H, int W, int* idx,
+                     int* info, void* ws, int cap_b, hipStream_t st);
+int launch_gms_climb(const float* votes, const uint8_t* fg, const int* idx, const int* counts, float* Z, int B, int S, int sub, int H, int W,
+                     float sigma, int iters, bool compact, void* ws, int cap_b, hipStream_t st);
+int launch_gms_link(const float* Z, const int* counts, int B, int S, float eps, int* labels, hipStream_t st);
+int launch_gms_assign(const float* votes, const uint8_t* fg, const float* Z, const int* seed_labels, const int* counts, int B, int S, int N,
+                      int min_pixels, int H, int W, int* ids, uint8_t* planes, float* centers, int* report, void* ws, int cap_b, hipStream_t st);
+int launch_gms_imp(int* ids, int B, int n_ids, int ksize, int largest, int N, int H, int W, uint8_t* planes, float* centers, int* report, void* ws,
+                   int cap_b, void* cleanup_ws, hipStream_t st);
+int launch_gms_copy_ids(const int* src, int* dst, size_t n, hipStream_t st);
+size_t gms_ws_bytes(int cap_b, int H, int W);
+size_t gms_imp_lds_bytes(int H, int W);
+int gms_prepare();
 // zoom-in refinement (zoom.hip): the gather / scatter between the two passes, all on `st`; ws: zoom_ws_bytes(cap_b >= B, H, W) bytes.
 // T slots <= cap_b * 254, 2 <= S <= 512, C crop-pass ids <= 254, max_inst 1..254.
 int launch_zoom_rois(const int* ids, int B, int n_ids, int H, int W, float padding, int* rois, void* ws, int cap_b, hipStream_t st);

@@ -80,6 +80,7 @@ struct quber_ctx {
     void* masknms_ws = nullptr;   // bit planes, pair table, rank map and per-frame tables of quber_mask_nms: allocated by its first call
     size_t masknms_ws_bytes = 0;
     void* meanshift_ws = nullptr; // seed slots, histograms, running minimum, raw labels, block partials of the mean-shift entries (meanshift.hip): allocated by their first call
+    void* gms_ws = nullptr;       // counts, compacted points, running minimum, raw labels, tables, block partials of the Gaussian mean-shift entries (gms.hip): allocated by their first call
     void* zoom_ws = nullptr;      // extents, keep flags, depth keys, paint order, key map of the zoom-in entries (zoom.hip): allocated by their first call
     void* losses_ws = nullptr;    // moments, centres, block partials, histograms, foreground plane of the loss entries (losses.hip): allocated by their first call
     double* gn_stats = nullptr;   // [GN_SLOTS][launch group <= 4][max_batch][32 groups][sum, sum of squares]

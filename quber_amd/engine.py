@@ -629,6 +629,125 @@ class Engine:
                                                         _stream()))
         return o
 
+    # ---- Gaussian mean shift of centre votes, and the IMP (csrc/gms.hip; INTEGRATION.md "Initial masks from centre votes") ----
+    def _gms_in(self, votes, fg):
+        assert votes.dtype == torch.float32 and votes.is_contiguous() and votes.dim() == 4 and votes.shape[1:] == (3, self.H, self.W)
+        B = votes.shape[0]
+        assert fg.dtype in (torch.uint8, torch.bool) and fg.is_contiguous() and fg.shape == (B, self.H, self.W)
+        return B
+
+    def gms_seeds(self, votes, fg, first, draws, subsample=5, out=None, info=None):
+        """votes f32 [B,3,H,W], fg u8 / bool [B,H,W], first i32 [B], draws i32 [B,num_seeds]: the bit patterns of the 32-bit draws of
+        gms.GaussianMeanShift.draws (``torch.from_numpy(r.view(np.int32))``) -> (indices i32 [B,num_seeds] into the subsampled foreground points, -1 behind
+        the frame's seeds; info i32 [B,3] = n, n_sub, seeds of the frame)."""
+        B = self._gms_in(votes, fg)
+        assert draws.dtype == torch.int32 and draws.is_contiguous() and draws.dim() == 2 and draws.shape[0] == B
+        S = draws.shape[1]
+        assert first.dtype == torch.int32 and first.is_contiguous() and first.shape == (B,)
+        out = self._ms_tensor(out, torch.int32, (B, S), "indices")
+        info = self._ms_tensor(info, torch.int32, (B, 3), "info")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_gms_seeds(self.h, _ptr(votes), _ptr(fg), B, int(subsample), _ptr(first), _ptr(draws), S, _ptr(out),
+                                                _ptr(info), _stream()))
+        return out, info
+
+    def gms_climb(self, votes, fg, seeds=None, indices=None, info=None, sigma=0.02, iters=10, subsample=5):
+        """seeds f32 [B,S,3] climbed IN PLACE, or indices i32 [B,S]: the subsampled points to start from (then seeds may be None or the
+        tensor to write into); info i32 [B,3] or None (every row is a seed) -> seeds: `iters` rounds of the Gaussian mean shift."""
+        B = self._gms_in(votes, fg)
+        assert seeds is not None or indices is not None
+        S = indices.shape[1] if indices is not None else seeds.shape[1]
+        assert indices is None or (indices.dtype == torch.int32 and indices.is_contiguous() and indices.shape == (B, S))
+        assert info is None or (info.dtype == torch.int32 and info.is_contiguous() and info.shape == (B, 3))
+        seeds = self._ms_tensor(seeds, torch.float32, (B, S, 3), "seeds")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_gms_climb(self.h, _ptr(votes), _ptr(fg), B, int(subsample), _ptr(indices), _ptr(info), S, float(sigma),
+                                                int(iters), _ptr(seeds), _stream()))
+        return seeds
+
+    def gms_link(self, seeds, info=None, epsilon=0.05, out=None):
+        """seeds f32 [B,S,3] -> seed labels i32 [B,S] (-1 behind the frame's seeds): the reference's connected_components."""
+        B, S = seeds.shape[:2]
+        assert seeds.dtype == torch.float32 and seeds.is_contiguous() and seeds.shape == (B, S, 3)
+        assert info is None or (info.dtype == torch.int32 and info.is_contiguous() and info.shape == (B, 3))
+        out = self._ms_tensor(out, torch.int32, (B, S), "seed labels")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_gms_link(self.h, _ptr(seeds), B, S, _ptr(info), float(epsilon), _ptr(out), _stream()))
+        return out
+
+    def gms_assign(self, votes, fg, seeds, seed_labels, n_masks, info=None, min_pixels=300, ids=None, masks=None, centers=None, report=None):
+        """Every foreground pixel to its nearest seed's label, the min_pixels filter, the survivors numbered 1..count -> {"ids": i32
+        [B,H,W], "masks": u8 [B,n_masks,H,W] of 0 / 255, "centers": f32 [B,n_masks,3], "report": i32 [B,6] = count, clusters found,
+        dropped by min_pixels, truncated, 0, fg pixels}."""
+        B = self._gms_in(votes, fg)
+        S, N = seeds.shape[1], int(n_masks)
+        assert seeds.dtype == torch.float32 and seeds.is_contiguous() and seeds.shape == (B, S, 3)
+        assert seed_labels.dtype == torch.int32 and seed_labels.is_contiguous() and seed_labels.shape == (B, S)
+        assert info is None or (info.dtype == torch.int32 and info.is_contiguous() and info.shape == (B, 3))
+        ids = self._ms_tensor(ids, torch.int32, (B, self.H, self.W), "ids")
+        masks = self._ms_tensor(masks, torch.uint8, (B, N, self.H, self.W), "masks")
+        centers = self._ms_tensor(centers, torch.float32, (B, N, 3), "centers")
+        report = self._ms_tensor(report, torch.int32, (B, 6), "report")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_gms_assign(self.h, _ptr(votes), _ptr(fg), B, _ptr(seeds), _ptr(seed_labels), _ptr(info), S, int(min_pixels),
+                                                 N, _ptr(ids), _ptr(masks), _ptr(centers), _ptr(report), _stream()))
+        return {"ids": ids, "masks": masks, "centers": centers, "report": report}
+
+    def _gms_imp_fits(self):
+        from .gms import IMP_LDS_BYTES, imp_plane_bytes
+        if imp_plane_bytes(self.H, self.W) > IMP_LDS_BYTES:
+            raise ValueError(f"cluster: the IMP's two bit planes of a {self.H} x {self.W} frame ({imp_plane_bytes(self.H, self.W)} bytes) "
+                             f"do not fit the LDS ({IMP_LDS_BYTES}); there is no global-memory fallback")
+
+    def gms_imp(self, ids, n_ids, imp=None, n_masks=0, masks=None, centers=None, report=None):
+        """ids i32 [B,H,W] (0, 1..n_ids), processed IN PLACE under `imp` (a gms.IMP; default the reference's): every id opened and closed
+        in ascending order on the current map, the largest 4-connected component, empty ids dropped and the rest renumbered ->
+        {"ids", "masks": u8 [B,n_masks,H,W] or None, "centers": the given f32 [B,n_ids,3] compacted alike or None, "report": i32 [B,6],
+        entries 0 (ids left) and 4 (ids emptied) written}."""
+        from .gms import IMP
+        imp = IMP() if imp is None else imp
+        self._gms_imp_fits()
+        B, N = ids.shape[0], int(n_masks)
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.shape == (B, self.H, self.W)
+        assert centers is None or (centers.dtype == torch.float32 and centers.is_contiguous() and centers.shape == (B, int(n_ids), 3))
+        if N:
+            masks = self._ms_tensor(masks, torch.uint8, (B, N, self.H, self.W), "masks")
+        report = torch.zeros((B, 6), dtype=torch.int32, device=self.device) if report is None else report
+        assert report.dtype == torch.int32 and report.is_contiguous() and report.shape == (B, 6)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_gms_imp(self.h, _ptr(ids), B, int(n_ids), imp.ksize, int(imp.largest), N, _ptr(masks) if N else None,
+                                              _ptr(centers), _ptr(report), _stream()))
+        return {"ids": ids, "masks": masks if N else None, "centers": centers, "report": report}
+
+    def gms(self, votes, fg, first, draws, gms=None, n_masks=None, out=None):
+        """The chain seeds -> climb -> link -> assign -> IMP under `gms` (a gms.GaussianMeanShift; default: the reference's): votes f32
+        [B,3,H,W], fg u8 / bool [B,H,W], first i32 [B], draws i32 [B,num_seeds] (32-bit words) -> {"indices": i32 [B,S], "seeds": f32
+        [B,S,3], "seed_labels": i32 [B,S], "info": i32 [B,3], "raw_ids": i32 [B,H,W] (before the IMP), "ids", "masks": u8
+        [B,n_masks,H,W], "centers": f32 [B,n_masks,3], "report": i32 [B,6]}.  out: such a dict to write into.  Nothing is copied to the
+        host; the first call on an engine allocates the workspace and cannot be captured into a graph."""
+        from .gms import GaussianMeanShift
+        g = GaussianMeanShift() if gms is None else gms
+        B = self._gms_in(votes, fg)
+        S = g.num_seeds
+        N = min(self.cap, 254) if n_masks is None else int(n_masks)
+        if g.imp is not None:
+            self._gms_imp_fits()
+        assert first.dtype == torch.int32 and first.is_contiguous() and first.shape == (B,)
+        assert draws.dtype == torch.int32 and draws.is_contiguous() and draws.shape == (B, S)
+        o = dict(out or {})
+        for key, dtype, shape in (("indices", torch.int32, (B, S)), ("seeds", torch.float32, (B, S, 3)), ("seed_labels", torch.int32, (B, S)),
+                                  ("info", torch.int32, (B, 3)), ("raw_ids", torch.int32, (B, self.H, self.W)),
+                                  ("ids", torch.int32, (B, self.H, self.W)), ("masks", torch.uint8, (B, N, self.H, self.W)),
+                                  ("centers", torch.float32, (B, N, 3)), ("report", torch.int32, (B, 6))):
+            o[key] = self._ms_tensor(o.get(key), dtype, shape, key)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_gms_cluster(self.h, _ptr(votes), _ptr(fg), B, _ptr(first), _ptr(draws), S, g.sigma, g.iters, g.epsilon,
+                                                  g.subsample, g.min_pixels, g.imp.ksize if g.imp is not None else 0,
+                                                  int(g.imp.largest) if g.imp is not None else 0, N, _ptr(o["indices"]), _ptr(o["seeds"]),
+                                                  _ptr(o["seed_labels"]), _ptr(o["info"]), _ptr(o["raw_ids"]), _ptr(o["ids"]), _ptr(o["masks"]),
+                                                  _ptr(o["centers"]), _ptr(o["report"]), _stream()))
+        return o
+
     # ---- zoom-in refinement: rois, crops, paste (csrc/zoom.hip; INTEGRATION.md "Zoom-in refinement") ----
     def zoom_rois(self, ids, n_ids, padding=0.25, out=None):
         """ids i32 [B,H,W] (device; compact: 0 none, 1..n_ids) -> rois i32 [B,n_ids,4] = (x0, y0, x1, y1) inclusive: the tight extent of

@@ -43,6 +43,14 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
     255, disjoint), ``cluster_ids`` (i32 [H,W]), ``cluster_seeds`` (f32 [num_seeds,64]: the climbed modes) and ``cluster_report`` (i64
     [4]: count, clusters before the depth filter, dropped by it, truncated).  Refused together with ``nms=``, with initial masks, and in
     ``enqueue_batch`` / ``predict_stream``.  Default: none, today's keys, nothing launched or allocated.
+  * ``cluster=GaussianMeanShift(num_seeds=200, sigma=0.02, iters=10, epsilon=0.05, subsample=5, min_pixels=300, imp=IMP(9, True),
+    seed=0)``: the same place for the third family of base model, UOIS-Net-3D, whose Depth Seeding Network gives a foreground map and a
+    3-D centre vote per pixel: the Gaussian mean shift of ``DSNWrapper.cluster`` and the IMP of ``process_initial_masks``
+    (uois/src/segmentation.py:129-187, :425-491) make the initial masks on the device (csrc/gms.hip; INTEGRATION.md "Initial masks from
+    centre votes").  ``predict`` / ``predict_batch`` take ``center_votes=`` (f32 [3,H,W] per frame, xyz + offsets, finite) and ``fg=``
+    (u8 / bool [H,W]) in place of masks.  The keys of ``MeanShift`` (``cluster_seeds`` is f32 [num_seeds,3], ``cluster_report`` i64 [6]:
+    count, clusters found, dropped by ``min_pixels``, truncated, emptied by the IMP, fg pixels) and ``cluster_raw_ids`` (i32 [H,W]: the
+    map before the IMP), ``cluster_centers`` (f32 [count,3]).  The same refusals; the input of the other clusterer is a ``ValueError``.
   * ``zoom=ZoomIn(crop=224, padding=0.25, min_overlap=0.5)``: the second, zoomed-in pass of the reference's base models (``crop_rois`` /
     ``match_label_crop``, eval/base_model.py:843-961) without leaving the device (csrc/zoom.hip; INTEGRATION.md "Zoom-in refinement"):
     every instance of pass 1 - run with all configured options, through post-processing and ``cleanup`` - is cropped with a padded box,
@@ -72,6 +80,7 @@ import torch
 from .. import arch, config as qconfig, engine as qengine
 from ..cleanup import Cleanup
 from ..masknms import MaskNMS, check_scores
+from ..gms import IMP_LDS_BYTES, GaussianMeanShift, imp_plane_bytes
 from ..meanshift import CHANNELS as CLUSTER_CHANNELS, MeanShift
 from ..perturb import Perturb
 from ..structures import Boxes, Instances
@@ -132,7 +141,7 @@ class RefineOptions:
     nms: MaskNMS = None               # scored, overlapping initial masks made disjoint on the device before anything else reads them
     zoom: ZoomIn = None               # a second pass on a padded, resized crop of every instance, pasted back on the device
     losses: Losses = None             # with a call's gt_labels=: the reference's training targets and loss dict of every frame, on the device
-    cluster: MeanShift = None         # the initial masks come from mean-shift clustering of pixel embeddings on the device, before anything else
+    cluster: object = None            # a MeanShift (pixel embeddings) or a GaussianMeanShift (centre votes): the initial masks are clustered on the device, before anything else
 
     @classmethod
     def parse(cls, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
@@ -146,7 +155,11 @@ class RefineOptions:
             raise ValueError("losses: not with zoom= (the crop pass has no ground truth: left out)")
         if perturb is not None and not isinstance(perturb, Perturb):
             raise ValueError(f"perturb={perturb!r}: expected None or a quber_amd.perturb.Perturb")
-        zoom, nms, cluster = ZoomIn.parse(zoom), MaskNMS.parse(nms), MeanShift.parse(cluster)
+        zoom, nms = ZoomIn.parse(zoom), MaskNMS.parse(nms)
+        if not isinstance(cluster, GaussianMeanShift):       # either clusterer: UCN's embeddings (MeanShift) or UOIS-Net-3D's centre votes
+            if cluster is not None and not isinstance(cluster, MeanShift):
+                raise ValueError(f"cluster={cluster!r}: expected None, a quber_amd.meanshift.MeanShift or a quber_amd.gms.GaussianMeanShift")
+            cluster = MeanShift.parse(cluster)
         if cluster is not None and nms is not None:
             raise ValueError("cluster: not with nms= (the clustering's masks are disjoint and have no scores)")
         return cls(bool(tta), bool(decode_errors), int(iterations), bool(until_converged), bool(track_initial), Cleanup.parse(cleanup),
@@ -333,8 +346,11 @@ class RefinerModel:
             return None
         if cluster_in is None:
             raise ValueError("cluster: this call path has no embeddings (predict and predict_batch take embeddings=)")
-        emb, first, z = cluster_in
-        cl = eng.meanshift(emb, first, self.cluster, d_masks.shape[1], z)
+        if isinstance(self.cluster, GaussianMeanShift):      # cluster_in = (votes f32 [B,3,H,W], fg u8 [B,H,W], first i32 [B], draws i32 [B,S])
+            cl = eng.gms(*cluster_in, self.cluster, d_masks.shape[1])
+        else:
+            emb, first, z = cluster_in
+            cl = eng.meanshift(emb, first, self.cluster, d_masks.shape[1], z)
         d_masks[:B].copy_(cl["masks"])
         return cl
 
@@ -596,6 +612,8 @@ class RefinerModel:
             cl = rec.cl
             r["cluster_masks"], r["cluster_ids"], r["cluster_seeds"] = cl["masks"][b, :n], cl["ids"][b], cl["seeds"][b]
             r["cluster_report"] = cl["report"][b].to(torch.int64)
+            if "raw_ids" in cl:                              # a GaussianMeanShift: the map before the IMP, and the clusters' centres
+                r["cluster_raw_ids"], r["cluster_centers"] = cl["raw_ids"][b], cl["centers"][b, :n]
         if pt is not None:
             r["perturbed_masks"], r["perturb_report"] = pt[0][b, :n], pt[1][b, :n].to(torch.int64)
         if it is not None:
@@ -878,17 +896,20 @@ class MaskRefinerPredictor:
         self.fast_path = os.environ.get("QUBER_PREDICT_FAST", "1") != "0"     # 0: the general batched path for single frames too
 
     # -- reference signature (predictor.py:287) --
-    def predict(self, rgb_img, depth_img=None, perturbed_masks=None, mask_scores=None, gt_labels=None, embeddings=None, depth_z=None):
+    def predict(self, rgb_img, depth_img=None, perturbed_masks=None, mask_scores=None, gt_labels=None, embeddings=None, depth_z=None,
+                center_votes=None, fg=None):
         # gt_labels (with losses=): the frame's ground-truth label map, integer [H,W], 0 = none, 1..n; the dict then carries `losses`
         # embeddings (with cluster=, in place of perturbed_masks): f32 [64,H,W]; depth_z: f32 [H,W], the depth filter's plane
-        if self.cluster is not None or embeddings is not None or depth_z is not None:
+        # center_votes, fg (with cluster=GaussianMeanShift(), in place of perturbed_masks): f32 [3,H,W] = xyz + offsets, and u8 / bool [H,W]
+        if self.cluster is not None or embeddings is not None or depth_z is not None or center_votes is not None or fg is not None:
             if perturbed_masks is not None:
                 raise ValueError("cluster: embeddings= takes the place of the initial masks; both were given")
             if mask_scores is not None:
                 raise ValueError("cluster: the clustering's masks have no scores; mask_scores= was given")
             return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], None,
                                       gt_labels=None if gt_labels is None else [gt_labels],
-                                      embeddings=None if embeddings is None else [embeddings], depth_z=None if depth_z is None else [depth_z])
+                                      embeddings=None if embeddings is None else [embeddings], depth_z=None if depth_z is None else [depth_z],
+                                      center_votes=None if center_votes is None else [center_votes], fg=None if fg is None else [fg])
         masks = np.zeros((0,) + rgb_img.shape[:2], np.uint8) if perturbed_masks is None else np.asarray(perturbed_masks)
         gts = None if gt_labels is None else [gt_labels]
         if self.nms is not None:                          # the general path: how many masks there are is known on the device only
@@ -905,18 +926,42 @@ class MaskRefinerPredictor:
             depth_img = None
         return [self.model.predict_one(rgb_img, depth_img, mask_bytes(masks, self.perturb is not None), gt_labels)]
 
-    def _cluster_inputs(self, B, H, W, masks_list, scores_list, embeddings, depth_z):
+    def _gms_inputs(self, B, H, W, center_votes, fg):
+        """cluster=GaussianMeanShift(): the checked host arrays (votes f32 [B,3,H,W], fg u8 [B,H,W]) of a call."""
+        if center_votes is None or fg is None or len(center_votes) != B or len(fg) != B:
+            raise ValueError("cluster: center_votes= and fg= of every frame are required when cluster= is a GaussianMeanShift")
+        votes = np.ascontiguousarray(np.stack([np.asarray(v) for v in center_votes]), dtype=np.float32)
+        if votes.shape != (B, 3, H, W):
+            raise ValueError(f"cluster: center_votes of shape {votes.shape[1:]} per frame, expected (3, {H}, {W})")
+        on = np.stack([np.asarray(f) for f in fg])
+        if on.shape != (B, H, W) or on.dtype not in (np.uint8, np.bool_):
+            raise ValueError(f"cluster: fg of shape {on.shape[1:]} and dtype {on.dtype} per frame, expected ({H}, {W}) of uint8 or bool")
+        if not np.isfinite(votes).all():
+            raise ValueError("cluster: center_votes must be finite")
+        if self.cluster.imp is not None and imp_plane_bytes(H, W) > IMP_LDS_BYTES:
+            raise ValueError(f"cluster: the IMP's two bit planes of a {H} x {W} frame do not fit the LDS; there is no global-memory fallback")
+        return votes, np.ascontiguousarray((on != 0).astype(np.uint8))
+
+    def _cluster_inputs(self, B, H, W, masks_list, scores_list, embeddings, depth_z, center_votes=None, fg=None):
         """cluster=: the checked host arrays (embeddings f32 [B,64,H,W], depth_z f32 [B,H,W] or None) of a call, before anything is
         uploaded or launched; None without cluster=.  The first seeds are drawn by the caller once every other check has passed."""
         ms = self.cluster
         if ms is None:
             if embeddings is not None or depth_z is not None:
                 raise ValueError("embeddings= / depth_z= need cluster= (a quber_amd.meanshift.MeanShift)")
+            if center_votes is not None or fg is not None:
+                raise ValueError("center_votes= / fg= need cluster= (a quber_amd.gms.GaussianMeanShift)")
             return None
         if masks_list is not None:
-            raise ValueError("cluster: embeddings= takes the place of the initial masks; both were given")
+            raise ValueError("cluster: embeddings= / center_votes= take the place of the initial masks; both were given")
         if scores_list is not None:
             raise ValueError("cluster: the clustering's masks have no scores; scores_list= was given")
+        if isinstance(ms, GaussianMeanShift):
+            if embeddings is not None or depth_z is not None:
+                raise ValueError("cluster: a GaussianMeanShift takes center_votes= and fg=, not embeddings= / depth_z=")
+            return self._gms_inputs(B, H, W, center_votes, fg)
+        if center_votes is not None or fg is not None:
+            raise ValueError("cluster: a MeanShift takes embeddings=, not center_votes= / fg=")
         if embeddings is None or len(embeddings) != B:
             raise ValueError("cluster: the embeddings of every frame are required when cluster= is set")
         emb = np.ascontiguousarray(np.stack([np.asarray(e) for e in embeddings]), dtype=np.float32)
@@ -933,14 +978,23 @@ class MaskRefinerPredictor:
                 raise ValueError(f"cluster: depth_z of shape {z.shape[1:]} per frame, expected ({H}, {W})")
         return emb, z
 
-    def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None, gt_labels=None, embeddings=None, depth_z=None):
+    def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None, gt_labels=None, embeddings=None, depth_z=None,
+                      center_votes=None, fg=None):
         """rgb_imgs/depth_imgs: u8 [B,H,W,3] arrays; masks_list: B arrays u8/bool [N_b,H,W]; scores_list (required with nms=): B arrays
         [N_b] of finite scores; gt_labels (with losses=): the B ground-truth label maps, integer [B,H,W] or a list.  With cluster=:
-        masks_list is None, embeddings: B arrays f32 [64,H,W], depth_z: B arrays f32 [H,W] (with depth_threshold).  -> list of B dicts."""
+        masks_list is None, embeddings: B arrays f32 [64,H,W], depth_z: B arrays f32 [H,W] (with depth_threshold); or, with a
+        GaussianMeanShift, center_votes: B arrays f32 [3,H,W] and fg: B arrays u8 / bool [H,W].  -> list of B dicts."""
         B, H, W = rgb_imgs.shape[:3]
-        cluster_in = self._cluster_inputs(B, H, W, masks_list, scores_list, embeddings, depth_z)
-        # rows of the mask tensor per frame; with cluster=: one plane per cluster there can be - the seeds' labels but the largest
-        counts = [len(m) for m in masks_list] if cluster_in is None else [min(max(self.cluster.num_seeds - 1, 1), 254)] * B
+        cluster_in = self._cluster_inputs(B, H, W, masks_list, scores_list, embeddings, depth_z, center_votes, fg)
+        gms = isinstance(self.cluster, GaussianMeanShift)
+        # rows of the mask tensor per frame; with cluster=: one plane per cluster there can be - the seeds' labels but the largest (a
+        # GaussianMeanShift: a label per seed, each with min_pixels pixels of the frame)
+        if cluster_in is None:
+            counts = [len(m) for m in masks_list]
+        elif gms:
+            counts = [min(self.cluster.num_seeds, 254, max(H * W // max(self.cluster.min_pixels, 1), 1))] * B
+        else:
+            counts = [min(max(self.cluster.num_seeds - 1, 1), 254)] * B
         sc = None
         if self.nms is not None:                          # checked before anything is uploaded or launched
             if scores_list is None or len(scores_list) != len(masks_list):
@@ -970,7 +1024,11 @@ class MaskRefinerPredictor:
         if cluster_in is None:
             d_masks[:B].copy_(torch.from_numpy(mk))
         else:                                             # the first seeds: drawn last, so that a call that raised above has drawn nothing
-            cluster_in = (cluster_in[0], self.cluster.first_seeds(B, H * W), cluster_in[1])
+            if gms:
+                first, draws = self.cluster.draws([self.cluster.n_sub(int(f.sum())) for f in cluster_in[1]])
+                cluster_in = (cluster_in[0], cluster_in[1], first, draws.view(np.int32))
+            else:
+                cluster_in = (cluster_in[0], self.cluster.first_seeds(B, H * W), cluster_in[1])
             cluster_in = tuple(None if a is None else torch.from_numpy(a).to(self.device) for a in cluster_in)
         rec = model.device_pass(eng, bgr, depth, d_masks, None if sc is None else torch.from_numpy(sc).to(self.device), B, may_stop=True,
                                 own=counts, gt=gt, cluster_in=cluster_in)
