@@ -336,6 +336,43 @@ int quber_mask_nms(quber_ctx* ctx, const uint8_t* dev_masks, const float* dev_sc
                    int32_t on_top, uint8_t* dev_out_masks, int32_t* dev_ids, int32_t* dev_source, float* dev_out_scores,
                    int32_t* dev_report, void* stream);
 
+/* COCO AP, the per-frame half (csrc/cocoap.hip): computeIoU + evaluateImg of the published COCOeval and bbIou / rleIou of its maskApi.c for
+ * ONE category, which the reference runs on the host through pycocotools (train_net.py:57 COCOEvaluator(use_fast_impl=False),
+ * maskrefiner/evaluation/instance_evaluation.py) on the masks, scores and boxes of model.py:318-356.  The numpy statement of what this call
+ * computes is tests/test_cocoap_cpu.py: coco_eval_img_np; DESIGN.md "COCO AP" has it in words.  accumulate / summarize run on the host
+ * (quber_amd/eval/coco_ap.py) on the records below.
+ *   dev_dt u8 [B][n_dt][H][W] (non-zero = inside), dev_scores f32 [B][n_dt]; a detection whose score is NaN is absent (never ranked): the
+ *     padding of a frame with fewer detections.  dev_gt u8 [B][n_gt][H][W], dev_gt_flags u8 [B][n_gt]: bit 0 = crowd, bit 1 = ignore, 0xFF =
+ *     absent.  dev_gt_area f64 [B][n_gt] or NULL: the ground-truth areas to use; an entry that is NaN, like NULL, means the computed one.
+ *   iou_type 0 = segm: i = pixels in both masks, da / ga = pixels in each; iou = 0 if i == 0, else i / da for a crowd, else
+ *     i / (da + ga - i), integers converted to float64 and divided once.  Areas: da, ga.
+ *   iou_type 1 = bbox: dev_dt_boxes f64 [B][n_dt][4], dev_gt_boxes f64 [B][n_gt][4] = x, y, w, h; either may be NULL - the tight box of
+ *     each mask (x0, y0, x1 + 1 - x0, y1 + 1 - y0; zeros for an empty mask) - and with both given the mask pointers may be NULL.
+ *     w = min(dx + dw, gx + gw) - max(dx, gx), h likewise, 0 if w <= 0 or h <= 0; i = w h; u = crowd ? dw dh : dw dh + gw gh - i; i / u in
+ *     float64, every operation rounded on its own.  Areas: dw dh, gw gh.
+ *   dev_iou_thrs f64 [n_thrs], dev_area_rng f64 [n_rng][2]: the host's constants, bit for bit.
+ *   The detections are ranked by score, descending, among equal scores the lower index first; the first 100 count.  Per area range
+ *     gi[g] = ignore or crowd or area_g outside [lo, hi]; gorder = the stable order of gi.  Per threshold t the ranked detections are
+ *     matched in order: best = min(t, 1 - 1e-10); walking gorder, a ground truth that is matched and no crowd is skipped, the walk stops at
+ *     the first ignored one once a counting one is held, iou < best is skipped, anything else replaces the held one (equal replaces: the
+ *     later wins).  A match sets dtm, dtIg = gi of the match; an unmatched detection is ignored iff its area is outside [lo, hi].
+ *   -> dev_counts i32 [B][2]: n_top (<= 100), n_gt_present
+ *   -> dev_order i32 [B][100]: the input index of every rank, -1 behind n_top;  dev_out_scores f32 [B][100], 0 behind n_top
+ *   -> dev_dt_area f64 [B][100] in rank order, 0 behind n_top;  dev_gt_area_used f64 [B][n_gt], 0 for an absent one
+ *   -> dev_iou f64 [B][100][n_gt]: rank x input ground truth; 0 behind n_top and for an absent ground truth
+ *   -> dev_dtm, dev_dtig u8 [B][n_rng][n_thrs][100], 0 behind n_top
+ *   -> dev_gi u8 [B][n_rng][n_gt]: 0 counts, 1 ignored, 2 absent;  dev_gorder i32 [B][n_rng][n_gt]: input indices, the absent ones last
+ * Every output byte is written by every call.  n_dt <= 1024, n_gt <= 1024 (neither is bounded by max_instances), n_thrs <= 16,
+ * n_rng <= 8: anything beyond is an error, never truncated.  Launches (rank, zero, pack + gram | boxes, iou, gorder, match) on `stream`; no
+ * host copy, no synchronisation, no memset node.  The workspace (bit planes of 100 + n_gt masks per frame, pair table, areas, boxes) is not
+ * part of quber_create: the first call allocates it and a call that needs a larger one replaces it (quber_workspace_bytes counts it), so
+ * such a call is not capturable into a graph; later calls are.  Works on a context created with with_network = 0. */
+int quber_coco_match(quber_ctx* ctx, const uint8_t* dev_dt, const float* dev_scores, const double* dev_dt_boxes, int32_t n_dt,
+                     const uint8_t* dev_gt, const uint8_t* dev_gt_flags, const double* dev_gt_area, const double* dev_gt_boxes, int32_t n_gt,
+                     int32_t batch, int32_t iou_type, const double* dev_iou_thrs, int32_t n_thrs, const double* dev_area_rng, int32_t n_rng,
+                     int32_t* dev_counts, int32_t* dev_order, float* dev_out_scores, double* dev_dt_area, double* dev_gt_area_used,
+                     double* dev_iou, uint8_t* dev_dtm, uint8_t* dev_dtig, uint8_t* dev_gi, int32_t* dev_gorder, void* stream);
+
 /* Mean-shift clustering of pixel embeddings into initial masks (csrc/meanshift.hip): the UCN base model's clustering_features ->
  * mean_shift_smart_init (select_smart_seeds, seed_hill_climbing_ball, connected_components) and filter_labels_depth of the reference
  * (eval/base_model.py:622-840 and :34-47, cosine metric), which it runs as torch and Python loops per frame.  The numpy statement of

@@ -121,6 +121,7 @@ void quber_destroy(quber_ctx* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->perturb_ws) (void)hipFree(c->perturb_ws);
     if (c->masknms_ws) (void)hipFree(c->masknms_ws);
+    if (c->cocoap_ws) (void)hipFree(c->cocoap_ws);
     if (c->meanshift_ws) (void)hipFree(c->meanshift_ws);
     if (c->gms_ws) (void)hipFree(c->gms_ws);
     if (c->zoom_ws) (void)hipFree(c->zoom_ws);
@@ -550,6 +551,32 @@ int quber_mask_nms(quber_ctx* c, const uint8_t* masks, const float* scores, int3
     }
     return launch_mask_nms(masks, scores, batch, n_masks, H, W, thresh, on_top, out_masks, ids, source, out_scores, report, c->masknms_ws,
                            (hipStream_t)stream);
+}
+
+// ---- the per-frame half of COCO AP (cocoap.hip); usable on a context without a network ----
+int quber_coco_match(quber_ctx* c, const uint8_t* dt, const float* scores, const double* dt_boxes, int32_t n_dt, const uint8_t* gt,
+                     const uint8_t* gt_flags, const double* gt_area, const double* gt_boxes, int32_t n_gt, int32_t batch, int32_t iou_type,
+                     const double* iou_thrs, int32_t n_thrs, const double* area_rng, int32_t n_rng, int32_t* counts, int32_t* order,
+                     float* out_scores, double* dt_area, double* gt_area_used, double* iou, uint8_t* dtm, uint8_t* dtig, uint8_t* gi,
+                     int32_t* gorder, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_gt < 0 || n_gt > 1024) return fail("coco match: n_gt outside 0..1024");
+    if (iou_type != 0 && iou_type != 1) return fail("coco match: iou_type must be 0 (segm) or 1 (bbox)");
+    const int H = c->cfg.height, W = c->cfg.width;
+    const size_t need = coco_match_ws_bytes(batch, n_gt, H, W, iou_type);
+    if (need > c->cocoap_ws_bytes) {         // the only allocation of this entry: made on first use, kept, grown when a larger call comes
+        if (c->cocoap_ws) {
+            QB_CHECK(hipFree(c->cocoap_ws));                 // (waits for the launches that may still use it)
+            c->alloc_bytes -= c->cocoap_ws_bytes;
+            c->cocoap_ws = nullptr; c->cocoap_ws_bytes = 0;
+        }
+        QB_CHECK(hipMalloc(&c->cocoap_ws, need));
+        c->cocoap_ws_bytes = need;
+        c->alloc_bytes += need;
+    }
+    const CocoMatchArgs q{dt, scores, dt_boxes, n_dt, gt, gt_flags, gt_area, gt_boxes, n_gt, iou_type, iou_thrs, n_thrs, area_rng, n_rng,
+                          counts, order, out_scores, dt_area, gt_area_used, iou, dtm, dtig, gi, gorder};
+    return launch_coco_match(q, batch, H, W, c->cocoap_ws, (hipStream_t)stream);
 }
 
 // ---- mean-shift clustering of pixel embeddings into initial masks (meanshift.hip); usable on a context without a network ----

@@ -382,6 +382,18 @@ int launch_mask_nms(const uint8_t* masks, const float* scores, int B, int N, int
                     int* ids, int* source, float* out_scores, int* report, void* ws, hipStream_t st);
 size_t mask_nms_ws_bytes(int B, int N, int H, int W);
 int mask_nms_max();
+// the per-frame half of COCO AP (cocoap.hip): rank -> zero -> pack | boxes -> gram -> iou -> gorder -> match, all on `st`; the tensors of
+// quber_coco_match (include/quber_hip.h) under its names; ws: coco_match_ws_bytes(>= B, n_gt, H, W, iou_type) bytes
+struct CocoMatchArgs {
+    const uint8_t* dt; const float* scores; const double* dt_boxes; int n_dt;
+    const uint8_t* gt; const uint8_t* gt_flags; const double* gt_area; const double* gt_boxes; int n_gt;
+    int iou_type; const double* iou_thrs; int n_thrs; const double* area_rng; int n_rng;
+    int* counts; int* order; float* out_scores; double* dt_area; double* gt_area_used; double* iou;
+    uint8_t* dtm; uint8_t* dtig; uint8_t* gi; int* gorder;
+};
+int launch_coco_match(const CocoMatchArgs& q, int B, int H, int W, void* ws, hipStream_t st);
+size_t coco_match_ws_bytes(int B, int n_gt, int H, int W, int bbox);
+int coco_match_top();
 // mean-shift clustering of an embedding map f32 [B][64][H][W] into masks (meanshift.hip), all on `st`; ws: meanshift_ws_bytes(cap_b >= B, H, W)
 // bytes.  S seeds <= 128 and <= H W; Z f32 [B][S][64]; N planes <= 254; depth_z f32 [B][H][W] or null (no depth filter)
 int launch_meanshift_seeds(const float* X, const int* first, int B, int S, int H, int W, int* idx, void* ws, int cap_b, hipStream_t st);

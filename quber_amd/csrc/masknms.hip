@@ -23,6 +23,7 @@
 //   finish  a one-block compaction per frame of the ranks with visible pixels (by counting) -> source, scores, report, the table
 //           rank -> output id; then one pass writes the id map and ALL N output planes (0 / 255; zero planes behind `count`).
 // Integer and bit arithmetic except the one float32 expression; every output is overwritten by every call.
+#include "bitplane.h"       // mn_plane_words, mn_pack_word, mn_gram_tile
 #include "common.h"
 
 namespace quber {
@@ -36,18 +37,6 @@ constexpr int MN_T = 1024;
 static_assert(MN_TILE * MN_TILE == 256 && MN_SLAB % 4 == 0 && (MN_PITCH / 4) % 2 == 1 && MN_CHUNK % MN_SLAB == 0, "gram tile layout");
 static_assert(MN_TILE * (MN_SLAB / 4) == 256, "one 16-byte piece per lane stages a slab of one group");
 
-// words of one padded plane
-static inline long mn_plane_words(int H, int W) { return (((long)H * ((W + 31) / 32)) + 3) / 4 * 4; }
-
-// 0x01 per non-zero byte of w -> 4 bits (the multiplier moves bits 0, 8, 16, 24 to 21, 22, 23, 24; no two products share a bit)
-__device__ __forceinline__ unsigned mn_nibble(unsigned w) {
-    const unsigned nz = ((((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u) >> 7;
-    return ((nz * 0x00204081u) >> 21) & 0xfu;
-}
-__device__ __forceinline__ unsigned mn_bits16(uint4 v) {
-    return mn_nibble(v.x) | mn_nibble(v.y) << 4 | mn_nibble(v.z) << 8 | mn_nibble(v.w) << 12;
-}
-
 // grid (ceil(pw / 256), B * N).  One word per lane; the words behind H * wpr (the plane's padding) are written as zero.
 template <bool ALIGNED>
 __global__ __launch_bounds__(256) void mn_pack_kernel(const uint8_t* __restrict__ masks, unsigned* __restrict__ planes, int H, int W, int wpr,
@@ -55,18 +44,7 @@ __global__ __launch_bounds__(256) void mn_pack_kernel(const uint8_t* __restrict_
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= pw) return;
     const size_t m = blockIdx.y;
-    unsigned bits = 0;
-    if (i < H * wpr) {
-        const int y = i / wpr, x0 = (i - y * wpr) * 32;
-        const uint8_t* p = masks + m * (size_t)H * W + (size_t)y * W + x0;
-        if (ALIGNED) {                                       // W % 16 == 0 and a 16-byte aligned base: x0 + 16 <= W
-            bits = mn_bits16(*reinterpret_cast<const uint4*>(p));
-            if (x0 + 16 < W) bits |= mn_bits16(*reinterpret_cast<const uint4*>(p + 16)) << 16;
-        } else {
-            const int nb = min(32, W - x0);
-            for (int k = 0; k < nb; ++k) bits |= (unsigned)(p[k] != 0) << k;
-        }
-    }
+    const unsigned bits = i < H * wpr ? mn_pack_word<ALIGNED>(masks + m * (size_t)H * W, i, W, wpr) : 0u;
     planes[m * (size_t)pw + i] = bits;
 }
 
@@ -83,28 +61,11 @@ __global__ __launch_bounds__(256) void mn_gram_kernel(const unsigned* __restrict
     const int t = threadIdx.x, b = blockIdx.z;
     const int w0 = blockIdx.y * MN_CHUNK, w1 = min(w0 + MN_CHUNK, pw);
     const unsigned* base = planes + (size_t)b * N * pw;
-    // staging: lane t loads piece t % 16 (4 words) of row t / 16 of each group
-    const int srow = t >> 4, sq = (t & 15) * 4;
-    const int ma = ta * MN_TILE + srow, mb = tb * MN_TILE + srow;
+    // lane t stages row t / 16 of each group and owns the pair (row t / 16 of group A, row t % 16 of group B)
+    const int srow = t >> 4, ma = ta * MN_TILE + srow, mb = tb * MN_TILE + srow;
     const int ra = t >> 4, rb = t & 15;
-    unsigned acc = 0;
-    for (int w = w0; w < w1; w += MN_SLAB) {
-        const bool in = w + sq < w1;                         // pw and w are multiples of 4: a piece is inside or outside as a whole
-        uint4 va = make_uint4(0, 0, 0, 0), vb = va;
-        if (in && ma < N) va = *reinterpret_cast<const uint4*>(base + (size_t)ma * pw + w + sq);
-        if (in && mb < N) vb = *reinterpret_cast<const uint4*>(base + (size_t)mb * pw + w + sq);
-        __syncthreads();                                     // the previous step's reads are done
-        *reinterpret_cast<uint4*>(sm + srow * MN_PITCH + sq) = va;
-        *reinterpret_cast<uint4*>(sm + (MN_TILE + srow) * MN_PITCH + sq) = vb;
-        __syncthreads();
-        const uint4* pa = reinterpret_cast<const uint4*>(sm + ra * MN_PITCH);
-        const uint4* pb = reinterpret_cast<const uint4*>(sm + (MN_TILE + rb) * MN_PITCH);
-#pragma unroll
-        for (int k = 0; k < MN_SLAB / 4; ++k) {
-            const uint4 a = pa[k], c = pb[k];
-            acc += __popc(a.x & c.x) + __popc(a.y & c.y) + __popc(a.z & c.z) + __popc(a.w & c.w);
-        }
-    }
+    const unsigned acc = mn_gram_tile<MN_TILE, MN_SLAB, MN_PITCH>(ma < N ? base + (size_t)ma * pw : nullptr, mb < N ? base + (size_t)mb * pw : nullptr,
+                                                                  w0, w1, sm);
     const int i = ta * MN_TILE + ra, j = tb * MN_TILE + rb;
     if (i <= j && j < N && acc) atomicAdd(inter + ((size_t)b * N + i) * N + j, acc);
 }

@@ -260,6 +260,43 @@ class MaskRefiner:
             frames.append(dict(out["losses"]))
         return {"frames": frames, "mean": mean_losses(frames), "n": len(frames)}
 
+    # -- COCO AP of the initial and the refined masks (csrc/cocoap.hip; INTEGRATION.md "COCO AP of initial and refined masks") --
+    def validation_ap(self, items, anno_paths, workers=2, batch=1):
+        """The number the reference's COCOEvaluator prints after an evaluation period, for the refined masks and for the initial masks
+        they came from.  items: predict_stream's; anno_paths: one annotation file (or array) per item, read with load_annotation and
+        renumbered 1..n in ascending label order (compact_labels): one ground truth per label.  The initial masks are scored with the
+        item's mask_scores (else 1.0), the refined ones with the predictor's instance scores, taken with their masks from the device
+        tensors of the output dict.  -> {"initial": {"stats": f64 [12], "results": detectron2's dict}, "refined": {...}, "n": frames}."""
+        from collections import deque
+        from .coco_ap import CocoAP
+        dev = self.refiner_predictor.device
+        aps = {"initial": CocoAP("segm", dev), "refined": CocoAP("segm", dev)}
+        seen = deque()                               # (initial masks, rgb path, mask scores) of the items predict_stream has pulled, in order
+
+        def tee():
+            for item in items:
+                seen.append((item[2], item[0], item[4] if len(item) > 4 else None))
+                yield item
+
+        n = 0
+        for res, anno_path in zip(self.predict_stream(tee(), workers=workers, batch=batch), anno_paths):
+            init, rgb_path, init_scores = seen.popleft()
+            anno = load_annotation(anno_path, rgb_path, self.dataset, self._resize)
+            if anno.ndim != 2:
+                raise ValueError("annotation must be a single-channel label image")
+            gt = compact_labels(anno)
+            init = np.asarray(init)
+            init = (init != 0).reshape((-1,) + gt.shape)
+            scores = np.ones(len(init), np.float32) if init_scores is None else check_scores(init_scores, len(init))
+            aps["initial"].update(init, scores, gt)
+            inst = res[1].get("instances")
+            if inst is not None:
+                aps["refined"].update(inst.pred_masks, inst.scores, gt)
+            else:
+                aps["refined"].update(np.zeros((0,) + gt.shape, np.uint8), np.zeros(0, np.float32), gt)
+            n += 1
+        return dict({k: {"stats": ap.summarize(), "results": ap.results()} for k, ap in aps.items()}, n=n)
+
     # -- the predicted error maps of one frame: scored against a ground truth, painted over the image (csrc/errhead.hip) --
     def _error_engine(self, h, w, n_masks=64):
         return self.refiner_predictor.model.engine_for(h, w, 1, n_masks)
