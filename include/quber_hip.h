@@ -336,6 +336,47 @@ int quber_mask_nms(quber_ctx* ctx, const uint8_t* dev_masks, const float* dev_sc
                    int32_t on_top, uint8_t* dev_out_masks, int32_t* dev_ids, int32_t* dev_source, float* dev_out_scores,
                    int32_t* dev_report, void* stream);
 
+/* Scene-level perturbation (csrc/scene.hip): the instance list of a frame degraded the way the reference builds the initial masks its
+ * checkpoints were trained on (tools/ours/perturbate_masks.py:101-205, run there on the host with one full-frame numpy pass per pair of
+ * masks) - false positives and over- / under-segmentations from a pool of proposals, merging of masks within ten pixels, splits along
+ * an axis-aligned line, deletions.  The host draws every random decision (quber_amd/scene.py: scene_draws) and this call executes
+ * them.  The numpy statement of what it computes is tests/test_scene_cpu.py: scene_perturb_np; INTEGRATION.md "Scene-level
+ * perturbation" has it in words.
+ *   dev_gt u8 [B][n_gt_rows][H][W], dev_props u8 [B][n_prop_rows][H][W] in (non-zero = inside; NULL with zero rows);
+ *   dev_n_gt, dev_n_prop i32 [B]: the rows of each frame that exist (clamped to the row counts); the rows behind them are never read
+ *   dev_fp_act, dev_gs_act u8 [B][n_prop_rows]; dev_merge_act, dev_split_act, dev_delete_act u8 [B][max_masks];
+ *   dev_split_try i32 [B][max_masks][10][4], rows (x1, y1, axis, side), x1 / y1 clamped to the frame
+ *   lim = (double)(W * H) * min_mask_ratio; iou(A, B) = (|A n B| + 1e-6) / (|A u B| + 1e-6) in float64.  The list starts empty:
+ *   1. proposal q (ascending) is appended as a false positive when fp_act[q], not (|Q| < lim or |Q| > 2.0 * the largest ground truth's
+ *      area, 0 without ground truth) and max_g iou(G_g, Q) < 0.3 (the maximum starts at 0);
+ *   2. ... as an over- / under-segmentation when gs_act[q], |Q| >= lim and max_g iou(G_g, Q) > 0.3;
+ *   3. ground truth g (ascending) is appended when the maximum over the entries E of 1-2 of (|G n E| + 1e-6) / ((|G u E| - |G n E|) + 1e-6)
+ *      is < 0.3 (the symmetric difference: the reference's uint8 sum of a 0 / 1 and a 0 / 255 mask wraps);
+ *   4. touch(a, b) = dilate10(L_a) meets L_b, dilate10(E)(y, x) = OR over i, j in 0..9 of E(y + i - 5, x + j - 5); every slot starts
+ *      as its own member set; for idx1 ascending with merge_act[idx1]: A = S[idx1]; for idx2 != idx1 ascending: if some a in A and b
+ *      in S[idx2] touch, S[idx1] = A u S[idx2] (replaced, not accumulated) and S[idx2] = {}.  Every entry becomes the union of its
+ *      members' planes; entries without a pixel are removed, the order is kept;
+ *   5. for idx ascending (the entries of step 4 only) with split_act[idx]: the first of its ten attempts for which 255.0 * |E \ C| >= lim
+ *      and 255.0 * |E n C| >= lim, C = rows [y1, H - 1) (axis 0, side 0), rows [0, y1) (0, 1), columns [x1, W - 1) (1, 0), columns
+ *      [0, x1) (1, 1): the entry becomes E \ C and E n C is appended;
+ *   6. the entries idx of the list as it stands with delete_act[idx] are dropped, the order is kept.
+ *   An append that would make the list longer than max_masks is not performed (in 5: the whole split) and counted in `dropped`.
+ *   -> dev_out_masks u8 [B][max_masks][H][W], 0 / 255, zero planes behind count; any alignment
+ *   -> dev_info i32 [B][max_masks][4]: kind (0 ground truth, 1 false positive, 2 over- / under-segmentation), the source index of the
+ *      slot's own origin, the number of members, split (0 none, 1 the kept half, 2 the cut-off half); zero rows behind count
+ *   -> dev_report i32 [B][8]: count, n_fp, n_gs, ground truths kept, absorbed, splits, deleted, dropped
+ * Every output is overwritten by every call.  n_gt_rows + n_prop_rows <= 256 and 1 <= max_masks <= 256 (anything else is an error);
+ * any H and W up to 2^30 pixels.  Launches (zero, pack, gram, select, dilate, touch, merge, compose, decide, write) on `stream`; no host
+ * copy, no synchronisation, no memset node.  The workspace (bit planes, tables, prefix sums) is not part of quber_create: the first
+ * call allocates it for its batch, row counts and max_masks and keeps it, a call that needs a larger one replaces it
+ * (quber_workspace_bytes counts it); such a call is not capturable into a graph, the others are.  Works on a context created with
+ * with_network = 0; the row counts are not bounded by max_instances. */
+int quber_scene_perturb(quber_ctx* ctx, const uint8_t* dev_gt, const uint8_t* dev_props, const int32_t* dev_n_gt, const int32_t* dev_n_prop,
+                        int32_t batch, int32_t n_gt_rows, int32_t n_prop_rows, int32_t max_masks, double min_mask_ratio,
+                        const uint8_t* dev_fp_act, const uint8_t* dev_gs_act, const uint8_t* dev_merge_act, const uint8_t* dev_split_act,
+                        const int32_t* dev_split_try, const uint8_t* dev_delete_act, uint8_t* dev_out_masks, int32_t* dev_info,
+                        int32_t* dev_report, void* stream);
+
 /* COCO AP, the per-frame half (csrc/cocoap.hip): computeIoU + evaluateImg of the published COCOeval and bbIou / rleIou of its maskApi.c for
  * ONE category, which the reference runs on the host through pycocotools (train_net.py:57 COCOEvaluator(use_fast_impl=False),
  * maskrefiner/evaluation/instance_evaluation.py) on the masks, scores and boxes of model.py:318-356.  The numpy statement of what this call

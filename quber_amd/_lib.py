@@ -69,6 +69,7 @@ SIGNATURES = {
     "quber_cleanup_postprocess": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "quber_perturb_masks": (C.c_int, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P]),
     "quber_mask_nms": (C.c_int, [_P, _P, _P, _I, _I, C.c_float, _I, _P, _P, _P, _P, _P, _P]),
+    "quber_scene_perturb": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_double] + [_P] * 10),
     "quber_coco_match": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I] + [_P] * 11),
     "quber_meanshift_seeds": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P]),
     "quber_meanshift_climb": (C.c_int, [_P, _P, _I, _I, _P, _I, C.c_float, _I, _P, _P]),

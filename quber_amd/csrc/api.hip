@@ -122,6 +122,7 @@ void quber_destroy(quber_ctx* c) {
     if (c->perturb_ws) (void)hipFree(c->perturb_ws);
     if (c->masknms_ws) (void)hipFree(c->masknms_ws);
     if (c->cocoap_ws) (void)hipFree(c->cocoap_ws);
+    if (c->scene_ws) (void)hipFree(c->scene_ws);
     if (c->meanshift_ws) (void)hipFree(c->meanshift_ws);
     if (c->gms_ws) (void)hipFree(c->gms_ws);
     if (c->zoom_ws) (void)hipFree(c->zoom_ws);
@@ -551,6 +552,37 @@ int quber_mask_nms(quber_ctx* c, const uint8_t* masks, const float* scores, int3
     }
     return launch_mask_nms(masks, scores, batch, n_masks, H, W, thresh, on_top, out_masks, ids, source, out_scores, report, c->masknms_ws,
                            (hipStream_t)stream);
+}
+
+// ---- scene-level perturbation of a frame's instance list (scene.hip); usable on a context without a network ----
+int quber_scene_perturb(quber_ctx* c, const uint8_t* gt, const uint8_t* props, const int32_t* n_gt, const int32_t* n_prop, int32_t batch,
+                        int32_t n_gt_rows, int32_t n_prop_rows, int32_t max_masks, double min_mask_ratio, const uint8_t* fp_act,
+                        const uint8_t* gs_act, const uint8_t* merge_act, const uint8_t* split_act, const int32_t* split_try,
+                        const uint8_t* delete_act, uint8_t* out_masks, int32_t* info, int32_t* report, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_gt_rows < 0 || n_prop_rows < 0 || (long)n_gt_rows + n_prop_rows > scene_max())
+        return fail("scene perturb: n_gt_rows + n_prop_rows outside 0..256");
+    if (max_masks < 1 || max_masks > scene_max()) return fail("scene perturb: max_masks outside 1..256");
+    if (!(min_mask_ratio >= 0.0 && min_mask_ratio <= 1.0)) return fail("scene perturb: min_mask_ratio outside 0..1");
+    const int H = c->cfg.height, W = c->cfg.width;
+    if ((long)H * W > (1L << 30)) return fail("scene perturb: a frame of more than 2^30 pixels");
+    if (!n_gt || !n_prop || !merge_act || !split_act || !split_try || !delete_act || !out_masks || !info || !report || (n_gt_rows > 0 && !gt) ||
+        (n_prop_rows > 0 && (!props || !fp_act || !gs_act)))
+        return fail("scene perturb: null tensor");
+    const size_t need = scene_ws_bytes(batch, n_gt_rows + n_prop_rows, max_masks, H, W);
+    if (need > c->scene_ws_bytes) {          // the only allocation of this entry: made on first use, kept, grown when a larger call comes
+        if (c->scene_ws) {
+            QB_CHECK(hipFree(c->scene_ws));                  // (waits for the launches that may still use it)
+            c->alloc_bytes -= c->scene_ws_bytes;
+            c->scene_ws = nullptr; c->scene_ws_bytes = 0;
+        }
+        QB_CHECK(hipMalloc(&c->scene_ws, need));
+        c->scene_ws_bytes = need;
+        c->alloc_bytes += need;
+    }
+    const ScenePerturbArgs q{gt, props, n_gt, n_prop, n_gt_rows, n_prop_rows, max_masks, min_mask_ratio, fp_act, gs_act, merge_act, split_act,
+                             split_try, delete_act, out_masks, info, report};
+    return launch_scene_perturb(q, batch, H, W, c->scene_ws, (hipStream_t)stream);
 }
 
 // ---- the per-frame half of COCO AP (cocoap.hip); usable on a context without a network ----

@@ -382,6 +382,16 @@ int launch_mask_nms(const uint8_t* masks, const float* scores, int B, int N, int
                     int* ids, int* source, float* out_scores, int* report, void* ws, hipStream_t st);
 size_t mask_nms_ws_bytes(int B, int N, int H, int W);
 int mask_nms_max();
+// scene-level perturbation of a frame's instance list (scene.hip): pack -> gram -> select -> dilate -> touch -> merge -> compose -> decide ->
+// write, all on `st`; the tensors of quber_scene_perturb (include/quber_hip.h) under its names; ws: scene_ws_bytes(>= B, N + P, M, H, W) bytes
+struct ScenePerturbArgs {
+    const uint8_t* gt; const uint8_t* props; const int* n_gt; const int* n_prop; int N; int P; int M; double min_mask_ratio;
+    const uint8_t* fp_act; const uint8_t* gs_act; const uint8_t* merge_act; const uint8_t* split_act; const int* split_try;
+    const uint8_t* delete_act; uint8_t* out_masks; int* info; int* report;
+};
+int launch_scene_perturb(const ScenePerturbArgs& q, int B, int H, int W, void* ws, hipStream_t st);
+size_t scene_ws_bytes(int B, int S, int M, int H, int W);
+int scene_max();
 // the per-frame half of COCO AP (cocoap.hip): rank -> zero -> pack | boxes -> gram -> iou -> gorder -> match, all on `st`; the tensors of
 // quber_coco_match (include/quber_hip.h) under its names; ws: coco_match_ws_bytes(>= B, n_gt, H, W, iou_type) bytes
 struct CocoMatchArgs {

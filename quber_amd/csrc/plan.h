@@ -81,6 +81,8 @@ struct quber_ctx {
     size_t masknms_ws_bytes = 0;
     void* cocoap_ws = nullptr;    // bit planes, pair table, areas and boxes of quber_coco_match: allocated on first use, grown on demand
     size_t cocoap_ws_bytes = 0;
+    void* scene_ws = nullptr;     // bit planes, pair and touch tables, member sets, prefix sums of quber_scene_perturb: allocated on first use, grown on demand
+    size_t scene_ws_bytes = 0;
     void* meanshift_ws = nullptr; // seed slots, histograms, running minimum, raw labels, block partials of the mean-shift entries (meanshift.hip): allocated by their first call
     void* gms_ws = nullptr;       // counts, compacted points, running minimum, raw labels, tables, block partials of the Gaussian mean-shift entries (gms.hip): allocated by their first call
     void* zoom_ws = nullptr;      // extents, keep flags, depth keys, paint order, key map of the zoom-in entries (zoom.hip): allocated by their first call

@@ -539,6 +539,36 @@ class Engine:
                                                _ptr(out_scores), _ptr(report), _stream()))
         return {"masks": out, "ids": ids, "source": source, "scores": out_scores, "report": report}
 
+    # ---- scene-level perturbation of a frame's instance list (csrc/scene.hip; INTEGRATION.md "Scene-level perturbation") ----
+    def scene_perturb(self, gt, props, n_gt, n_prop, draws, max_masks, min_mask_ratio=0.01, out=None, info=None, report=None):
+        """gt u8 [B,N,H,W], props u8 [B,P,H,W] (non-zero = inside; N or P may be 0), n_gt / n_prop i32 [B]: the rows of each frame that
+        exist, draws: the tables of scene.ScenePerturb.draws() / scene.scene_draws() as device tensors (fp_act, gs_act u8 [B,P];
+        merge_act, split_act, delete_act u8 [B,M]; split_try i32 [B,M,10,4]), all on the device -> {"masks": u8 [B,M,H,W] of 0 / 255,
+        zero planes behind count; "info": i32 [B,M,4] (kind, source, members, split); "report": i32 [B,8] (count, n_fp, n_gs, ground
+        truths kept, absorbed, splits, deleted, dropped)}.  N + P <= 256, M = max_masks <= 256.  Nothing is copied to the host; the
+        first call on an engine (and one that needs a larger workspace) allocates and cannot be captured into a graph."""
+        B, N, P, M, dev = gt.shape[0], gt.shape[1], props.shape[1], int(max_masks), self.device
+        assert gt.dtype == torch.uint8 and gt.is_contiguous() and gt.shape == (B, N, self.H, self.W)
+        assert props.dtype == torch.uint8 and props.is_contiguous() and props.shape == (B, P, self.H, self.W)
+        for t in (n_gt, n_prop):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.shape == (B,)
+        for key, shape, dtype in (("fp_act", (B, P), torch.uint8), ("gs_act", (B, P), torch.uint8), ("merge_act", (B, M), torch.uint8),
+                                  ("split_act", (B, M), torch.uint8), ("delete_act", (B, M), torch.uint8), ("split_try", (B, M, 10, 4), torch.int32)):
+            t = draws[key]
+            assert t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape and t.device == gt.device, key
+        out = torch.empty((B, M, self.H, self.W), dtype=torch.uint8, device=dev) if out is None else out
+        info = torch.empty((B, M, 4), dtype=torch.int32, device=dev) if info is None else info
+        report = torch.empty((B, 8), dtype=torch.int32, device=dev) if report is None else report
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (B, M, self.H, self.W)
+        assert info.dtype == torch.int32 and info.is_contiguous() and info.shape == (B, M, 4)
+        assert report.dtype == torch.int32 and report.is_contiguous() and report.shape == (B, 8)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_scene_perturb(self.h, _ptr(gt) if N else None, _ptr(props) if P else None, _ptr(n_gt), _ptr(n_prop), B, N, P, M,
+                                                    float(min_mask_ratio), _ptr(draws["fp_act"]) if P else None, _ptr(draws["gs_act"]) if P else None,
+                                                    _ptr(draws["merge_act"]), _ptr(draws["split_act"]), _ptr(draws["split_try"]),
+                                                    _ptr(draws["delete_act"]), _ptr(out), _ptr(info), _ptr(report), _stream()))
+        return {"masks": out, "info": info, "report": report}
+
     # ---- mean-shift clustering of pixel embeddings (csrc/meanshift.hip; INTEGRATION.md "Initial masks from pixel embeddings") ----
     def _ms_tensor(self, t, dtype, shape, what):
         if t is None:

@@ -132,15 +132,17 @@ class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
                  lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
                  decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
-                 nms=None, zoom=None, losses=None):
-        # tta ... losses: the predictor's options (maskrefiner/predictor.py: module docstring, RefineOptions), for predict()
+                 nms=None, zoom=None, losses=None, scene=None):
+        # tta ... scene: the predictor's options (maskrefiner/predictor.py: module docstring, RefineOptions), for predict()
         # and predict_stream(batch=k) alike, except: until_converged stops early in predict() only (the stream always runs the fixed
         # count); cleanup "largest" is the UOIS path's largest_connected_component (4-connected), "holes" the SAM refiner's
         # remove_small_regions(mask, 300, "holes"); nms takes its scores from predict(..., mask_scores=) and a fifth element of
         # predict_stream's items; zoom is predict() only: predict_stream refuses it; losses (a quber_amd.losses.Losses) acts in
-        # predict(..., gt_labels=) and validation_losses() - the stream carries no ground truth
+        # predict(..., gt_labels=) and validation_losses() - the stream carries no ground truth; scene (a quber_amd.scene.ScenePerturb)
+        # takes initial_masks as the frame's ground truth and predict(..., proposals=) as its pool of segments: predict_stream refuses it
         options = RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
-                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom, losses=losses)
+                                      track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom, losses=losses,
+                                      scene=scene)
         self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, options=options)
         self.dataset = dataset
         self.lmffnet = None
@@ -198,13 +200,14 @@ class MaskRefiner:
         return {"rgb": np.ascontiguousarray(rgb), "depth": depth, "masks": initial_masks, "zero_depth": zero_depth, "depth_dev": d_dev,
                 "scores": scores}
 
-    def _refine(self, fr, gt_labels=None):
+    def _refine(self, fr, gt_labels=None, proposals=None):
         """The reference's timed region and what follows it (eval/refiner_model.py:265-297) on a loaded frame."""
         start = time.time()
+        kw = {} if proposals is None else {"proposals": proposals}
         if self.dataset == "armbench":
-            output = self.refiner_predictor.predict(fr["rgb"], None, fr["masks"], fr["scores"], gt_labels=gt_labels)[0]
+            output = self.refiner_predictor.predict(fr["rgb"], None, fr["masks"], fr["scores"], gt_labels=gt_labels, **kw)[0]
         else:
-            output = self.refiner_predictor.predict(fr["rgb"], fr["depth"], fr["masks"], fr["scores"], gt_labels=gt_labels)[0]
+            output = self.refiner_predictor.predict(fr["rgb"], fr["depth"], fr["masks"], fr["scores"], gt_labels=gt_labels, **kw)[0]
         refined = output["instances"].to("cpu").pred_masks.numpy() if "instances" in output else []
         return self._finish(fr, output, refined, start)
 
@@ -233,8 +236,14 @@ class MaskRefiner:
             refined = np.asarray(out)
         return refined, output, elapsed, fg
 
-    def predict(self, rgb_path, depth_path, initial_masks, fg_mask=None, mask_scores=None, gt_labels=None):
-        return self._refine(self._load(rgb_path, depth_path, initial_masks, mask_scores), gt_labels)
+    def predict(self, rgb_path, depth_path, initial_masks, fg_mask=None, mask_scores=None, gt_labels=None, proposals=None):
+        # proposals (with scene=): u8 / bool [P,H,W] at the size of initial_masks - the pool the scene perturbation draws false positives
+        # and over- / under-segmentations from; may be absent
+        fr = self._load(rgb_path, depth_path, initial_masks, mask_scores)
+        if proposals is not None and self.dataset == "armbench" and len(proposals):
+            h, w = fr["rgb"].shape[:2]
+            proposals = np.array([self._resize(m, h, w, linear=False) for m in mask_bytes(proposals, True)])
+        return self._refine(fr, gt_labels, proposals)
 
     # -- the reference's validation losses (csrc/losses.hip; INTEGRATION.md "Validation losses") --
     def validation_losses(self, output_or_items, anno_paths=None):
@@ -356,6 +365,8 @@ class MaskRefiner:
         logits in the last bits (split-K partitions follow the launch size), which tests/test_gpu_network.py bounds and explains."""
         if self.refiner_predictor.zoom is not None:
             raise ValueError("zoom: predict_stream has no zoomed form; call predict() per frame (or construct without zoom=)")
+        if self.refiner_predictor.scene is not None:
+            raise ValueError("scene: predict_stream has no scene form; call predict() per frame (or construct without scene=)")
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         import threading

@@ -68,6 +68,14 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
     the pass's final logits (the merged ones under ``tta``).  Every dict gains ``losses`` ({loss_sem_seg, loss_center, loss_offset,
     loss_eee_*: float}, per frame), ``loss_terms`` (the raw sums) and, with ``keep_targets=True``, ``loss_targets``.  Refused together
     with ``iterations > 1`` or ``zoom=``.  Default, or a call without ``gt_labels``: nothing launched, today's keys.
+  * ``scene=ScenePerturb(seed=0, max_masks=64, min_mask_ratio=0.01)``: the call's masks are the frame's GROUND TRUTH and its instance list
+    is degraded on the device the way the reference builds its training inputs (tools/ours/perturbate_masks.py:101-205: false
+    positives and over- / under-segmentations from ``proposals=`` (u8 / bool [P,H,W] per frame, may be absent), merge, split, delete:
+    csrc/scene.hip; INTEGRATION.md "Scene-level perturbation") after ``nms`` and before ``perturb``; the mask rows of the pass are
+    ``max_masks`` and everything downstream sees the scene's masks as THE initial masks.  Every dict gains ``scene_masks`` (u8
+    [count,H,W], 0 / 255), ``scene_info`` (i64 [count,4]: kind, source, members, split) and ``scene_report`` (i64 [8]: count, n_fp, n_gs,
+    ground truths kept, absorbed, splits, deleted, dropped).  ``predict`` and ``predict_batch``; refused together with ``cluster=`` or
+    ``zoom=`` and in ``enqueue_batch`` / ``predict_stream``.  Default: none, today's keys, nothing launched or allocated.
 There is no CPU fallback: construction fails if the HIP library or a GPU is missing.
 """
 import os
@@ -83,6 +91,7 @@ from ..masknms import MaskNMS, check_scores
 from ..gms import IMP_LDS_BYTES, GaussianMeanShift, imp_plane_bytes
 from ..meanshift import CHANNELS as CLUSTER_CHANNELS, MeanShift
 from ..perturb import Perturb
+from ..scene import MAX_SLOTS as SCENE_MAX_SLOTS, ScenePerturb
 from ..structures import Boxes, Instances
 from ..losses import Losses
 from ..zoom import ZoomIn
@@ -142,10 +151,11 @@ class RefineOptions:
     zoom: ZoomIn = None               # a second pass on a padded, resized crop of every instance, pasted back on the device
     losses: Losses = None             # with a call's gt_labels=: the reference's training targets and loss dict of every frame, on the device
     cluster: object = None            # a MeanShift (pixel embeddings) or a GaussianMeanShift (centre votes): the initial masks are clustered on the device, before anything else
+    scene: ScenePerturb = None        # the uploaded masks are a frame's ground truth: its instance list is degraded on the device (after nms, before perturb)
 
     @classmethod
     def parse(cls, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
-              nms=None, zoom=None, losses=None, cluster=None):
+              nms=None, zoom=None, losses=None, cluster=None, scene=None):
         if int(iterations) < 1:
             raise ValueError("iterations must be >= 1")
         losses = Losses.parse(losses)
@@ -162,8 +172,13 @@ class RefineOptions:
             cluster = MeanShift.parse(cluster)
         if cluster is not None and nms is not None:
             raise ValueError("cluster: not with nms= (the clustering's masks are disjoint and have no scores)")
+        scene = ScenePerturb.parse(scene)
+        if scene is not None and cluster is not None:
+            raise ValueError("scene: not with cluster= (the clustering's masks are no ground truth: left out)")
+        if scene is not None and zoom is not None:
+            raise ValueError("scene: not with zoom= (left out)")
         return cls(bool(tta), bool(decode_errors), int(iterations), bool(until_converged), bool(track_initial), Cleanup.parse(cleanup),
-                   perturb, nms, zoom, losses, cluster)
+                   perturb, nms, zoom, losses, cluster, scene)
 
     def for_crops(self):
         """The crop pass of zoom: the same tta, iterations and cleanup; nothing that concerns the caller's initial masks."""
@@ -173,7 +188,7 @@ class RefineOptions:
 @dataclass(slots=True)
 class PassResult:
     """What device_pass enqueued for B frames: the engine, the last pass's logits and post tables, the initial masks u8 [B,N,H,W] as
-    the network saw them, and what refine() / track() / decode() / perturb_masks() / nms_masks() returned (None: option off).  own: per
+    the network saw them, and what refine() / track() / decode() / perturb_masks() / nms_masks() / scene_masks() returned (None: option off; own_nm: under scene, the NMS's own counts).  own: per
     frame, how many of the N mask rows are the frame's own - the rows of initial_overlap, perturbed_masks and nms_masks; a sequence
     indexed by frame (under nms in the stream: a pinned tensor the NMS's counts are copied into, valid once e1 has passed).
     enqueue_batch alone fills the rest - this record is its handle: the pre-extracted masks u8 [B,slots,H,W], the pinned instance
@@ -191,6 +206,8 @@ class PassResult:
     nm: dict = None
     cl: dict = None
     ls: dict = None
+    sn: dict = None
+    own_nm: object = None
     masks: object = None
     slots: int = 0
     count: object = None
@@ -257,16 +274,17 @@ class RefinerModel:
     (reference MaskRefiner.forward, model.py:115-358).  Engines are cached per (H, W, batch capacity)."""
 
     def __init__(self, cfg, state_dict, device, tta=False, decode_errors=False, iterations=1, until_converged=False,
-                 track_initial=False, cleanup=None, perturb=None, nms=None, zoom=None, losses=None, cluster=None, options=None):
-        # options: a RefineOptions in place of the eleven keywords.  Its fields become plain attributes, which is what the code below
+                 track_initial=False, cleanup=None, perturb=None, nms=None, zoom=None, losses=None, cluster=None, scene=None, options=None):
+        # options: a RefineOptions in place of the twelve keywords.  Its fields become plain attributes, which is what the code below
         # reads (a test and a tool switch model.decode_errors between calls)
         self.options = options or RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
                                                       track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom,
-                                                      losses=losses, cluster=cluster)
+                                                      losses=losses, cluster=cluster, scene=scene)
         vars(self).update(vars(self.options))
         self._zoom_model = None   # the crop pass: a RefinerModel on the same cfg and weights, built by the first zoomed call
         self.debug_zoom = None    # tests: a list that receives, per zoomed call, the inputs and outputs of every stage
         self._perturb_dev = {}    # (frames, masks, H, W) -> the programs and targets of such a call on the device
+        self._scene_dev = {}      # (frames, proposal rows, H, W) -> the draw tables of such a call on the device
         self.cfg = cfg
         self.state_dict = state_dict
         self.device = torch.device(device)
@@ -353,6 +371,25 @@ class RefinerModel:
             cl = eng.meanshift(emb, first, self.cluster, d_masks.shape[1], z)
         d_masks[:B].copy_(cl["masks"])
         return cl
+
+    def scene_masks(self, eng, d_masks, scene_in, nm, B):
+        """scene: the first B frames of d_masks u8 [>= B,M,H,W] (device), M = scene.max_masks, are FILLED with the instance list the scene
+        perturbation makes of scene_in = (ground truth u8 [B,N,H,W] - after nms when that is set -, n_gt i32 [B], proposals u8 [B,P,H,W],
+        n_prop i32 [B]), all on the device; nm: what nms_masks returned for the ground truth (its count is then each frame's n_gt).
+        -> what Engine.scene_perturb returns."""
+        gt, n_gt, props, n_prop = scene_in
+        if nm is not None:
+            n_gt = nm["report"][:, 0].contiguous()
+        P, key = props.shape[1], (B, props.shape[1], eng.H, eng.W)
+        if key not in self._scene_dev:
+            if len(self._scene_dev) >= 8:
+                self._scene_dev.pop(next(iter(self._scene_dev)))
+            d = self.scene.draws(B, P, eng.H, eng.W)
+            self._scene_dev[key] = {k: torch.from_numpy(d[k].copy()).to(self.device) for k in
+                                    ("fp_act", "gs_act", "merge_act", "split_act", "split_try", "delete_act")}
+        sn = eng.scene_perturb(gt, props, n_gt, n_prop, self._scene_dev[key], self.scene.max_masks, self.scene.min_mask_ratio)
+        d_masks[:B].copy_(sn["masks"])
+        return sn
 
     def perturb_masks(self, eng, d_masks, B):
         """perturb: the first B frames of d_masks u8 [>= B,N,H,W] (device) are replaced by their perturbed versions, in place as far as
@@ -492,8 +529,8 @@ class RefinerModel:
             explicit = eng.error_maps(init, gt_masks)
         return {"rec": eng.losses(logits, tg["targets"], explicit, self.losses, heads=heads), "targets": tg, "heads": heads, "explicit": explicit}
 
-    def device_pass(self, eng, bgr, depth, masks, scores, B, *, may_stop, bufs=None, own=None, slots=None, gt=None, cluster_in=None):
-        """Enqueues cluster (cluster_in: see cluster_masks) -> nms -> perturb -> encode (tta: mirror, encode) -> forward -> postprocess ->
+    def device_pass(self, eng, bgr, depth, masks, scores, B, *, may_stop, bufs=None, own=None, slots=None, gt=None, cluster_in=None, scene_in=None):
+        """Enqueues cluster (cluster_in: see cluster_masks) -> nms -> scene (scene_in: see scene_masks; nms then runs on ITS ground truth) -> perturb -> encode (tta: mirror, encode) -> forward -> postprocess ->
         refine -> track -> decode for B frames on the current stream -> PassResult.  bgr / depth (or None) u8 [f*B,H,W,3] and masks u8 [f*B,N,H,W] on the device, f = 2 under tta
         with the frames in the first halves; scores f32 [B,N] (required with nms).  Nothing is read back unless may_stop and
         until_converged (refine()).  bufs: predict_one's _FrameStaging - its offsets, post tables, iteration buffers and overlap tables
@@ -501,7 +538,14 @@ class RefinerModel:
         of every frame are extracted between track and decode, where the stream has always launched that."""
         N = masks.shape[1]
         cl = self.cluster_masks(eng, masks, cluster_in, B)
-        nm = self.nms_masks(eng, masks, scores, B)
+        sn = None
+        if self.scene is not None:
+            if scene_in is None:
+                raise ValueError("scene: this call path has no scene form (predict and predict_batch have)")
+            nm = self.nms_masks(eng, scene_in[0], scores, B)
+            sn = self.scene_masks(eng, masks, scene_in, nm, B)
+        else:
+            nm = self.nms_masks(eng, masks, scores, B)
         pt = self.perturb_masks(eng, masks, B)            # before the mirror, the encoding and everything else that reads the masks
         offsets = bufs.offsets if bufs is not None else None
         if self.tta:                                      # (either way the logits are a fresh tensor, owned by the caller through the dict)
@@ -512,7 +556,7 @@ class RefinerModel:
         logits, post, it = self.refine(eng, bgr, depth, logits, post, B, may_stop, bufs.iter_bufs if bufs is not None else None)
         d_masks = masks[:B]
         ov = self.track(eng, d_masks, post, it, (bufs.overlap[0][:, :N], bufs.overlap[1]) if bufs is not None and self.track_initial else None)
-        rec = PassResult(eng, B, logits, post, d_masks=d_masks, own=[N] * B if own is None else own, it=it, ov=ov, pt=pt, nm=nm, cl=cl)
+        rec = PassResult(eng, B, logits, post, d_masks=d_masks, own=[N] * B if own is None else own, it=it, ov=ov, pt=pt, nm=nm, cl=cl, sn=sn)
         if slots is not None:
             rec.slots = min(max(1, slots), eng.cap)
             rec.masks = eng.extract_masks(post, rec.slots)
@@ -606,7 +650,8 @@ class RefinerModel:
             if mh is not None:
                 r[head + "_mask_hist"] = mh[b]
         if nm is not None:
-            r["nms_masks"], r["nms_source"], r["nms_scores"] = nm["masks"][b, :n], nm["source"][b, :n].to(torch.int64), nm["scores"][b, :n]
+            nn = n if rec.own_nm is None else int(rec.own_nm[b])
+            r["nms_masks"], r["nms_source"], r["nms_scores"] = nm["masks"][b, :nn], nm["source"][b, :nn].to(torch.int64), nm["scores"][b, :nn]
             r["nms_report"] = nm["report"][b, :2].to(torch.int64)
         if rec.cl is not None:
             cl = rec.cl
@@ -614,6 +659,9 @@ class RefinerModel:
             r["cluster_report"] = cl["report"][b].to(torch.int64)
             if "raw_ids" in cl:                              # a GaussianMeanShift: the map before the IMP, and the clusters' centres
                 r["cluster_raw_ids"], r["cluster_centers"] = cl["raw_ids"][b], cl["centers"][b, :n]
+        if rec.sn is not None:
+            r["scene_masks"], r["scene_info"] = rec.sn["masks"][b, :n], rec.sn["info"][b, :n].to(torch.int64)
+            r["scene_report"] = rec.sn["report"][b].to(torch.int64)
         if pt is not None:
             r["perturbed_masks"], r["perturb_report"] = pt[0][b, :n], pt[1][b, :n].to(torch.int64)
         if it is not None:
@@ -648,6 +696,9 @@ class RefinerModel:
             rec.own = [int(c) for c in rec.nm["report"][:, 0].cpu().numpy()]
         if rec.cl is not None:
             rec.own = [int(c) for c in rec.cl["report"][:, 0].cpu().numpy()]
+        if rec.sn is not None:                       # the scene's list is what the network saw; the NMS's counts keep their own rows
+            rec.own_nm = rec.own if rec.nm is not None else None
+            rec.own = [int(c) for c in rec.sn["report"][:, 0].cpu().numpy()]
         count = post["count"].cpu().numpy()
         conv = rec.it["conv"].cpu().numpy() if rec.it is not None else np.zeros((B,), np.int32)
         if rec.ls is not None:
@@ -673,6 +724,8 @@ class RefinerModel:
             raise ValueError("zoom: predict_one has no zoomed form; MaskRefinerPredictor.predict takes the batched path")
         if self.cluster is not None:
             raise ValueError("cluster: predict_one has no clustering form; MaskRefinerPredictor.predict takes the batched path")
+        if self.scene is not None:
+            raise ValueError("scene: predict_one has no scene form; MaskRefinerPredictor.predict takes the batched path")
         H, W = bgr.shape[:2]
         n = int(masks.shape[0])
         f = 2 if self.tta else 1                     # frames on the device: the frame [and its mirror]
@@ -739,6 +792,8 @@ class RefinerModel:
             raise ValueError("zoom: enqueue_batch / predict_stream have no zoomed form; use predict or predict_batch")
         if self.cluster is not None:
             raise ValueError("cluster: enqueue_batch / predict_stream have no clustering form; use predict or predict_batch")
+        if self.scene is not None:
+            raise ValueError("scene: enqueue_batch / predict_stream have no scene form; use predict or predict_batch")
         if halves:
             assert self.tta and d_bgr.shape[0] % 2 == 0
         B, H, W = d_bgr.shape[:3]
@@ -861,11 +916,11 @@ class RefinerModel:
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
                  seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False,
-                 cleanup=None, perturb=None, nms=None, zoom=None, losses=None, cluster=None, options=None):
+                 cleanup=None, perturb=None, nms=None, zoom=None, losses=None, cluster=None, scene=None, options=None):
         # the options (module docstring), checked before anything is loaded; options: a RefineOptions in their place
         self.options = options or RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
                                                       track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom,
-                                                      losses=losses, cluster=cluster)
+                                                      losses=losses, cluster=cluster, scene=scene)
         vars(self).update(vars(self.options))
         if config_file is None:
             self.cfg = qconfig.canonical_cfg()
@@ -897,7 +952,7 @@ class MaskRefinerPredictor:
 
     # -- reference signature (predictor.py:287) --
     def predict(self, rgb_img, depth_img=None, perturbed_masks=None, mask_scores=None, gt_labels=None, embeddings=None, depth_z=None,
-                center_votes=None, fg=None):
+                center_votes=None, fg=None, proposals=None):
         # gt_labels (with losses=): the frame's ground-truth label map, integer [H,W], 0 = none, 1..n; the dict then carries `losses`
         # embeddings (with cluster=, in place of perturbed_masks): f32 [64,H,W]; depth_z: f32 [H,W], the depth filter's plane
         # center_votes, fg (with cluster=GaussianMeanShift(), in place of perturbed_masks): f32 [3,H,W] = xyz + offsets, and u8 / bool [H,W]
@@ -912,6 +967,10 @@ class MaskRefinerPredictor:
                                       center_votes=None if center_votes is None else [center_votes], fg=None if fg is None else [fg])
         masks = np.zeros((0,) + rgb_img.shape[:2], np.uint8) if perturbed_masks is None else np.asarray(perturbed_masks)
         gts = None if gt_labels is None else [gt_labels]
+        if self.scene is not None or proposals is not None:      # the general path; proposals (with scene=): u8 / bool [P,H,W], may be absent
+            return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks],
+                                      None if mask_scores is None else [mask_scores], gt_labels=gts,
+                                      proposals=None if proposals is None else [proposals])
         if self.nms is not None:                          # the general path: how many masks there are is known on the device only
             return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], [masks], [mask_scores], gt_labels=gts)
         if self.zoom is not None:                         # the general path: it keeps the frame on the device for the crops
@@ -941,6 +1000,28 @@ class MaskRefinerPredictor:
         if self.cluster.imp is not None and imp_plane_bytes(H, W) > IMP_LDS_BYTES:
             raise ValueError(f"cluster: the IMP's two bit planes of a {H} x {W} frame do not fit the LDS; there is no global-memory fallback")
         return votes, np.ascontiguousarray((on != 0).astype(np.uint8))
+
+    def _scene_inputs(self, B, H, W, proposals):
+        """scene=: the checked proposals of a call -> (u8 [B,P,H,W] with P = the longest list, zero rows behind a frame's own; their
+        counts), before anything is uploaded or launched; None without scene=."""
+        if self.scene is None:
+            if proposals is not None:
+                raise ValueError("proposals= needs scene= (a quber_amd.scene.ScenePerturb)")
+            return None
+        if proposals is None:
+            proposals = [np.zeros((0, H, W), np.uint8)] * B
+        if len(proposals) != B:
+            raise ValueError(f"scene: proposals of {len(proposals)} frames for a batch of {B}")
+        arrs = []
+        for b, p in enumerate(proposals):
+            p = np.zeros((0, H, W), np.uint8) if p is None else np.asarray(p)
+            if p.ndim != 3 or p.shape[1:] != (H, W) or p.dtype not in (np.uint8, np.bool_):
+                raise ValueError(f"scene: the proposals of frame {b} have shape {p.shape} and dtype {p.dtype}, expected (P, {H}, {W}) of uint8 or bool")
+            arrs.append(p)
+        out = np.zeros((B, max(len(p) for p in arrs), H, W), np.uint8)
+        for b, p in enumerate(arrs):
+            out[b, :len(p)] = p != 0
+        return out, [len(p) for p in arrs]
 
     def _cluster_inputs(self, B, H, W, masks_list, scores_list, embeddings, depth_z, center_votes=None, fg=None):
         """cluster=: the checked host arrays (embeddings f32 [B,64,H,W], depth_z f32 [B,H,W] or None) of a call, before anything is
@@ -979,12 +1060,14 @@ class MaskRefinerPredictor:
         return emb, z
 
     def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None, gt_labels=None, embeddings=None, depth_z=None,
-                      center_votes=None, fg=None):
+                      center_votes=None, fg=None, proposals=None):
         """rgb_imgs/depth_imgs: u8 [B,H,W,3] arrays; masks_list: B arrays u8/bool [N_b,H,W]; scores_list (required with nms=): B arrays
         [N_b] of finite scores; gt_labels (with losses=): the B ground-truth label maps, integer [B,H,W] or a list.  With cluster=:
         masks_list is None, embeddings: B arrays f32 [64,H,W], depth_z: B arrays f32 [H,W] (with depth_threshold); or, with a
-        GaussianMeanShift, center_votes: B arrays f32 [3,H,W] and fg: B arrays u8 / bool [H,W].  -> list of B dicts."""
+        GaussianMeanShift, center_votes: B arrays f32 [3,H,W] and fg: B arrays u8 / bool [H,W].  With scene=: masks_list holds every frame's
+        GROUND TRUTH and proposals (optional) B arrays u8 / bool [P_b,H,W], the pool of segment proposals.  -> list of B dicts."""
         B, H, W = rgb_imgs.shape[:3]
+        props = self._scene_inputs(B, H, W, proposals)
         cluster_in = self._cluster_inputs(B, H, W, masks_list, scores_list, embeddings, depth_z, center_votes, fg)
         gms = isinstance(self.cluster, GaussianMeanShift)
         # rows of the mask tensor per frame; with cluster=: one plane per cluster there can be - the seeds' labels but the largest (a
@@ -1009,19 +1092,26 @@ class MaskRefinerPredictor:
         elif not self.depth_on:
             depth_imgs = None
         n = max(counts + [1])
+        n_rows = n if self.scene is None else self.scene.max_masks       # the mask rows of the pass
+        if props is not None and n + props[0].shape[1] > SCENE_MAX_SLOTS:
+            raise ValueError(f"scene: {n} ground-truth rows and {props[0].shape[1]} proposal rows: more than {SCENE_MAX_SLOTS} in all")
         mk = np.zeros((B, n, H, W) if cluster_in is None else (0,), np.uint8)
         for b, m in enumerate(masks_list if cluster_in is None else ()):
             if len(m):
                 mk[b, :len(m)] = mask_bytes(m, self.perturb is not None or self.nms is not None, binarise=True)
         model = self.model
         gt = model.upload_gt(gt_labels, B, H, W)
-        eng = model.engine_for(H, W, 2 * B if self.tta else B, max(n, gt[2]) if gt is not None else n)
+        eng = model.engine_for(H, W, 2 * B if self.tta else B, max(n, n_rows, gt[2]) if gt is not None else max(n, n_rows))
         # uploaded straight into B-frame tensors (tta: the first halves of the 2B-frame buffers)
-        bgr, depth, d_masks = model.batch_buffers(B, H, W, n, depth_imgs is not None)
+        bgr, depth, d_masks = model.batch_buffers(B, H, W, n_rows, depth_imgs is not None)
         bgr[:B].copy_(torch.from_numpy(np.ascontiguousarray(rgb_imgs, dtype=np.uint8)))
         if depth is not None:
             depth[:B].copy_(torch.from_numpy(np.ascontiguousarray(depth_imgs, dtype=np.uint8)))
-        if cluster_in is None:
+        scene_in = None
+        if self.scene is not None:                        # the uploaded masks are the scene's ground truth, in a tensor of their own
+            i32 = lambda v: torch.from_numpy(np.asarray(v, np.int32)).to(self.device)
+            scene_in = (torch.from_numpy(mk).to(self.device), i32(counts), torch.from_numpy(props[0]).to(self.device), i32(props[1]))
+        elif cluster_in is None:
             d_masks[:B].copy_(torch.from_numpy(mk))
         else:                                             # the first seeds: drawn last, so that a call that raised above has drawn nothing
             if gms:
@@ -1031,5 +1121,5 @@ class MaskRefinerPredictor:
                 cluster_in = (cluster_in[0], self.cluster.first_seeds(B, H * W), cluster_in[1])
             cluster_in = tuple(None if a is None else torch.from_numpy(a).to(self.device) for a in cluster_in)
         rec = model.device_pass(eng, bgr, depth, d_masks, None if sc is None else torch.from_numpy(sc).to(self.device), B, may_stop=True,
-                                own=counts, gt=gt, cluster_in=cluster_in)
+                                own=counts, gt=gt, cluster_in=cluster_in, scene_in=scene_in)
         return model.results(rec, (bgr, depth))
