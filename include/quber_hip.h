@@ -39,7 +39,10 @@ typedef struct quber_config {
     int32_t min_instance_area;       /* post_processing.py:145 (512) */
     int32_t label_divisor;           /* register_uoais_sim_panoptic.py:177-186 (1000) */
     int32_t with_network;            /* 0: only the encode / error-map / post-processing kernels are usable;
-                                        1: the refiner network; 2: the LMFFNet foreground network of the post-filter
+                                        1: the refiner network; 3: the CGNet foreground network of the UOAIS base model
+                                           (foreground_segmentation/cgnet.py, classes = 2, in_channel = 4; quber_forward then maps
+                                           (bgr, depth) to [B][2][H][W] logits, H and W multiples of 8; csrc/plan_cgnet.hip, option key 52);
+                                           2: the LMFFNet foreground network of the post-filter
                                            (foreground_segmentation/lmffnet.py; quber_forward then maps (bgr, depth) to
                                            3 class planes [B][3][H][W], dev_offsets is ignored) */
     float center_threshold;          /* PANOPTIC_DEEPLAB.CENTER_THRESHOLD (0.3) */
@@ -679,6 +682,16 @@ int quber_foreground_filter(const float* dev_fg_logits, int32_t n_classes, int32
                             int32_t batch, int32_t n_masks, int64_t hw, uint8_t* dev_fg_mask, uint64_t* dev_counts,
                             void* stream);
 
+/* the foreground filter of the UOAIS base model (eval/base_model.py:210-216) on a CGNet foreground map (quber_foreground_filter with
+ * n_classes = 2, fg_class = 1 on the logits of a with_network = 3 context):
+ *   dev_fg u8 [B][fg_h][fg_w], dev_masks u8 [B][n_masks][h][w] at any size (may be NULL with n_masks = 0)
+ *   -> dev_counts u64 [B][n_masks][2] = (|mask & fg'|, |mask|), fg'(y, x) = fg(floor(y fg_h / h), floor(x fg_w / w)) (OpenCV's float64
+ *      factors 1 / (h / fg_h), 1 / (w / fg_w)): the
+ *      cv2.resize(fg, (w, h), INTER_NEAREST) of foreground_segmentation/predictor.py:50 folded into the read.  The caller skips empty
+ *      masks and keeps those with inter / area > 0.5.  Integer sums: exact.  Nothing is written for n_masks = 0. */
+int quber_foreground_overlap(const uint8_t* dev_fg, int32_t fg_h, int32_t fg_w, const uint8_t* dev_masks, int32_t batch, int32_t n_masks,
+                             int32_t h, int32_t w, uint64_t* dev_counts, void* stream);
+
 /* adapter pre-processing - depth normalisation.  Replaces normalize_depth (eval/preprocess_utils.py:12-28) and the
  * zero-depth bookkeeping of eval/refiner_model.py:250.
  *   dev_depth: uint16 [n] (is_float32 = 0, e.g. PNG millimetres, evaluated in float64 like numpy) or f32 [n]
@@ -815,6 +828,10 @@ double quber_forward_flops_padding(quber_ctx* ctx);
  *         phase on its own (rows and columns decide independently; 640x480: res5.1/.2 conv2 and ASPP d = 6 / 12 run 88 / 96 / 108 / 132 tiles per
  *         image instead of 96 / 128 / 144 / 144).  Which layers take Winograd, and with which tile, is not affected.  The same arithmetic per
  *         tile; a pixel falls into another tile, so the last bits move as on a ragged frame; 0 = per phase everywhere, the bits before the key.
+ * key 52 (1; plan) CGNet contexts (with_network = 3): a context-guided block (foreground_segmentation/cgnet.py:231-261) as two kernels -
+ *         cg_joint (1x1 + BN + PReLU into LDS with a halo, both depthwise 3x3, BN + PReLU of the concatenation, per-tile channel sums) and
+ *         cg_apply (global mean, the two fully connected layers, channel scale, residual), csrc/cgnet.hip; 0 = 1x1 convolution, two depthwise
+ *         launches, cg_sums and cg_apply: five launches per block, the same arithmetic but for the K order of the 1x1.
  * Process-only keys (quber_set_tuning): key 2 = give the stand-alone conv ops a split-K workspace (value != 0) or drop it (0);
  * key 11 = stand-alone conv op: dilated 3x3 layers in tap-major K order with the zero-padding filter rows skipped;
  * key 12 = stand-alone conv ops: quber_config.compute_dtype of the launch (1 = bf16 / 2 = fp16 operands, 3 = bf16x3);
@@ -962,6 +979,29 @@ int quber_op_upsample_logits(const float* dev_q, float* dev_out, int32_t batch, 
 int quber_op_preprocess(const uint8_t* dev_bgr, const uint8_t* dev_depth, const float* dev_offsets, void* dev_x, int32_t x_c, int32_t es,
                         int32_t batch, int32_t batch_cap, int32_t h, int32_t w, const float* mean6, const float* std6, int32_t streams,
                         void* stream);
+/* The kernels of the CGNet foreground network (csrc/cgnet.hip), each on explicit fp32 NHWC views - test hooks: the network reaches them only
+ * through quber_forward of a with_network = 3 context.  A view is (pointer to its first channel, cs = elements between two pixels); c = 64
+ * or 128.  A refused view returns an error and launches nothing; no op allocates or synchronises.
+ *   quber_op_cgnet_tiles   tiles per frame of the partials buffer f64 [batch][tiles][c]: joint != 0: the 8 x 8 tiles quber_op_cgnet_joint writes,
+ *                          0: the 64-pixel runs quber_op_cgnet_sums writes
+ *   quber_op_cgnet_joint   joi = prelu(bn2([dw3x3(t) | dw3x3 dilated by dil (t)])), t = prelu(bn1(W1 x)) with zero padding OF t; dil 1..4;
+ *                          dev_w1 [c/2][c], scale1 / shift1 / slope1 [c/2], dev_wloc / dev_wsur [c/2][3][3], scale2 / shift2 / slope2 [c];
+ *                          x in aligned groups of 4 channels; also writes this launch's partials
+ *   quber_op_cgnet_sums    the partials of a tensor
+ *   quber_op_cgnet_apply   y = sigmoid(fc2 relu(fc0 mean + b0) + b2) with mean = (partials added in tile order) / (h w), hidden = c / r <= 8 units;
+ *                          out = [x +] joi * y (dev_x may be NULL); dev_mean / dev_y f32 [batch][c] receive the mean and y (may be NULL);
+ *                          views in aligned groups of 4 channels */
+int32_t quber_op_cgnet_tiles(int32_t h, int32_t w, int32_t joint);
+int quber_op_cgnet_joint(const float* dev_x, int32_t x_cs, float* dev_joi, int32_t joi_cs, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t dil,
+                         const float* dev_w1, const float* dev_scale1, const float* dev_shift1, const float* dev_slope1, const float* dev_wloc,
+                         const float* dev_wsur, const float* dev_scale2, const float* dev_shift2, const float* dev_slope2, double* dev_partials,
+                         int32_t tiles, void* stream);
+int quber_op_cgnet_sums(const float* dev_x, int32_t x_cs, int32_t batch, int32_t h, int32_t w, int32_t c, double* dev_partials, int32_t tiles,
+                        void* stream);
+int quber_op_cgnet_apply(const float* dev_joi, int32_t joi_cs, const float* dev_x, int32_t x_cs, float* dev_out, int32_t out_cs, int32_t batch,
+                         int32_t h, int32_t w, int32_t c, int32_t hidden, const double* dev_partials, int32_t tiles, const float* dev_fc0,
+                         const float* dev_b0, const float* dev_fc2, const float* dev_b2, float* dev_mean, float* dev_y, void* stream);
+
 /* The kernels of the LMFFNet foreground network (csrc/lmff.hip), each on explicit fp32 NHWC views - test hooks: the network reaches them
  * only through quber_forward of a with_network = 2 context.  A view is (pointer to its first channel, cs = elements between two pixels)
  * over batch x h x w x c; scale / shift / slope are per-channel device arrays of c floats.  A view the launcher refuses returns the

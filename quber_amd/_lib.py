@@ -142,6 +142,12 @@ SIGNATURES = {
     "quber_op_upsample_logits": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_uint32, _P]),
     "quber_op_preprocess": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "quber_op_group_pixels": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "quber_foreground_overlap": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
+    # the CGNet kernels on explicit fp32 views (tests/test_gpu_cgnet.py): pointer, cs per view
+    "quber_op_cgnet_tiles": (C.c_int32, [_I, _I, _I]),
+    "quber_op_cgnet_joint": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I] + [_P] * 10 + [_I, _P]),
+    "quber_op_cgnet_sums": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "quber_op_cgnet_apply": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     # the LMFFNet kernels on explicit fp32 views (tests/test_gpu_lmff_kernels.py): pointer, cs per view
     "quber_op_lmff_preprocess": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "quber_op_lmff_dwconv": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

@@ -16,6 +16,10 @@ int quber::check_cfg(const quber_config& c) {
         if (c.height % 8 || c.width % 8) return fail("LMFFNet needs height and width to be multiples of 8");
         return c.max_batch >= 1 ? 0 : fail("max_batch must be >= 1");
     }
+    if (c.with_network == 3) {
+        if (c.height % 8 || c.width % 8) return fail("CGNet needs height and width to be multiples of 8");
+        return c.max_batch >= 1 ? 0 : fail("max_batch must be >= 1");
+    }
     if (c.max_batch < 1) return fail("max_batch must be >= 1");
     if (c.max_instances < 1) return fail("max_instances must be >= 1");
     if (c.resnet_depth != 50 && c.resnet_depth != 101 && c.resnet_depth != 152) return fail("resnet_depth must be 50, 101 or 152");
@@ -103,7 +107,9 @@ int quber_create(const quber_config* cfg, quber_ctx** out) {
     }
     if (cfg->with_network) {      // the weights the plan will ask for
         Builder dry(c, true);
-        if (cfg->with_network == 2) build_lmff(dry); else dry.build();
+        if (cfg->with_network == 2) build_lmff(dry);
+        else if (cfg->with_network == 3) build_cgnet(dry);
+        else dry.build();
     }
     *out = c;
     return 0;
@@ -152,10 +158,10 @@ int quber_finalize_weights(quber_ctx* c) {
     quber::TuneScope tscope(&c->tune);          // the plan is shaped by THIS context's options
     Builder b(c, false);
     c->flops = c->wino_flops = c->wino_saved = c->wino_pad = 0.0;
-    if (c->cfg.with_network == 2) {
+    if (c->cfg.with_network == 2 || c->cfg.with_network == 3) {
         c->splitk_floats = (size_t)4 << 20;
         c->splitk_ws = (float*)b.dalloc_bytes(sizeof(float) * c->splitk_floats);
-        build_lmff(b);
+        if (c->cfg.with_network == 2) build_lmff(b); else build_cgnet(b);
     } else {
         b.build();
     }
@@ -296,13 +302,13 @@ int quber_explicit_error_maps(quber_ctx* c, const uint8_t* init, int32_t n_init,
 }
 
 // The shared preamble of quber_forward / quber_forward_profiled: checks, this context's options for every launcher (`scope`, until the caller returns), the pointers
-// the plan's ops read, the preprocess kernel.  0 = go on, < 0 = error, 1 = an LMFFNet context that the caller runs itself (lmff_own; nothing stored or launched).
+// the plan's ops read, the preprocess kernel.  0 = go on, < 0 = error, 1 = an LMFFNet / CGNet context that the caller runs itself (lmff_own; nothing stored or launched).
 static int forward_begin(quber_ctx* c, const char* who, std::optional<quber::TuneScope>& scope, const uint8_t* bgr, const uint8_t* depth,
                          const float* offs, int batch, float* logits, bool lmff_own, bool rest_ok, const char* null_msg, hipStream_t st) {
     if (check_batch(c, batch)) return -1;
     if (!c->finalized) return fail(std::string(who) + " before quber_finalize_weights");
     scope.emplace(&c->tune);
-    if (lmff_own && c->cfg.with_network == 2) return 1;
+    if (lmff_own && c->cfg.with_network >= 2) return 1;
     if (!bgr || (!depth && c->cfg.streams == 2) || !offs || !logits || !rest_ok) return fail(null_msg);
     c->cur_out = logits;
     c->cur_bgr = bgr; c->cur_depth = depth; c->cur_off = offs;
@@ -314,10 +320,11 @@ int quber_forward(quber_ctx* c, const uint8_t* bgr, const uint8_t* depth, const 
     hipStream_t st = (hipStream_t)stream;
     std::optional<quber::TuneScope> tscope;
     int rc = forward_begin(c, "quber_forward", tscope, bgr, depth, offs, batch, logits, true, true, "null tensor", st);
-    if (rc == 1) {   // LMFFNet: (bgr, depth) -> 3 class planes; `offs` is unused
+    if (rc == 1) {   // LMFFNet / CGNet: (bgr, depth) -> 3 / 2 class planes; `offs` is unused
         if (!bgr || !depth || !logits) return fail("null tensor");
         c->cur_out = logits;
-        int r2 = launch_lmff_preprocess(bgr, depth, (long)batch * c->cfg.height * c->cfg.width, c->X.p, st);
+        const long pixels = (long)batch * c->cfg.height * c->cfg.width;
+        int r2 = c->cfg.with_network == 3 ? launch_cg_preprocess(bgr, depth, pixels, c->X.p, st) : launch_lmff_preprocess(bgr, depth, pixels, c->X.p, st);
         for (size_t i = 0; !r2 && i < c->ops.size(); ++i)
             if (!c->ops[i].ctl) r2 = c->ops[i].run(batch, st);
         return r2;
@@ -941,6 +948,11 @@ int quber_foreground_filter(const float* fg_logits, int32_t n_classes, int32_t f
     if (rc || n_masks == 0) return rc;
     if (!masks || !counts) return fail("null masks / counts");
     return launch_mask_overlap(masks, fg_mask, batch, n_masks, hw, (unsigned long long*)counts, st);
+}
+
+int quber_foreground_overlap(const uint8_t* fg, int32_t fg_h, int32_t fg_w, const uint8_t* masks, int32_t batch, int32_t n_masks, int32_t h, int32_t w,
+                             uint64_t* counts, void* stream) {
+    return launch_fg_overlap(fg, fg_h, fg_w, masks, batch, n_masks, h, w, (unsigned long long*)counts, (hipStream_t)stream);
 }
 
 int quber_normalize_depth(const void* depth, int32_t is_float32, int64_t n_pixels, double min_val, double max_val,

@@ -496,6 +496,31 @@ int quber_op_lmff_gate(const float* o, int32_t o_cs, const float* att, int32_t a
     return launch_mad_gate(lview(o, B, h, w, c, o_cs), lview(att, B, h, w, c, att_cs), q, B, c, (hipStream_t)stream);
 }
 
+// ---- the CGNet kernels of cgnet.hip on explicit fp32 views (tests): arguments -> View -> launcher, nothing else ----
+int32_t quber_op_cgnet_tiles(int32_t h, int32_t w, int32_t joint) {
+    if (h < 1 || w < 1) return 0;
+    return joint ? cg_joint_tiles(h, w) : cg_sums_tiles(h, w);
+}
+
+int quber_op_cgnet_joint(const float* x, int32_t x_cs, float* joi, int32_t joi_cs, int32_t B, int32_t h, int32_t w, int32_t c, int32_t dil, const float* w1,
+                         const float* scale1, const float* shift1, const float* slope1, const float* wloc, const float* wsur, const float* scale2,
+                         const float* shift2, const float* slope2, double* partials, int32_t tiles, void* stream) {
+    return launch_cg_joint(lview(x, B, h, w, c, x_cs), lview(joi, B, h, w, c, joi_cs), B, dil, w1, scale1, shift1, slope1, wloc, wsur, scale2, shift2, slope2, partials,
+                           tiles, (hipStream_t)stream);
+}
+
+int quber_op_cgnet_sums(const float* x, int32_t x_cs, int32_t B, int32_t h, int32_t w, int32_t c, double* partials, int32_t tiles, void* stream) {
+    return launch_cg_sums(lview(x, B, h, w, c, x_cs), B, partials, tiles, (hipStream_t)stream);
+}
+
+int quber_op_cgnet_apply(const float* joi, int32_t joi_cs, const float* x, int32_t x_cs, float* out, int32_t out_cs, int32_t B, int32_t h, int32_t w, int32_t c,
+                         int32_t hidden, const double* partials, int32_t tiles, const float* fc0, const float* b0, const float* fc2, const float* b2, float* mean,
+                         float* y, void* stream) {
+    const View xv = lview(x, B, h, w, c, x_cs);
+    return launch_cg_apply(lview(joi, B, h, w, c, joi_cs), x ? &xv : nullptr, lview(out, B, h, w, c, out_cs), B, hidden, partials, tiles, fc0, b0, fc2, b2, mean, y,
+                           (hipStream_t)stream);
+}
+
 int quber_op_maxpool3x3s2(const float* x, int32_t B, int32_t h, int32_t w, int32_t c, float* y, void* stream) {
     if (c % 4) return fail("maxpool: channels must be a multiple of 4");
     return launch_maxpool3x3s2(mkview(x, B, h, w, c), mkview(y, B, (h + 1) / 2, (w + 1) / 2, c), B, 1, (hipStream_t)stream);

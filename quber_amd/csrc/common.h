@@ -215,6 +215,7 @@ struct Tuning {
                                  //   conv_igemm.hip there, 2 = only the layers of up to 128 output channels
     int h8_norm = 1;             // key 39 (plan): fp16 data path: a patch-kernel layer applies the GroupNorm + ReLU in front of it to its LDS patches (same arithmetic as the norm pass, no pass over
                                  //   the tensor in HBM); 0 = every norm is a pass of its own
+    int cgnet_fused = 1;         // key 52 (plan): CGNet (plan_cgnet.hip): a context-guided block as cg_joint + cg_apply (cgnet.hip); 0 = 1x1 convolution, two depthwise launches, cg_sums, cg_apply
     int h8_min_tiles = 224;      // key 32 (launch): fewest tiles (all groups) of a launch that takes it (one block per CU: a launch of fewer tiles leaves CUs idle)
 };
 extern Tuning g_tune;
@@ -293,6 +294,19 @@ int launch_mad_gate(const View& o, const View& att, float* q, int B, int C, hipS
 int launch_argmax_fg(const float* logits, int B, long HW, int nc, int cls, uint8_t* fg, hipStream_t st);
 int launch_mask_overlap(const uint8_t* masks, const uint8_t* fg, int B, int K, long HW, unsigned long long* counts,
                         hipStream_t st);
+
+// CGNet foreground network of the UOAIS base model + its overlap filter (cgnet.hip).  partials: f64 [B][tiles][C] per-channel tile sums,
+// tiles = cg_joint_tiles (8 x 8 tiles, written by launch_cg_joint) or cg_sums_tiles (64-pixel runs, launch_cg_sums); launch_cg_apply adds them in tile order
+int cg_joint_tiles(int H, int W);
+int cg_sums_tiles(int H, int W);
+int launch_cg_preprocess(const uint8_t* bgr, const uint8_t* depth, long pixels, float* x, hipStream_t st);
+int launch_cg_joint(const View& x, const View& joi, int B, int dil, const float* w1, const float* s1, const float* h1, const float* a1, const float* wloc,
+                    const float* wsur, const float* s2, const float* h2, const float* a2, double* partials, int tiles, hipStream_t st);
+int launch_cg_sums(const View& in, int B, double* partials, int tiles, hipStream_t st);
+int launch_cg_apply(const View& joi, const View* x, const View& out, int B, int hidden, const double* partials, int tiles, const float* fc0, const float* b0,
+                    const float* fc2, const float* b2, float* mean, float* y, hipStream_t st);
+int launch_cg_planes(const View& in, int nc, int B, float* q, hipStream_t st);
+int launch_fg_overlap(const uint8_t* fg, int fh, int fw, const uint8_t* masks, int B, int K, int H, int W, unsigned long long* counts, hipStream_t st);
 
 int launch_boundary_overlap(const int* pred, const int* gt, int H, int W, const int* labels, int n_pred, int n_gt, int radius,
                             void* ws, unsigned* out, hipStream_t st);

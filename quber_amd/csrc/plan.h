@@ -177,6 +177,7 @@ struct Builder {
     void build();       // the refiner network
 };
 void build_lmff(Builder& b);     // LMFFNet (plan_lmff.hip)
+void build_cgnet(Builder& b);    // CGNet (plan_cgnet.hip)
 
 int check_cfg(const quber_config& c);
 bool op_set_tuning(int key, int value);      // api_ops.hip: the process-only keys 2, 11, 12, 26 of quber_set_tuning; false: not one of them

@@ -29,7 +29,7 @@ constexpr TuneKey TUNE_KEYS[] = {
     {37, &Tuning::x8_min_nk, false},            {38, &Tuning::h8_narrow, false},
     {39, &Tuning::h8_norm, true},               {41, &Tuning::aspp_lanes, true},
     {42, &Tuning::small_n_64, false},           {43, &Tuning::zone_cols, false},
-    {51, &Tuning::wino_pack, true},
+    {51, &Tuning::wino_pack, true},              {52, &Tuning::cgnet_fused, true},
 };
 int* tuning_field(Tuning& t, int key) {
     for (const TuneKey& k : TUNE_KEYS)

@@ -132,7 +132,10 @@ class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
                  lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
                  decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
-                 nms=None, zoom=None, losses=None, scene=None):
+                 nms=None, zoom=None, losses=None, scene=None, initial_filter=None):
+        # initial_filter: None | "cgnet" | a quber_amd.foreground.predictor.CGNet - the UOAIS base model's foreground filter
+        # (eval/base_model.py:209-216) applied to initial_masks (and mask_scores) in _load, before anything else reads them:
+        # predict() and predict_stream() alike; the foreground map and the kept indices come back as output["initial_fg"] / ["initial_keep"]
         # tta ... scene: the predictor's options (maskrefiner/predictor.py: module docstring, RefineOptions), for predict()
         # and predict_stream(batch=k) alike, except: until_converged stops early in predict() only (the stream always runs the fixed
         # count); cleanup "largest" is the UOIS path's largest_connected_component (4-connected), "holes" the SAM refiner's
@@ -154,6 +157,14 @@ class MaskRefiner:
         if foreground_filter:
             from ..foreground.predictor import lmffNet
             self.lmffnet = lmffNet(lmffnet_weights, device=device)
+        self.initial_filter = None
+        if initial_filter is not None:
+            from ..foreground.predictor import CGNet
+            if dataset == "armbench":
+                raise ValueError("initial_filter: CGNet reads a depth image; the armbench path has none")
+            if isinstance(initial_filter, str) and initial_filter != "cgnet":
+                raise ValueError(f"initial_filter: unknown filter '{initial_filter}' (None, 'cgnet' or a CGNet instance)")
+            self.initial_filter = CGNet(device=device) if isinstance(initial_filter, str) else initial_filter
 
     def _dev(self, a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(self.refiner_predictor.device)
@@ -197,8 +208,19 @@ class MaskRefiner:
             d_dev = None
         else:
             depth = d_dev.cpu().numpy()
-        return {"rgb": np.ascontiguousarray(rgb), "depth": depth, "masks": initial_masks, "zero_depth": zero_depth, "depth_dev": d_dev,
-                "scores": scores}
+        fr = {"rgb": np.ascontiguousarray(rgb), "depth": depth, "masks": initial_masks, "zero_depth": zero_depth, "depth_dev": d_dev,
+              "scores": scores}
+        if self.initial_filter is not None:
+            # eval/base_model.py:209-216 on the frame as the refiner will see it; the masks keep their own size (the count kernel reads the
+            # 240 x 320 foreground map at the nearest-neighbour position)
+            from ..foreground.predictor import filter_masks_uoais
+            fg, counts = self.initial_filter.filter_counts(fr["rgb"], depth, initial_masks)
+            kept, keep = filter_masks_uoais(initial_masks, counts)
+            fr["masks"] = np.asarray(kept, dtype=initial_masks.dtype).reshape((len(keep),) + tuple(initial_masks.shape[1:]))
+            if scores is not None:
+                fr["scores"] = scores[keep]
+            fr["initial_fg"], fr["initial_keep"] = fg, keep
+        return fr
 
     def _refine(self, fr, gt_labels=None, proposals=None):
         """The reference's timed region and what follows it (eval/refiner_model.py:265-297) on a loaded frame."""
@@ -217,6 +239,8 @@ class MaskRefiner:
         if self.dataset == "armbench":
             return refined, output, time.time() - start, None
         rgb, depth, zero_depth = fr["rgb"], fr["depth"], fr["zero_depth"]
+        if "initial_keep" in fr:
+            output["initial_fg"], output["initial_keep"] = fr["initial_fg"], fr["initial_keep"]
         fg, filt = None, refined
         if self.lmffnet is not None:
             from ..foreground.predictor import filter_masks
