@@ -39,7 +39,10 @@ typedef struct quber_config {
     int32_t min_instance_area;       /* post_processing.py:145 (512) */
     int32_t label_divisor;           /* register_uoais_sim_panoptic.py:177-186 (1000) */
     int32_t with_network;            /* 0: only the encode / error-map / post-processing kernels are usable;
-                                        1: the refiner network; 3: the CGNet foreground network of the UOAIS base model
+                                        1: the refiner network; 4: the Depth Seeding Network of UOIS-Net-3D (uois/src/networks.py
+                                           UNetESP_Encoder / UNetESP_Decoder, uois/src/segmentation.py:72-127; feature_dim is read off the first
+                                           convolution's weight; H and W multiples of 16; runs through quber_dsn_forward, not quber_forward;
+                                           csrc/plan_dsn.hip, option key 53); 3: the CGNet foreground network of the UOAIS base model
                                            (foreground_segmentation/cgnet.py, classes = 2, in_channel = 4; quber_forward then maps
                                            (bgr, depth) to [B][2][H][W] logits, H and W multiples of 8; csrc/plan_cgnet.hip, option key 52);
                                            2: the LMFFNet foreground network of the post-filter
@@ -832,6 +835,10 @@ double quber_forward_flops_padding(quber_ctx* ctx);
  *         cg_joint (1x1 + BN + PReLU into LDS with a halo, both depthwise 3x3, BN + PReLU of the concatenation, per-tile channel sums) and
  *         cg_apply (global mean, the two fully connected layers, channel scale, residual), csrc/cgnet.hip; 0 = 1x1 convolution, two depthwise
  *         launches, cg_sums and cg_apply: five launches per block, the same arithmetic but for the K order of the 1x1.
+ * key 53 (0; plan) Depth Seeding Network contexts (with_network = 4): the second half of an ESP module (uois/src/networks.py:108-125) as one kernel,
+ *         esp_branches (csrc/dsn.hip): the five dilated 3x3 convolutions of t on v_mfma_f32_16x16x4_f32, the running sums d2, d2 + d4, ... kept in the
+ *         accumulators, the residual, the store and per-tile GroupNorm sums; 0 = five convolution launches into temporaries + esp_merge.  The same
+ *         convolutions; a running sum is continued in the accumulator instead of rounded and added (profiles/dsn_ab.md decides the default).
  * Process-only keys (quber_set_tuning): key 2 = give the stand-alone conv ops a split-K workspace (value != 0) or drop it (0);
  * key 11 = stand-alone conv op: dilated 3x3 layers in tap-major K order with the zero-padding filter rows skipped;
  * key 12 = stand-alone conv ops: quber_config.compute_dtype of the launch (1 = bf16 / 2 = fp16 operands, 3 = bf16x3);
@@ -979,6 +986,53 @@ int quber_op_upsample_logits(const float* dev_q, float* dev_out, int32_t batch, 
 int quber_op_preprocess(const uint8_t* dev_bgr, const uint8_t* dev_depth, const float* dev_offsets, void* dev_x, int32_t x_c, int32_t es,
                         int32_t batch, int32_t batch_cap, int32_t h, int32_t w, const float* mean6, const float* std6, int32_t streams,
                         void* stream);
+/* Depth Seeding Network of UOIS-Net-3D on a with_network = 4 context: xyz -> foreground logits, centre offsets, centre votes, classes.
+ *   dev_xyz f32 [B][3][H][W] planar (x, y, z in metres, as compute_xyz delivers them; NaN allowed).  The network's input is xyz with NaN -> 0
+ *   and, when bit 0 of flags is set, y negated (eval/base_model.py:496-498); no other flag bit is defined.
+ *   -> dev_fg_logits f32 [B][3][H][W] (fg_module, classes background / table / objects), dev_offsets f32 [B][3][H][W] (cd_module),
+ *      dev_votes f32 [B][3][H][W] = cleaned xyz + offsets (one float32 add: DSNWrapper.cluster's predicted centres),
+ *      dev_fg_classes u8 [B][H][W] = the FIRST maximal logit (the reference takes argmax(softmax(logits)): where float32 softmax rounds two distinct
+ *      logits to one probability it returns the lower index instead), dev_fg u8 [B][H][W] = (class == 2).
+ *   Any output pointer may be NULL.  dev_votes / dev_fg are the layouts quber_gms_cluster reads.  Everything runs on `stream`; no host copy, no
+ *   memset node, no allocation: the call can be captured into a graph. */
+int quber_dsn_forward(quber_ctx* ctx, const float* dev_xyz, int32_t batch, int32_t flags, float* dev_fg_logits, float* dev_offsets, float* dev_votes,
+                      uint8_t* dev_fg_classes, uint8_t* dev_fg, void* stream);
+/* the same forward with a HIP-event pair around every op of the plan (benchmark use; tools/dsn_ab.py): synchronises `stream`, then writes the milliseconds
+ * of op i (quber_op_info) to op_ms[i], quber_num_ops doubles on the host */
+int quber_dsn_forward_profiled(quber_ctx* ctx, const float* dev_xyz, int32_t batch, int32_t flags, float* dev_fg_logits, float* dev_offsets,
+                               float* dev_votes, uint8_t* dev_fg_classes, uint8_t* dev_fg, void* stream, double* op_ms);
+
+/* The kernels of the Depth Seeding Network (csrc/dsn.hip), each on explicit fp32 views - test hooks: the network reaches them only through
+ * quber_dsn_forward.  An NHWC view is (pointer to its first channel, cs = elements between two pixels).  An ESP module of c channels splits them as
+ * n = c / 5 (integer), n1 = c - 4 n.  A refused view returns an error and launches nothing; no op allocates or synchronises.
+ *   quber_op_dsn_pack      planar xyz f32 [batch][3][h][w] -> dev_x8 NHWC with 8 channels (x, y, z, five zeros) and dev_clean planar; NaN -> 0, then
+ *                          y negated when bit 0 of flags is set; either destination may be NULL
+ *   quber_op_esp_tiles     tiles (runs of 64 pixels) per frame of the partials buffer f64 [batch][tiles][groups][2] = (sum, sum of squares)
+ *   quber_op_esp_packed_floats / quber_op_esp_pack   the five OIHW filters (dilated1 [n1][n][3][3], the others [n][n][3][3]) -> the operand order
+ *                          of quber_op_esp_branches, a buffer of quber_op_esp_packed_floats(n1) floats
+ *   quber_op_esp_branches  out = [x +] [d1 | d2 | d2 + d4 | (d2 + d4) + d8 | ((d2 + d4) + d8) + d16], dK = 3x3 of t with dilation = padding = K, zero
+ *                          padding of t; t: n channels on a channel stride of at least 16 ceil(n1 / 16) in aligned groups of 4 - the channels
+ *                          n .. 16 ceil(n1 / 16) are read and multiplied by zero: they must be finite; n1 in 1..32, 49..64, 97..112 or 193..208;
+ *                          dev_x may be NULL; also writes the partials of out for `groups` norm groups (1..64, dividing c)
+ *   quber_op_esp_merge     the same out and partials from the five convolutions as tensors (d1: n1 channels on d1_cs; the others n channels on d_cs),
+ *                          added in the reference's order
+ *   quber_op_esp_stats     partials added in tile order -> dev_stats f64 [batch][groups][2], the layout quber_op_gn_apply reads
+ *   quber_op_dsn_head      features NHWC (c a multiple of 4) -> logits = wfg [3][c] f, offsets = wcd [3][c] f, votes = dev_clean + offsets, classes =
+ *                          the first maximal logit, fg = (class == 2); planar outputs as in quber_dsn_forward, any may be NULL */
+int32_t quber_op_esp_tiles(int32_t h, int32_t w);
+int64_t quber_op_esp_packed_floats(int32_t n1);
+int quber_op_dsn_pack(const float* dev_xyz, int32_t batch, int32_t h, int32_t w, int32_t flags, float* dev_x8, float* dev_clean, void* stream);
+int quber_op_esp_pack(const float* dev_w1, const float* dev_w2, const float* dev_w4, const float* dev_w8, const float* dev_w16, int32_t n, int32_t n1,
+                      float* dev_packed, void* stream);
+int quber_op_esp_branches(const float* dev_t, int32_t t_cs, const float* dev_x, int32_t x_cs, float* dev_out, int32_t out_cs, int32_t batch, int32_t h,
+                          int32_t w, int32_t c, int32_t groups, const float* dev_packed, double* dev_partials, int32_t tiles, void* stream);
+int quber_op_esp_merge(const float* dev_d1, int32_t d1_cs, const float* dev_d2, const float* dev_d4, const float* dev_d8, const float* dev_d16,
+                       int32_t d_cs, const float* dev_x, int32_t x_cs, float* dev_out, int32_t out_cs, int32_t batch, int32_t h, int32_t w, int32_t c,
+                       int32_t groups, double* dev_partials, int32_t tiles, void* stream);
+int quber_op_esp_stats(const double* dev_partials, int32_t batch, int32_t tiles, int32_t groups, double* dev_stats, void* stream);
+int quber_op_dsn_head(const float* dev_f, int32_t f_cs, int32_t batch, int32_t h, int32_t w, int32_t c, const float* dev_clean, const float* dev_wfg,
+                      const float* dev_wcd, float* dev_logits, float* dev_offsets, float* dev_votes, uint8_t* dev_classes, uint8_t* dev_fg, void* stream);
+
 /* The kernels of the CGNet foreground network (csrc/cgnet.hip), each on explicit fp32 NHWC views - test hooks: the network reaches them only
  * through quber_forward of a with_network = 3 context.  A view is (pointer to its first channel, cs = elements between two pixels); c = 64
  * or 128.  A refused view returns an error and launches nothing; no op allocates or synchronises.

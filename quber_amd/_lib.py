@@ -143,6 +143,17 @@ SIGNATURES = {
     "quber_op_preprocess": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "quber_op_group_pixels": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "quber_foreground_overlap": (C.c_int, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
+    # the Depth Seeding Network (csrc/dsn.hip, csrc/plan_dsn.hip) and its kernels on explicit fp32 views (tests/test_gpu_dsn.py)
+    "quber_dsn_forward": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "quber_dsn_forward_profiled": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "quber_op_esp_tiles": (C.c_int32, [_I, _I]),
+    "quber_op_esp_packed_floats": (C.c_int64, [_I]),
+    "quber_op_dsn_pack": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "quber_op_esp_pack": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "quber_op_esp_branches": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "quber_op_esp_merge": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "quber_op_esp_stats": (C.c_int, [_P, _I, _I, _I, _P, _P]),
+    "quber_op_dsn_head": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # the CGNet kernels on explicit fp32 views (tests/test_gpu_cgnet.py): pointer, cs per view
     "quber_op_cgnet_tiles": (C.c_int32, [_I, _I, _I]),
     "quber_op_cgnet_joint": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I] + [_P] * 10 + [_I, _P]),

@@ -20,6 +20,10 @@ int quber::check_cfg(const quber_config& c) {
         if (c.height % 8 || c.width % 8) return fail("CGNet needs height and width to be multiples of 8");
         return c.max_batch >= 1 ? 0 : fail("max_batch must be >= 1");
     }
+    if (c.with_network == 4) {
+        if (c.height < 16 || c.width < 16 || c.height % 16 || c.width % 16) return fail("the Depth Seeding Network needs height and width to be multiples of 16");
+        return c.max_batch >= 1 ? 0 : fail("max_batch must be >= 1");
+    }
     if (c.max_batch < 1) return fail("max_batch must be >= 1");
     if (c.max_instances < 1) return fail("max_instances must be >= 1");
     if (c.resnet_depth != 50 && c.resnet_depth != 101 && c.resnet_depth != 152) return fail("resnet_depth must be 50, 101 or 152");
@@ -109,6 +113,7 @@ int quber_create(const quber_config* cfg, quber_ctx** out) {
         Builder dry(c, true);
         if (cfg->with_network == 2) build_lmff(dry);
         else if (cfg->with_network == 3) build_cgnet(dry);
+        else if (cfg->with_network == 4) build_dsn(dry);
         else dry.build();
     }
     *out = c;
@@ -158,10 +163,12 @@ int quber_finalize_weights(quber_ctx* c) {
     quber::TuneScope tscope(&c->tune);          // the plan is shaped by THIS context's options
     Builder b(c, false);
     c->flops = c->wino_flops = c->wino_saved = c->wino_pad = 0.0;
-    if (c->cfg.with_network == 2 || c->cfg.with_network == 3) {
+    if (c->cfg.with_network >= 2 && c->cfg.with_network <= 4) {
         c->splitk_floats = (size_t)4 << 20;
         c->splitk_ws = (float*)b.dalloc_bytes(sizeof(float) * c->splitk_floats);
-        if (c->cfg.with_network == 2) build_lmff(b); else build_cgnet(b);
+        if (c->cfg.with_network == 2) build_lmff(b);
+        else if (c->cfg.with_network == 3) build_cgnet(b);
+        else build_dsn(b);
     } else {
         b.build();
     }
@@ -308,6 +315,7 @@ static int forward_begin(quber_ctx* c, const char* who, std::optional<quber::Tun
     if (check_batch(c, batch)) return -1;
     if (!c->finalized) return fail(std::string(who) + " before quber_finalize_weights");
     scope.emplace(&c->tune);
+    if (c->cfg.with_network == 4) return fail(std::string(who) + ": a Depth Seeding Network context runs through quber_dsn_forward");
     if (lmff_own && c->cfg.with_network >= 2) return 1;
     if (!bgr || (!depth && c->cfg.streams == 2) || !offs || !logits || !rest_ok) return fail(null_msg);
     c->cur_out = logits;
@@ -356,6 +364,53 @@ int quber_forward(quber_ctx* c, const uint8_t* bgr, const uint8_t* depth, const 
     c->lane_now = 0;
     c->lanes_on = false;
     return 0;
+}
+
+// quber_dsn_forward / quber_dsn_forward_profiled: the checks, the pointers the plan's first and last op read, every op in plan order; op_ms (profiled form): an
+// event pair around every op, read after one synchronisation
+static int dsn_run(quber_ctx* c, const char* who, const float* xyz, int batch, int flags, float* fg_logits, float* offsets, float* votes, uint8_t* fg_classes, uint8_t* fg,
+                   hipStream_t st, double* op_ms) {
+    if (check_batch(c, batch)) return -1;
+    if (c->cfg.with_network != 4) return fail(std::string(who) + ": the context was not created with with_network = 4");
+    if (!c->finalized) return fail(std::string(who) + " before quber_finalize_weights");
+    if (!xyz) return fail(std::string(who) + ": null xyz");
+    if (flags & ~1) return fail(std::string(who) + ": unknown flag bits");
+    quber::TuneScope tscope(&c->tune);
+    c->dsn_xyz = xyz; c->dsn_flags = flags;
+    c->dsn_logits = fg_logits; c->dsn_offsets = offsets; c->dsn_votes = votes; c->dsn_classes = fg_classes; c->dsn_fg = fg;
+    const size_t n = c->ops.size();
+    if (op_ms && c->prof_events.size() < 2 * n) {
+        const size_t old = c->prof_events.size();
+        c->prof_events.resize(2 * n);
+        for (size_t i = old; i < 2 * n; ++i) QB_CHECK(hipEventCreate(&c->prof_events[i]));
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (op_ms) QB_CHECK(hipEventRecord(c->prof_events[2 * i], st));
+        if (!c->ops[i].ctl) {
+            const int rc = c->ops[i].run(batch, st);
+            if (rc) return rc;
+        }
+        if (op_ms) QB_CHECK(hipEventRecord(c->prof_events[2 * i + 1], st));
+    }
+    if (!op_ms) return 0;
+    QB_CHECK(hipStreamSynchronize(st));
+    for (size_t i = 0; i < n; ++i) {
+        float ms = 0.f;
+        QB_CHECK(hipEventElapsedTime(&ms, c->prof_events[2 * i], c->prof_events[2 * i + 1]));
+        op_ms[i] = ms;
+    }
+    return 0;
+}
+
+int quber_dsn_forward(quber_ctx* c, const float* xyz, int32_t batch, int32_t flags, float* fg_logits, float* offsets, float* votes, uint8_t* fg_classes, uint8_t* fg,
+                      void* stream) {
+    return dsn_run(c, "quber_dsn_forward", xyz, batch, flags, fg_logits, offsets, votes, fg_classes, fg, (hipStream_t)stream, nullptr);
+}
+
+int quber_dsn_forward_profiled(quber_ctx* c, const float* xyz, int32_t batch, int32_t flags, float* fg_logits, float* offsets, float* votes, uint8_t* fg_classes,
+                               uint8_t* fg, void* stream, double* op_ms) {
+    if (!op_ms) return fail("quber_dsn_forward_profiled: null op_ms");
+    return dsn_run(c, "quber_dsn_forward_profiled", xyz, batch, flags, fg_logits, offsets, votes, fg_classes, fg, (hipStream_t)stream, op_ms);
 }
 
 int quber_forward_profiled(quber_ctx* c, const uint8_t* bgr, const uint8_t* depth, const float* offs, int32_t batch,

@@ -521,6 +521,46 @@ int quber_op_cgnet_apply(const float* joi, int32_t joi_cs, const float* x, int32
                            (hipStream_t)stream);
 }
 
+// ---- the Depth Seeding Network kernels of dsn.hip on explicit fp32 views (tests): arguments -> View -> launcher, nothing else ----
+int32_t quber_op_esp_tiles(int32_t h, int32_t w) { return (h < 1 || w < 1) ? 0 : esp_tiles(h, w); }
+int64_t quber_op_esp_packed_floats(int32_t n1) { return (n1 < 1 || n1 > 208) ? 0 : (int64_t)esp_packed_floats(n1); }
+
+int quber_op_dsn_pack(const float* xyz, int32_t B, int32_t h, int32_t w, int32_t flags, float* x8, float* clean, void* stream) {
+    return launch_dsn_pack(xyz, B, h, w, flags, x8, clean, (hipStream_t)stream);
+}
+
+int quber_op_esp_pack(const float* w1, const float* w2, const float* w4, const float* w8, const float* w16, int32_t n, int32_t n1, float* packed, void* stream) {
+    const float* const w[5] = {w1, w2, w4, w8, w16};
+    return launch_esp_pack(w, n, n1, packed, (hipStream_t)stream);
+}
+
+int quber_op_esp_branches(const float* t, int32_t t_cs, const float* x, int32_t x_cs, float* out, int32_t out_cs, int32_t B, int32_t h, int32_t w, int32_t c,
+                          int32_t groups, const float* packed, double* partials, int32_t tiles, void* stream) {
+    const int n = c / 5, n1 = c - 4 * n;
+    const View xv = lview(x, B, h, w, c, x_cs);
+    return launch_esp_branches(lview(t, B, h, w, n, t_cs), x ? &xv : nullptr, lview(out, B, h, w, c, out_cs), B, n, n1, groups, packed, partials, tiles,
+                               (hipStream_t)stream);
+}
+
+int quber_op_esp_merge(const float* d1, int32_t d1_cs, const float* d2, const float* d4, const float* d8, const float* d16, int32_t d_cs, const float* x,
+                       int32_t x_cs, float* out, int32_t out_cs, int32_t B, int32_t h, int32_t w, int32_t c, int32_t groups, double* partials, int32_t tiles,
+                       void* stream) {
+    const int n = c / 5, n1 = c - 4 * n;
+    const View d[5] = {lview(d1, B, h, w, n1, d1_cs), lview(d2, B, h, w, n, d_cs), lview(d4, B, h, w, n, d_cs), lview(d8, B, h, w, n, d_cs),
+                       lview(d16, B, h, w, n, d_cs)};
+    const View xv = lview(x, B, h, w, c, x_cs);
+    return launch_esp_merge(d, x ? &xv : nullptr, lview(out, B, h, w, c, out_cs), B, n, n1, groups, partials, tiles, (hipStream_t)stream);
+}
+
+int quber_op_esp_stats(const double* partials, int32_t B, int32_t tiles, int32_t groups, double* stats, void* stream) {
+    return launch_esp_stats(partials, B, tiles, groups, stats, (hipStream_t)stream);
+}
+
+int quber_op_dsn_head(const float* f, int32_t f_cs, int32_t B, int32_t h, int32_t w, int32_t c, const float* clean, const float* wfg, const float* wcd,
+                      float* logits, float* offsets, float* votes, uint8_t* classes, uint8_t* fg, void* stream) {
+    return launch_dsn_head(lview(f, B, h, w, c, f_cs), B, clean, wfg, wcd, logits, offsets, votes, classes, fg, (hipStream_t)stream);
+}
+
 int quber_op_maxpool3x3s2(const float* x, int32_t B, int32_t h, int32_t w, int32_t c, float* y, void* stream) {
     if (c % 4) return fail("maxpool: channels must be a multiple of 4");
     return launch_maxpool3x3s2(mkview(x, B, h, w, c), mkview(y, B, (h + 1) / 2, (w + 1) / 2, c), B, 1, (hipStream_t)stream);

@@ -216,6 +216,8 @@ struct Tuning {
     int h8_norm = 1;             // key 39 (plan): fp16 data path: a patch-kernel layer applies the GroupNorm + ReLU in front of it to its LDS patches (same arithmetic as the norm pass, no pass over
                                  //   the tensor in HBM); 0 = every norm is a pass of its own
     int cgnet_fused = 1;         // key 52 (plan): CGNet (plan_cgnet.hip): a context-guided block as cg_joint + cg_apply (cgnet.hip); 0 = 1x1 convolution, two depthwise launches, cg_sums, cg_apply
+    int dsn_fused = 0;           // key 53 (plan): Depth Seeding Network (plan_dsn.hip): the five dilated convolutions of an ESP module, their running sums, the residual and the GroupNorm sums
+                                 //   as one kernel, esp_branches (dsn.hip); 0 = five convolution launches + esp_merge
     int h8_min_tiles = 224;      // key 32 (launch): fewest tiles (all groups) of a launch that takes it (one block per CU: a launch of fewer tiles leaves CUs idle)
 };
 extern Tuning g_tune;
@@ -307,6 +309,19 @@ int launch_cg_apply(const View& joi, const View* x, const View& out, int B, int 
                     const float* fc2, const float* b2, float* mean, float* y, hipStream_t st);
 int launch_cg_planes(const View& in, int nc, int B, float* q, hipStream_t st);
 int launch_fg_overlap(const uint8_t* fg, int fh, int fw, const uint8_t* masks, int B, int K, int H, int W, unsigned long long* counts, hipStream_t st);
+
+// Depth Seeding Network of UOIS-Net-3D (dsn.hip).  partials: f64 [B][esp_tiles][groups][2] (sum, sum of squares) per 64-pixel run, written by launch_esp_branches /
+// launch_esp_merge; launch_esp_stats adds them in tile order into stats f64 [B][groups][2], the layout launch_gn_apply reads.  packed: esp_packed_floats(n1) floats
+int esp_tiles(int H, int W);
+int esp_nt(int n1);
+size_t esp_packed_floats(int n1);
+int launch_dsn_pack(const float* xyz, int B, int H, int W, int flags, float* x8, float* clean, hipStream_t st);
+int launch_esp_pack(const float* const w[5], int n, int n1, float* packed, hipStream_t st);
+int launch_esp_branches(const View& t, const View* x, const View& out, int B, int n, int n1, int groups, const float* packed, double* partials, int tiles, hipStream_t st);
+int launch_esp_merge(const View d[5], const View* x, const View& out, int B, int n, int n1, int groups, double* partials, int tiles, hipStream_t st);
+int launch_esp_stats(const double* partials, int B, int tiles, int groups, double* stats, hipStream_t st);
+int launch_dsn_head(const View& f, int B, const float* clean, const float* wfg, const float* wcd, float* logits, float* offsets, float* votes, uint8_t* classes,
+                    uint8_t* fg, hipStream_t st);
 
 int launch_boundary_overlap(const int* pred, const int* gt, int H, int W, const int* labels, int n_pred, int n_gt, int radius,
                             void* ws, unsigned* out, hipStream_t st);

@@ -109,6 +109,14 @@ struct quber_ctx {
     const uint8_t* cur_depth = nullptr;
     const float* cur_off = nullptr;
     float* cur_out = nullptr;
+    // Depth Seeding Network contexts (with_network = 4): what the plan's first and last op read, set by quber_dsn_forward
+    const float* dsn_xyz = nullptr;
+    int dsn_flags = 0;
+    float* dsn_clean = nullptr;   // [Bmax][3][H][W]: xyz with NaN -> 0 and the y flag applied
+    double* dsn_stats = nullptr;  // GroupNorm sums of every norm of the plan, cleared by its first op
+    size_t dsn_stats_bytes = 0;
+    float *dsn_logits = nullptr, *dsn_offsets = nullptr, *dsn_votes = nullptr;
+    uint8_t *dsn_classes = nullptr, *dsn_fg = nullptr;
     double flops = 0.0;
     double wino_flops = 0.0;      // algorithmic FLOPs (batch 1) of the layers that take the Winograd path
     double wino_saved = 0.0;      // ... and the part of them the path does not execute
@@ -178,6 +186,7 @@ struct Builder {
 };
 void build_lmff(Builder& b);     // LMFFNet (plan_lmff.hip)
 void build_cgnet(Builder& b);    // CGNet (plan_cgnet.hip)
+void build_dsn(Builder& b);      // Depth Seeding Network of UOIS-Net-3D (plan_dsn.hip)
 
 int check_cfg(const quber_config& c);
 bool op_set_tuning(int key, int value);      // api_ops.hip: the process-only keys 2, 11, 12, 26 of quber_set_tuning; false: not one of them

@@ -51,6 +51,15 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
     (u8 / bool [H,W]) in place of masks.  The keys of ``MeanShift`` (``cluster_seeds`` is f32 [num_seeds,3], ``cluster_report`` i64 [6]:
     count, clusters found, dropped by ``min_pixels``, truncated, emptied by the IMP, fg pixels) and ``cluster_raw_ids`` (i32 [H,W]: the
     map before the IMP), ``cluster_centers`` (f32 [count,3]).  The same refusals; the input of the other clusterer is a ``ValueError``.
+  * ``seeding=DepthSeeding(weights_or_path, negate_y=True)`` beside ``cluster=GaussianMeanShift.uois()``: the votes and the foreground
+    come from UOIS-Net-3D's Depth Seeding Network on the device (csrc/dsn.hip, csrc/plan_dsn.hip, quber_amd/seeding; INTEGRATION.md
+    "Initial masks from a depth image").  ``predict`` / ``predict_batch`` take ``xyz=`` (f32 [H,W,3] or [3,H,W] per frame: the organised
+    point cloud, NaN where there is no depth; H and W multiples of 16) in place of ``center_votes=`` / ``fg=``; the network's votes and
+    foreground go to the clustering as device pointers on the same stream, and the dicts are those of the same votes handed over from
+    the host, bit for bit.  Only the three class counts per frame are read back: the seeded draw of a frame's first seed needs its
+    foreground count.  Every dict gains ``seeding_fg`` (u8 [H,W]: 0 background, 1 table, 2 objects) and ``seeding_report`` (i64 [3]: the
+    pixels of each class).  ``xyz=`` is a ``ValueError`` without ``seeding=``, together with ``center_votes=`` / ``fg=`` / masks, with a
+    ``cluster=`` that is not a ``GaussianMeanShift``, and in ``enqueue_batch`` / ``predict_stream``.
   * ``zoom=ZoomIn(crop=224, padding=0.25, min_overlap=0.5)``: the second, zoomed-in pass of the reference's base models (``crop_rois`` /
     ``match_label_crop``, eval/base_model.py:843-961) without leaving the device (csrc/zoom.hip; INTEGRATION.md "Zoom-in refinement"):
     every instance of pass 1 - run with all configured options, through post-processing and ``cleanup`` - is cropped with a padded box,
@@ -778,7 +787,7 @@ class RefinerModel:
         return self.frame_dict(rec, 0, k, masks_b, int(stg.pin_count[1]) if rec.it is not None else 0)
 
     # -- batched form on device-resident frames, split into "enqueue" and "collect" so that a caller can keep one batch in flight --
-    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None, d_scores=None, gt_labels=None):
+    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None, d_scores=None, gt_labels=None, xyz=None):
         """d_bgr / d_depth: u8 [B,H,W,3] (depth None for single-stream configs), d_masks: u8 [B,N,H,W] on the device.  Enqueues a1 ...
         a11 and the extraction of the first `slots` instance masks of every frame on the current stream WITHOUT synchronising;
         returns a handle for collect_batch().  halves=True (test-time augmentation only): the tensors are 2B-frame buffers
@@ -790,6 +799,8 @@ class RefinerModel:
             raise ValueError("nms: d_scores is required when nms= is set")
         if self.zoom is not None:
             raise ValueError("zoom: enqueue_batch / predict_stream have no zoomed form; use predict or predict_batch")
+        if xyz is not None:
+            raise ValueError("xyz: enqueue_batch / predict_stream have no seeding form; use predict or predict_batch")
         if self.cluster is not None:
             raise ValueError("cluster: enqueue_batch / predict_stream have no clustering form; use predict or predict_batch")
         if self.scene is not None:
@@ -916,8 +927,14 @@ class RefinerModel:
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
                  seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False,
-                 cleanup=None, perturb=None, nms=None, zoom=None, losses=None, cluster=None, scene=None, options=None):
+                 cleanup=None, perturb=None, nms=None, zoom=None, losses=None, cluster=None, scene=None, options=None, seeding=None):
         # the options (module docstring), checked before anything is loaded; options: a RefineOptions in their place
+        # seeding: None or a quber_amd.seeding.DepthSeeding - nothing is imported, allocated or launched for it without one
+        if seeding is not None:
+            from ..seeding import DepthSeeding
+            if not isinstance(seeding, DepthSeeding):
+                raise ValueError(f"seeding={seeding!r}: expected None or a quber_amd.seeding.DepthSeeding")
+        self.seeding = seeding
         self.options = options or RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
                                                       track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom,
                                                       losses=losses, cluster=cluster, scene=scene)
@@ -952,19 +969,21 @@ class MaskRefinerPredictor:
 
     # -- reference signature (predictor.py:287) --
     def predict(self, rgb_img, depth_img=None, perturbed_masks=None, mask_scores=None, gt_labels=None, embeddings=None, depth_z=None,
-                center_votes=None, fg=None, proposals=None):
+                center_votes=None, fg=None, proposals=None, xyz=None):
+        # xyz (with seeding= and cluster=GaussianMeanShift(), in place of center_votes / fg): f32 [H,W,3] or [3,H,W], the organised point cloud
         # gt_labels (with losses=): the frame's ground-truth label map, integer [H,W], 0 = none, 1..n; the dict then carries `losses`
         # embeddings (with cluster=, in place of perturbed_masks): f32 [64,H,W]; depth_z: f32 [H,W], the depth filter's plane
         # center_votes, fg (with cluster=GaussianMeanShift(), in place of perturbed_masks): f32 [3,H,W] = xyz + offsets, and u8 / bool [H,W]
-        if self.cluster is not None or embeddings is not None or depth_z is not None or center_votes is not None or fg is not None:
+        if self.cluster is not None or embeddings is not None or depth_z is not None or center_votes is not None or fg is not None or xyz is not None:
             if perturbed_masks is not None:
-                raise ValueError("cluster: embeddings= takes the place of the initial masks; both were given")
+                raise ValueError("cluster: embeddings= / center_votes= / xyz= take the place of the initial masks; both were given")
             if mask_scores is not None:
                 raise ValueError("cluster: the clustering's masks have no scores; mask_scores= was given")
             return self.predict_batch(rgb_img[None], None if depth_img is None else depth_img[None], None,
                                       gt_labels=None if gt_labels is None else [gt_labels],
                                       embeddings=None if embeddings is None else [embeddings], depth_z=None if depth_z is None else [depth_z],
-                                      center_votes=None if center_votes is None else [center_votes], fg=None if fg is None else [fg])
+                                      center_votes=None if center_votes is None else [center_votes], fg=None if fg is None else [fg],
+                                      xyz=None if xyz is None else [xyz])
         masks = np.zeros((0,) + rgb_img.shape[:2], np.uint8) if perturbed_masks is None else np.asarray(perturbed_masks)
         gts = None if gt_labels is None else [gt_labels]
         if self.scene is not None or proposals is not None:      # the general path; proposals (with scene=): u8 / bool [P,H,W], may be absent
@@ -1000,6 +1019,46 @@ class MaskRefinerPredictor:
         if self.cluster.imp is not None and imp_plane_bytes(H, W) > IMP_LDS_BYTES:
             raise ValueError(f"cluster: the IMP's two bit planes of a {H} x {W} frame do not fit the LDS; there is no global-memory fallback")
         return votes, np.ascontiguousarray((on != 0).astype(np.uint8))
+
+    def _xyz_inputs(self, B, H, W, xyz, masks_list, scores_list, embeddings, depth_z, center_votes, fg):
+        """seeding=: the checked point clouds of a call as one device tensor f32 [B,3,H,W], before anything is launched; None without xyz=."""
+        if xyz is None:
+            return None
+        if self.seeding is None:
+            raise ValueError("xyz= needs seeding= (a quber_amd.seeding.DepthSeeding)")
+        if not isinstance(self.cluster, GaussianMeanShift):
+            raise ValueError("xyz: the Depth Seeding Network's votes go to cluster=GaussianMeanShift(); this predictor has " +
+                             ("no cluster=" if self.cluster is None else "a MeanShift"))
+        if center_votes is not None or fg is not None:
+            raise ValueError("xyz: the network makes the votes and the foreground; center_votes= / fg= were given as well")
+        if embeddings is not None or depth_z is not None:
+            raise ValueError("cluster: a GaussianMeanShift takes xyz= or center_votes= and fg=, not embeddings= / depth_z=")
+        if masks_list is not None:
+            raise ValueError("xyz: the clustering makes the initial masks; masks were given as well")
+        if scores_list is not None:
+            raise ValueError("cluster: the clustering's masks have no scores; scores_list= was given")
+        if len(xyz) != B:
+            raise ValueError(f"xyz: the point clouds of {len(xyz)} frames for a batch of {B}")
+        if H % 16 or W % 16:
+            raise ValueError(f"xyz: the Depth Seeding Network needs a height and width that are multiples of 16, not {H} x {W}")
+        if self.cluster.imp is not None and imp_plane_bytes(H, W) > IMP_LDS_BYTES:
+            raise ValueError(f"cluster: the IMP's two bit planes of a {H} x {W} frame do not fit the LDS; there is no global-memory fallback")
+        from ..seeding import as_xyz_batch
+        return as_xyz_batch(list(xyz), H, W, self.device)
+
+    def _seed(self, x):
+        """xyz f32 [B,3,H,W] on the device -> (votes, fg, first, draws) for Engine.gms, all on the device, the class map u8 [B,H,W] and the
+        class counts i64 [B,3] (host).  One D2H of 3 B + 1 integers: the draw of a frame's first seed needs its foreground count."""
+        B, _, H, W = x.shape
+        votes, on, cls = self.seeding.engine_for(H, W, B, self.device).seed(x)
+        tally = torch.stack([(cls == k).sum((1, 2)) for k in range(3)], 1)
+        host = torch.cat([tally.reshape(-1), torch.isfinite(votes).all().to(torch.int64)[None]]).cpu().numpy()
+        if not host[-1]:
+            raise ValueError("seeding: the centre votes are not finite (xyz must be finite, or NaN where there is no depth)")
+        tally = host[:-1].reshape(B, 3)
+        first, draws = self.cluster.draws([self.cluster.n_sub(int(n)) for n in tally[:, 2]])
+        dev = lambda a: torch.from_numpy(a).to(self.device)
+        return (votes, on, dev(first), dev(draws.view(np.int32))), cls, tally
 
     def _scene_inputs(self, B, H, W, proposals):
         """scene=: the checked proposals of a call -> (u8 [B,P,H,W] with P = the longest list, zero rows behind a frame's own; their
@@ -1060,15 +1119,19 @@ class MaskRefinerPredictor:
         return emb, z
 
     def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None, gt_labels=None, embeddings=None, depth_z=None,
-                      center_votes=None, fg=None, proposals=None):
+                      center_votes=None, fg=None, proposals=None, xyz=None):
         """rgb_imgs/depth_imgs: u8 [B,H,W,3] arrays; masks_list: B arrays u8/bool [N_b,H,W]; scores_list (required with nms=): B arrays
         [N_b] of finite scores; gt_labels (with losses=): the B ground-truth label maps, integer [B,H,W] or a list.  With cluster=:
         masks_list is None, embeddings: B arrays f32 [64,H,W], depth_z: B arrays f32 [H,W] (with depth_threshold); or, with a
-        GaussianMeanShift, center_votes: B arrays f32 [3,H,W] and fg: B arrays u8 / bool [H,W].  With scene=: masks_list holds every frame's
+        GaussianMeanShift, center_votes: B arrays f32 [3,H,W] and fg: B arrays u8 / bool [H,W] - or, with seeding=, xyz: B point clouds f32
+        [H,W,3] / [3,H,W] in their place.  With scene=: masks_list holds every frame's
         GROUND TRUTH and proposals (optional) B arrays u8 / bool [P_b,H,W], the pool of segment proposals.  -> list of B dicts."""
         B, H, W = rgb_imgs.shape[:3]
         props = self._scene_inputs(B, H, W, proposals)
-        cluster_in = self._cluster_inputs(B, H, W, masks_list, scores_list, embeddings, depth_z, center_votes, fg)
+        seed_x = self._xyz_inputs(B, H, W, xyz, masks_list, scores_list, embeddings, depth_z, center_votes, fg)
+        seeded = None
+        # (with xyz=: a placeholder until the network has run, below, once every other check has passed)
+        cluster_in = () if seed_x is not None else self._cluster_inputs(B, H, W, masks_list, scores_list, embeddings, depth_z, center_votes, fg)
         gms = isinstance(self.cluster, GaussianMeanShift)
         # rows of the mask tensor per frame; with cluster=: one plane per cluster there can be - the seeds' labels but the largest (a
         # GaussianMeanShift: a label per seed, each with min_pixels pixels of the frame)
@@ -1114,12 +1177,19 @@ class MaskRefinerPredictor:
         elif cluster_in is None:
             d_masks[:B].copy_(torch.from_numpy(mk))
         else:                                             # the first seeds: drawn last, so that a call that raised above has drawn nothing
-            if gms:
+            if seed_x is not None:
+                cluster_in, *seeded = self._seed(seed_x)
+            elif gms:
                 first, draws = self.cluster.draws([self.cluster.n_sub(int(f.sum())) for f in cluster_in[1]])
                 cluster_in = (cluster_in[0], cluster_in[1], first, draws.view(np.int32))
             else:
                 cluster_in = (cluster_in[0], self.cluster.first_seeds(B, H * W), cluster_in[1])
-            cluster_in = tuple(None if a is None else torch.from_numpy(a).to(self.device) for a in cluster_in)
+            if seed_x is None:
+                cluster_in = tuple(None if a is None else torch.from_numpy(a).to(self.device) for a in cluster_in)
         rec = model.device_pass(eng, bgr, depth, d_masks, None if sc is None else torch.from_numpy(sc).to(self.device), B, may_stop=True,
                                 own=counts, gt=gt, cluster_in=cluster_in, scene_in=scene_in)
-        return model.results(rec, (bgr, depth))
+        outs = model.results(rec, (bgr, depth))
+        if seeded is not None:
+            for b, r in enumerate(outs):
+                r["seeding_fg"], r["seeding_report"] = seeded[0][b], torch.from_numpy(seeded[1][b].astype(np.int64))
+        return outs
