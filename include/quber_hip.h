@@ -856,6 +856,11 @@ int32_t quber_debug_persistent_segments(int32_t tiles, int32_t blocks, int32_t k
                                         int32_t* out4, int32_t cap);
 int32_t quber_debug_persistent_fixup(int32_t tiles, int32_t blocks, int32_t k_slices, int32_t min_share, int32_t xcd, int32_t j,
                                      int32_t* tile, int32_t* slots, int32_t cap);
+/* Host view of a device workspace layout, for the CPU tests: no GPU.  The bytes the layout walk of entry `which` ends at:
+ * 0 mask NMS (b frames, n masks), 1 COCO matching (b, n ground truths, flag = iou_type), 2 scene perturbation (b, n = N + P rows,
+ * m = max_masks), 3 mean shift, 4 Gaussian mean shift, 5 zoom-in, 6 losses (b = max_batch each), 7 clean-up, 8 post-processing
+ * (b, n = top_k); h x w frames; arguments an entry does not name are ignored.  -1: unknown `which`. */
+int64_t quber_debug_ws_bytes(int32_t which, int32_t b, int32_t n, int32_t m, int32_t h, int32_t w, int32_t flag);
 /* the launch plan of quber_forward, in execution order (after the input pre-processing kernel):
  * kind 0 = convolution, 1 = GroupNorm, 2 = other; flops = algorithmic FLOPs at batch 1 */
 int quber_num_ops(quber_ctx* ctx);

@@ -55,6 +55,21 @@ int quber::check_cfg(const quber_config& c) {
     return 0;
 }
 
+// Makes `w` hold at least `need` bytes: nothing when it already does, else a new buffer replaces the old one and alloc_bytes stays exact.
+// A buffer never shrinks; an entry that asks for the same size on every call allocates once.
+static int ws_reserve(quber_ctx* c, LazyWs& w, size_t need) {
+    if (need <= w.bytes) return 0;
+    if (w.p) {
+        QB_CHECK(hipFree(w.p));                              // (waits for the launches that may still use it)
+        c->alloc_bytes -= w.bytes;
+        w = LazyWs();
+    }
+    QB_CHECK(hipMalloc(&w.p, need));
+    w.bytes = need;
+    c->alloc_bytes += need;
+    return 0;
+}
+
 extern "C" {
 
 const char* quber_version(void) { return "quber-hip 0.1 (gfx950, fp32 MFMA)"; }
@@ -130,14 +145,8 @@ void quber_destroy(quber_ctx* c) {
         if (c->lane_stream[l]) (void)hipStreamDestroy(c->lane_stream[l]);
     }
     for (void* p : c->allocs) (void)hipFree(p);
-    if (c->perturb_ws) (void)hipFree(c->perturb_ws);
-    if (c->masknms_ws) (void)hipFree(c->masknms_ws);
-    if (c->cocoap_ws) (void)hipFree(c->cocoap_ws);
-    if (c->scene_ws) (void)hipFree(c->scene_ws);
-    if (c->meanshift_ws) (void)hipFree(c->meanshift_ws);
-    if (c->gms_ws) (void)hipFree(c->gms_ws);
-    if (c->zoom_ws) (void)hipFree(c->zoom_ws);
-    if (c->losses_ws) (void)hipFree(c->losses_ws);
+    for (LazyWs& w : c->lazy)
+        if (w.p) (void)hipFree(w.p);
     delete c;
 }
 
@@ -240,6 +249,21 @@ int32_t quber_debug_persistent_segments(int32_t tiles, int32_t blocks, int32_t k
 }
 int32_t quber_debug_persistent_fixup(int32_t tiles, int32_t blocks, int32_t k_slices, int32_t min_share, int32_t xcd, int32_t j, int32_t* tile, int32_t* slots, int32_t cap) {
     return quber::conv_persistent_fixup(tiles, blocks, k_slices, min_share, xcd, j, tile, slots, cap);
+}
+
+int64_t quber_debug_ws_bytes(int32_t which, int32_t b, int32_t n, int32_t m, int32_t h, int32_t w, int32_t flag) {
+    switch (which) {
+    case 0: return (int64_t)mask_nms_ws_bytes(b, n, h, w);
+    case 1: return (int64_t)coco_match_ws_bytes(b, n, h, w, flag);
+    case 2: return (int64_t)scene_ws_bytes(b, n, m, h, w);
+    case 3: return (int64_t)meanshift_ws_bytes(b, h, w);
+    case 4: return (int64_t)gms_ws_bytes(b, h, w);
+    case 5: return (int64_t)zoom_ws_bytes(b, h, w);
+    case 6: return (int64_t)losses_ws_bytes(b, h, w);
+    case 7: return (int64_t)cleanup_ws_bytes(b, h, w, n);
+    case 8: return (int64_t)postprocess_ws_bytes(b, h, w, n);
+    default: return -1;
+    }
 }
 
 int quber_profile_begin(quber_ctx* c) {
@@ -577,20 +601,9 @@ int quber_perturb_masks(quber_ctx* c, const uint8_t* masks, int32_t batch, int32
     const bool fits = perturb_fits_lds(H, W);
     if (placement == 1 && !fits) return fail("perturb: three bit planes of this frame do not fit the 160 KB of LDS a workgroup may declare");
     const bool lds = placement == 1 || (placement == 0 && fits);
-    if (!lds) {          // the only allocation of this entry: made on first use, kept, grown when a larger batch comes
-        const size_t need = perturb_ws_bytes(M, H, W);
-        if (need > c->perturb_ws_bytes) {
-            if (c->perturb_ws) {
-                QB_CHECK(hipFree(c->perturb_ws));            // (waits for the launches that may still use it)
-                c->alloc_bytes -= c->perturb_ws_bytes;
-                c->perturb_ws = nullptr; c->perturb_ws_bytes = 0;
-            }
-            QB_CHECK(hipMalloc(&c->perturb_ws, need));
-            c->perturb_ws_bytes = need;
-            c->alloc_bytes += need;
-        }
-    }
-    return launch_perturb(masks, M, H, W, programs, n_ops, ops_per_round, iou_targets, out, report, lds ? 1 : 0, c->perturb_ws, (hipStream_t)stream);
+    // the only allocation of this entry: made on first use, kept, grown when a larger batch comes
+    if (!lds && ws_reserve(c, c->lazy[WS_PERTURB], perturb_ws_bytes(M, H, W))) return -1;
+    return launch_perturb(masks, M, H, W, programs, n_ops, ops_per_round, iou_targets, out, report, lds ? 1 : 0, c->lazy[WS_PERTURB].p, (hipStream_t)stream);
 }
 
 // ---- mask NMS of scored, overlapping initial masks (masknms.hip); usable on a context without a network ----
@@ -606,13 +619,9 @@ int quber_mask_nms(quber_ctx* c, const uint8_t* masks, const float* scores, int3
     if (!ids || !report || (n_masks > 0 && (!masks || !scores || !out_masks || !source || !out_scores))) return fail("mask nms: null tensor");
     const size_t bytes = (size_t)batch * n_masks * H * W;
     if (out_masks != masks && out_masks < masks + bytes && masks < out_masks + bytes) return fail("mask nms: dev_out_masks overlaps dev_masks partially");
-    if (n_masks > 0 && !c->masknms_ws) {     // the only allocation of this entry: made by the first call, for max_batch x limit masks, and kept
-        const size_t need = mask_nms_ws_bytes(c->cfg.max_batch, limit, H, W);
-        QB_CHECK(hipMalloc(&c->masknms_ws, need));
-        c->masknms_ws_bytes = need;
-        c->alloc_bytes += need;
-    }
-    return launch_mask_nms(masks, scores, batch, n_masks, H, W, thresh, on_top, out_masks, ids, source, out_scores, report, c->masknms_ws,
+    // the only allocation of this entry: made by the first call, for max_batch x limit masks, and kept
+    if (n_masks > 0 && ws_reserve(c, c->lazy[WS_MASKNMS], mask_nms_ws_bytes(c->cfg.max_batch, limit, H, W))) return -1;
+    return launch_mask_nms(masks, scores, batch, n_masks, H, W, thresh, on_top, out_masks, ids, source, out_scores, report, c->lazy[WS_MASKNMS].p,
                            (hipStream_t)stream);
 }
 
@@ -631,20 +640,11 @@ int quber_scene_perturb(quber_ctx* c, const uint8_t* gt, const uint8_t* props, c
     if (!n_gt || !n_prop || !merge_act || !split_act || !split_try || !delete_act || !out_masks || !info || !report || (n_gt_rows > 0 && !gt) ||
         (n_prop_rows > 0 && (!props || !fp_act || !gs_act)))
         return fail("scene perturb: null tensor");
-    const size_t need = scene_ws_bytes(batch, n_gt_rows + n_prop_rows, max_masks, H, W);
-    if (need > c->scene_ws_bytes) {          // the only allocation of this entry: made on first use, kept, grown when a larger call comes
-        if (c->scene_ws) {
-            QB_CHECK(hipFree(c->scene_ws));                  // (waits for the launches that may still use it)
-            c->alloc_bytes -= c->scene_ws_bytes;
-            c->scene_ws = nullptr; c->scene_ws_bytes = 0;
-        }
-        QB_CHECK(hipMalloc(&c->scene_ws, need));
-        c->scene_ws_bytes = need;
-        c->alloc_bytes += need;
-    }
+    // the only allocation of this entry: made on first use, kept, grown when a larger call comes
+    if (ws_reserve(c, c->lazy[WS_SCENE], scene_ws_bytes(batch, n_gt_rows + n_prop_rows, max_masks, H, W))) return -1;
     const ScenePerturbArgs q{gt, props, n_gt, n_prop, n_gt_rows, n_prop_rows, max_masks, min_mask_ratio, fp_act, gs_act, merge_act, split_act,
                              split_try, delete_act, out_masks, info, report};
-    return launch_scene_perturb(q, batch, H, W, c->scene_ws, (hipStream_t)stream);
+    return launch_scene_perturb(q, batch, H, W, c->lazy[WS_SCENE].p, (hipStream_t)stream);
 }
 
 // ---- the per-frame half of COCO AP (cocoap.hip); usable on a context without a network ----
@@ -657,29 +657,16 @@ int quber_coco_match(quber_ctx* c, const uint8_t* dt, const float* scores, const
     if (n_gt < 0 || n_gt > 1024) return fail("coco match: n_gt outside 0..1024");
     if (iou_type != 0 && iou_type != 1) return fail("coco match: iou_type must be 0 (segm) or 1 (bbox)");
     const int H = c->cfg.height, W = c->cfg.width;
-    const size_t need = coco_match_ws_bytes(batch, n_gt, H, W, iou_type);
-    if (need > c->cocoap_ws_bytes) {         // the only allocation of this entry: made on first use, kept, grown when a larger call comes
-        if (c->cocoap_ws) {
-            QB_CHECK(hipFree(c->cocoap_ws));                 // (waits for the launches that may still use it)
-            c->alloc_bytes -= c->cocoap_ws_bytes;
-            c->cocoap_ws = nullptr; c->cocoap_ws_bytes = 0;
-        }
-        QB_CHECK(hipMalloc(&c->cocoap_ws, need));
-        c->cocoap_ws_bytes = need;
-        c->alloc_bytes += need;
-    }
+    // the only allocation of this entry: made on first use, kept, grown when a larger call comes
+    if (ws_reserve(c, c->lazy[WS_COCOAP], coco_match_ws_bytes(batch, n_gt, H, W, iou_type))) return -1;
     const CocoMatchArgs q{dt, scores, dt_boxes, n_dt, gt, gt_flags, gt_area, gt_boxes, n_gt, iou_type, iou_thrs, n_thrs, area_rng, n_rng,
                           counts, order, out_scores, dt_area, gt_area_used, iou, dtm, dtig, gi, gorder};
-    return launch_coco_match(q, batch, H, W, c->cocoap_ws, (hipStream_t)stream);
+    return launch_coco_match(q, batch, H, W, c->lazy[WS_COCOAP].p, (hipStream_t)stream);
 }
 
 // ---- mean-shift clustering of pixel embeddings into initial masks (meanshift.hip); usable on a context without a network ----
 static int meanshift_ws(quber_ctx* c) {      // the only allocation of the five entries: made by the first call, for max_batch frames, and kept
-    if (c->meanshift_ws) return 0;
-    const size_t need = meanshift_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width);
-    QB_CHECK(hipMalloc(&c->meanshift_ws, need));
-    c->alloc_bytes += need;
-    return 0;
+    return ws_reserve(c, c->lazy[WS_MEANSHIFT], meanshift_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width));
 }
 
 static int meanshift_args(quber_ctx* c, const char* what, int32_t batch, int32_t channels, int32_t num_seeds) {
@@ -697,7 +684,7 @@ int quber_meanshift_seeds(quber_ctx* c, const float* emb, int32_t batch, int32_t
     if (meanshift_args(c, "meanshift seeds", batch, channels, num_seeds)) return -1;
     if (!emb || !first || !indices) return fail("meanshift seeds: null tensor");
     if (meanshift_ws(c)) return -1;
-    return launch_meanshift_seeds(emb, first, batch, num_seeds, c->cfg.height, c->cfg.width, indices, c->meanshift_ws, c->cfg.max_batch,
+    return launch_meanshift_seeds(emb, first, batch, num_seeds, c->cfg.height, c->cfg.width, indices, c->lazy[WS_MEANSHIFT].p, c->cfg.max_batch,
                                   (hipStream_t)stream);
 }
 
@@ -708,7 +695,7 @@ int quber_meanshift_climb(quber_ctx* c, const float* emb, int32_t batch, int32_t
     if (iters < 0 || iters > 1000) return fail("meanshift climb: iters outside 0..1000");
     if (!(kappa >= 0.f) || kappa > 64.f) return fail("meanshift climb: kappa outside 0..64");
     if (meanshift_ws(c)) return -1;
-    return launch_meanshift_climb(emb, indices, seeds, batch, num_seeds, c->cfg.height, c->cfg.width, kappa, iters, c->meanshift_ws,
+    return launch_meanshift_climb(emb, indices, seeds, batch, num_seeds, c->cfg.height, c->cfg.width, kappa, iters, c->lazy[WS_MEANSHIFT].p,
                                   c->cfg.max_batch, (hipStream_t)stream);
 }
 
@@ -731,7 +718,7 @@ int quber_meanshift_assign(quber_ctx* c, const float* emb, int32_t batch, int32_
     if (!emb || !seeds || !seed_labels || !ids || !report || (n_masks > 0 && !masks)) return fail("meanshift assign: null tensor");
     if (meanshift_ws(c)) return -1;
     return launch_meanshift_assign(emb, seeds, seed_labels, depth_z, depth_threshold, batch, num_seeds, n_masks, c->cfg.height, c->cfg.width, ids,
-                                   masks, report, c->meanshift_ws, c->cfg.max_batch, (hipStream_t)stream);
+                                   masks, report, c->lazy[WS_MEANSHIFT].p, c->cfg.max_batch, (hipStream_t)stream);
 }
 
 int quber_meanshift_cluster(quber_ctx* c, const float* emb, int32_t batch, int32_t channels, const int32_t* first, int32_t num_seeds, float kappa,
@@ -749,21 +736,18 @@ int quber_meanshift_cluster(quber_ctx* c, const float* emb, int32_t batch, int32
     if (meanshift_ws(c)) return -1;
     const int H = c->cfg.height, W = c->cfg.width, cap = c->cfg.max_batch;
     hipStream_t st = (hipStream_t)stream;
-    if (launch_meanshift_seeds(emb, first, batch, num_seeds, H, W, indices, c->meanshift_ws, cap, st)) return -1;
-    if (launch_meanshift_climb(emb, indices, seeds, batch, num_seeds, H, W, kappa, iters, c->meanshift_ws, cap, st)) return -1;
+    if (launch_meanshift_seeds(emb, first, batch, num_seeds, H, W, indices, c->lazy[WS_MEANSHIFT].p, cap, st)) return -1;
+    if (launch_meanshift_climb(emb, indices, seeds, batch, num_seeds, H, W, kappa, iters, c->lazy[WS_MEANSHIFT].p, cap, st)) return -1;
     if (launch_meanshift_link(seeds, batch, num_seeds, epsilon, seed_labels, st)) return -1;
     return launch_meanshift_assign(emb, seeds, seed_labels, depth_z, depth_threshold, batch, num_seeds, n_masks, H, W, ids, masks, report,
-                                   c->meanshift_ws, cap, st);
+                                   c->lazy[WS_MEANSHIFT].p, cap, st);
 }
 
 // ---- Gaussian mean shift of centre votes into initial masks, and the IMP (gms.hip); usable on a context without a network ----
 static int gms_ws(quber_ctx* c) {            // the only allocation of the six entries: made by the first call, for max_batch frames, and kept
-    if (c->gms_ws) return 0;
+    if (c->lazy[WS_GMS].p) return 0;
     if (gms_prepare()) return -1;
-    const size_t need = gms_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width);
-    QB_CHECK(hipMalloc(&c->gms_ws, need));
-    c->alloc_bytes += need;
-    return 0;
+    return ws_reserve(c, c->lazy[WS_GMS], gms_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width));
 }
 
 static int gms_args(quber_ctx* c, const char* what, int32_t batch, int32_t num_seeds) {
@@ -778,7 +762,7 @@ int quber_gms_seeds(quber_ctx* c, const float* votes, const uint8_t* fg, int32_t
     if (gms_args(c, "gms seeds", batch, num_seeds)) return -1;
     if (!votes || !fg || !first || !draws || !indices) return fail("gms seeds: null tensor");
     if (gms_ws(c)) return -1;
-    return launch_gms_seeds(votes, fg, first, draws, batch, num_seeds, subsample, c->cfg.height, c->cfg.width, indices, info, c->gms_ws,
+    return launch_gms_seeds(votes, fg, first, draws, batch, num_seeds, subsample, c->cfg.height, c->cfg.width, indices, info, c->lazy[WS_GMS].p,
                             c->cfg.max_batch, (hipStream_t)stream);
 }
 
@@ -788,7 +772,7 @@ int quber_gms_climb(quber_ctx* c, const float* votes, const uint8_t* fg, int32_t
     if (!votes || !fg || !seeds) return fail("gms climb: null tensor");
     if (gms_ws(c)) return -1;
     return launch_gms_climb(votes, fg, indices, info, seeds, batch, num_seeds, subsample, c->cfg.height, c->cfg.width, sigma, iters, true,
-                            c->gms_ws, c->cfg.max_batch, (hipStream_t)stream);
+                            c->lazy[WS_GMS].p, c->cfg.max_batch, (hipStream_t)stream);
 }
 
 int quber_gms_link(quber_ctx* c, const float* seeds, int32_t batch, int32_t num_seeds, const int32_t* info, float epsilon, int32_t* seed_labels,
@@ -804,7 +788,7 @@ int quber_gms_assign(quber_ctx* c, const float* votes, const uint8_t* fg, int32_
     if (!votes || !fg || !seeds || !seed_labels || !ids || !centers || !report) return fail("gms assign: null tensor");
     if (gms_ws(c)) return -1;
     return launch_gms_assign(votes, fg, seeds, seed_labels, info, batch, num_seeds, n_masks, min_pixels, c->cfg.height, c->cfg.width, ids, masks,
-                             centers, report, c->gms_ws, c->cfg.max_batch, (hipStream_t)stream);
+                             centers, report, c->lazy[WS_GMS].p, c->cfg.max_batch, (hipStream_t)stream);
 }
 
 int quber_gms_imp(quber_ctx* c, int32_t* ids, int32_t batch, int32_t n_ids, int32_t ksize, int32_t largest, int32_t n_masks, uint8_t* masks,
@@ -812,7 +796,7 @@ int quber_gms_imp(quber_ctx* c, int32_t* ids, int32_t batch, int32_t n_ids, int3
     if (check_batch(c, batch)) return -1;
     if (!ids) return fail("gms imp: null tensor");
     if (gms_ws(c)) return -1;
-    return launch_gms_imp(ids, batch, n_ids, ksize, largest, n_masks, c->cfg.height, c->cfg.width, masks, centers, report, c->gms_ws,
+    return launch_gms_imp(ids, batch, n_ids, ksize, largest, n_masks, c->cfg.height, c->cfg.width, masks, centers, report, c->lazy[WS_GMS].p,
                           c->cfg.max_batch, c->cleanup_ws, (hipStream_t)stream);
 }
 
@@ -832,24 +816,20 @@ int quber_gms_cluster(quber_ctx* c, const float* votes, const uint8_t* fg, int32
     }
     if (gms_ws(c)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (launch_gms_seeds(votes, fg, first, draws, batch, num_seeds, subsample, H, W, indices, info, c->gms_ws, cap, st)) return -1;
-    if (launch_gms_climb(votes, fg, indices, info, seeds, batch, num_seeds, subsample, H, W, sigma, iters, false, c->gms_ws, cap, st)) return -1;
+    if (launch_gms_seeds(votes, fg, first, draws, batch, num_seeds, subsample, H, W, indices, info, c->lazy[WS_GMS].p, cap, st)) return -1;
+    if (launch_gms_climb(votes, fg, indices, info, seeds, batch, num_seeds, subsample, H, W, sigma, iters, false, c->lazy[WS_GMS].p, cap, st)) return -1;
     if (launch_gms_link(seeds, info, batch, num_seeds, epsilon, seed_labels, st)) return -1;
     if (launch_gms_assign(votes, fg, seeds, seed_labels, info, batch, num_seeds, n_masks, min_pixels, H, W, raw_ids, imp_ksize ? nullptr : masks,
-                          centers, report, c->gms_ws, cap, st))
+                          centers, report, c->lazy[WS_GMS].p, cap, st))
         return -1;
     if (launch_gms_copy_ids(raw_ids, ids, (size_t)batch * H * W, st)) return -1;
     if (!imp_ksize) return 0;
-    return launch_gms_imp(ids, batch, n_masks, imp_ksize, imp_largest, n_masks, H, W, masks, centers, report, c->gms_ws, cap, c->cleanup_ws, st);
+    return launch_gms_imp(ids, batch, n_masks, imp_ksize, imp_largest, n_masks, H, W, masks, centers, report, c->lazy[WS_GMS].p, cap, c->cleanup_ws, st);
 }
 
 // ---- zoom-in refinement: rois, crops, paste (zoom.hip); usable on a context without a network ----
 static int zoom_ws(quber_ctx* c) {           // the only allocation of the three entries: made by the first call, for max_batch frames, and kept
-    if (c->zoom_ws) return 0;
-    const size_t need = zoom_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width);
-    QB_CHECK(hipMalloc(&c->zoom_ws, need));
-    c->alloc_bytes += need;
-    return 0;
+    return ws_reserve(c, c->lazy[WS_ZOOM], zoom_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width));
 }
 
 static int zoom_aligned4(std::initializer_list<const void*> ps) {
@@ -866,7 +846,7 @@ int quber_zoom_rois(quber_ctx* c, const int32_t* ids, int32_t batch, int32_t n_i
     if (zoom_aligned4({ids, rois})) return -1;
     if (n_ids == 0) return 0;
     if (zoom_ws(c)) return -1;
-    return launch_zoom_rois(ids, batch, n_ids, c->cfg.height, c->cfg.width, padding, rois, c->zoom_ws, c->cfg.max_batch, (hipStream_t)stream);
+    return launch_zoom_rois(ids, batch, n_ids, c->cfg.height, c->cfg.width, padding, rois, c->lazy[WS_ZOOM].p, c->cfg.max_batch, (hipStream_t)stream);
 }
 
 int quber_zoom_crop(quber_ctx* c, const uint8_t* bgr, const uint8_t* depth, const int32_t* ids, const int32_t* slots, const int32_t* rois,
@@ -899,17 +879,13 @@ int quber_zoom_paste(quber_ctx* c, const int32_t* crop_ids, const float* crop_sc
     if (zoom_aligned4({crop_ids, crop_scores, table, area, slots, rois, out_ids, source, out_scores, boxes, report})) return -1;
     if (zoom_ws(c)) return -1;
     return launch_zoom_paste(crop_ids, crop_scores, table, area, depth_crop, slots, rois, batch, n_ids, n_slots, crop, n_crop_ids, min_overlap,
-                             max_inst, c->cfg.height, c->cfg.width, out_ids, out_masks, source, out_scores, boxes, report, c->zoom_ws,
+                             max_inst, c->cfg.height, c->cfg.width, out_ids, out_masks, source, out_scores, boxes, report, c->lazy[WS_ZOOM].p,
                              c->cfg.max_batch, (hipStream_t)stream);
 }
 
 // ---- validation losses: targets, loss record (losses.hip); usable on a context without a network ----
 static int losses_ws(quber_ctx* c) {         // the only allocation of the two entries: made by the first call, for max_batch frames, and kept
-    if (c->losses_ws) return 0;
-    const size_t need = losses_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width);
-    QB_CHECK(hipMalloc(&c->losses_ws, need));
-    c->alloc_bytes += need;
-    return 0;
+    return ws_reserve(c, c->lazy[WS_LOSSES], losses_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width));
 }
 
 int quber_loss_targets(quber_ctx* c, const int32_t* gt, int32_t batch, int32_t n_gt, int32_t sigma, int32_t small_area, float small_weight,
@@ -924,7 +900,7 @@ int quber_loss_targets(quber_ctx* c, const int32_t* gt, int32_t batch, int32_t n
     if ((uintptr_t)points & 7) return fail("loss targets: dev_points is not 8-byte aligned");
     if (losses_ws(c)) return -1;
     return launch_loss_targets(gt, batch, n_gt, c->cfg.height, c->cfg.width, sigma, small_area, small_weight, c->cfg.encode_legacy_f32 ? 1 : 0, gauss,
-                               targets, points, area, c->losses_ws, c->cfg.max_batch, (hipStream_t)stream);
+                               targets, points, area, c->lazy[WS_LOSSES].p, c->cfg.max_batch, (hipStream_t)stream);
 }
 
 int quber_losses(quber_ctx* c, const float* logits, int32_t n_planes, const float* targets, const uint8_t* explicit_maps, const quber_loss_spec* sp,
@@ -949,7 +925,7 @@ int quber_losses(quber_ctx* c, const float* logits, int32_t n_planes, const floa
     const long k = sp->top_k == 1.0 ? HW : (long)(sp->top_k * (double)HW);          // int(top_k * numel): model.py:70
     if (k < 1) return fail("losses: top_k selects no pixel of this frame (the reference would return NaN)");
     if (losses_ws(c)) return -1;
-    return launch_losses(logits, n_planes, targets, explicit_maps, *sp, ncls, k, batch, c->cfg.height, c->cfg.width, out, c->losses_ws,
+    return launch_losses(logits, n_planes, targets, explicit_maps, *sp, ncls, k, batch, c->cfg.height, c->cfg.width, out, c->lazy[WS_LOSSES].p,
                          c->cfg.max_batch, (hipStream_t)stream);
 }
 

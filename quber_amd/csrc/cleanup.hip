@@ -208,12 +208,6 @@ __global__ __launch_bounds__(CC_T) void cc_area_kernel(const int* __restrict__ i
 static_assert(CC_T == CC_BINS, "cc_area_kernel: one thread per bin");
 
 // workspace layout (bytes): ids | parent | area | nmin | nmax  i32 / u32 B*HW each | best u64 B*256 | report u32 B*255*4 | lut f32 B*256 | stats B*cap
-static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-size_t cleanup_ws_bytes(int B, int H, int W, int cap) {
-    const size_t px = (size_t)B * H * W;
-    return 5 * al(px * 4) + al((size_t)B * CC_BINS * 8) + al((size_t)B * 255 * 16) + al((size_t)B * CC_BINS * 4) + al((size_t)B * cap * sizeof(InstStat));
-}
-
 struct CcWs {
     int *ids, *parent, *nmin, *nmax;
     unsigned* area;
@@ -222,21 +216,22 @@ struct CcWs {
     float* lut;
     InstStat* stats;
 };
-static CcWs cc_carve(void* ws, int B, int H, int W) {
+static size_t cc_layout(CcWs* out, void* ws, int B, int H, int W, int cap) {
     const size_t px = (size_t)B * H * W;
-    char* w = reinterpret_cast<char*>(ws);
-    CcWs c;
-    c.ids = reinterpret_cast<int*>(w); w += al(px * 4);
-    c.parent = reinterpret_cast<int*>(w); w += al(px * 4);
-    c.area = reinterpret_cast<unsigned*>(w); w += al(px * 4);
-    c.nmin = reinterpret_cast<int*>(w); w += al(px * 4);
-    c.nmax = reinterpret_cast<int*>(w); w += al(px * 4);
-    c.best = reinterpret_cast<unsigned long long*>(w); w += al((size_t)B * CC_BINS * 8);
-    c.rep = reinterpret_cast<unsigned*>(w); w += al((size_t)B * 255 * 16);
-    c.lut = reinterpret_cast<float*>(w); w += al((size_t)B * CC_BINS * 4);
-    c.stats = reinterpret_cast<InstStat*>(w);
-    return c;
+    CcWs none, &c = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    c.ids = w.take<int>(px);
+    c.parent = w.take<int>(px);
+    c.area = w.take<unsigned>(px);
+    c.nmin = w.take<int>(px);
+    c.nmax = w.take<int>(px);
+    c.best = w.take<unsigned long long>((size_t)B * CC_BINS);
+    c.rep = w.take<unsigned>((size_t)B * 255 * 4);
+    c.lut = w.take<float>((size_t)B * CC_BINS);
+    c.stats = w.take<InstStat>((size_t)B * cap);
+    return w.off;
 }
+size_t cleanup_ws_bytes(int B, int H, int W, int cap) { return cc_layout(nullptr, nullptr, B, H, W, cap); }
 
 // `ws`: sized by cleanup_ws_bytes for a batch >= B of this frame size
 int launch_cleanup_ids(int* ids, int B, int H, int W, int n_ids, int conn, int keep_largest, int min_island, int max_hole, void* ws,
@@ -250,7 +245,8 @@ int launch_cleanup_ids(int* ids, int B, int H, int W, int n_ids, int conn, int k
     const long HW = (long)H * W;
     if (HW < 1 || (long)B * HW > 0x7fffffffL) return fail("cleanup: more than 2^31 - 1 pixels");
     if (!ids || !ws) return fail("cleanup: null tensor");
-    const CcWs c = cc_carve(ws, B, H, W);
+    CcWs c;
+    cc_layout(&c, ws, B, H, W, 0);           // (stats is the last field and not used here: its length does not matter)
     unsigned* rep = report ? report : c.rep;
     const dim3 grid((unsigned)((HW + CC_T - 1) / CC_T), (unsigned)B), blk(CC_T);
     const double px = (double)B * (double)HW;
@@ -308,7 +304,8 @@ int launch_cleanup_postprocess(const float* logits, int nch, int B, int H, int W
     if (cap < 1 || cap > 254) return fail("cleanup_postprocess: top_k outside 1..254");
     if (nch < 2) return fail("cleanup_postprocess: logits need the foreground and centre planes");
     if (!logits || !pan || !labels || !count || !scores || !boxes || !ws) return fail("cleanup_postprocess: null tensor");
-    const CcWs c = cc_carve(ws, B, H, W);
+    CcWs c;
+    cc_layout(&c, ws, B, H, W, cap);
     const long HW = (long)H * W;
     if (int rc = launch_relabel_panoptic(pan, labels, count, B, cap, 0, H, W, c.ids, st)) return rc;
     if (int rc = launch_cleanup_ids(c.ids, B, H, W, cap, conn, keep_largest, min_island, max_hole, ws, report, st)) return rc;

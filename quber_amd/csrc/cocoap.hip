@@ -285,14 +285,22 @@ __global__ __launch_bounds__(64) void ca_match_kernel(const double* __restrict__
     for (int d = n_top + lane; d < CA_TOP; d += 64) { dtm[out + d] = 0; dtig[out + d] = 0; }
 }
 
-// workspace layout: planes | inter, area (zeroed together) | boxes
-static size_t ca_align(size_t v) { return (v + 255) / 256 * 256; }
+// workspace layout: planes (segm only) | inter, area (zeroed together) | boxes
+struct CaWs { unsigned* planes; unsigned* inter; unsigned* area; double* boxes; size_t zero_bytes; };
 
-size_t coco_match_ws_bytes(int B, int n_gt, int H, int W, int bbox) {
-    const size_t P = CA_TOP + n_gt;
-    return (bbox ? 0 : ca_align((size_t)B * P * mn_plane_words(H, W) * 4)) + ca_align(((size_t)B * CA_TOP * n_gt + (size_t)B * P) * 4) +
-           ca_align((size_t)B * P * 4 * sizeof(double));
+static size_t ca_layout(CaWs* out, void* ws, int B, int n_gt, int H, int W, int bbox) {
+    const size_t b = (size_t)B, P = CA_TOP + n_gt, pairs = b * CA_TOP * n_gt;
+    CaWs none, &r = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    r.planes = bbox ? nullptr : w.take<unsigned>(b * P * mn_plane_words(H, W));
+    r.inter = w.take<unsigned>(pairs + b * P);
+    r.area = r.inter ? r.inter + pairs : nullptr;
+    r.zero_bytes = (pairs + b * P) * 4;
+    r.boxes = w.take<double>(b * P * 4);
+    return w.off;
 }
+
+size_t coco_match_ws_bytes(int B, int n_gt, int H, int W, int bbox) { return ca_layout(nullptr, nullptr, B, n_gt, H, W, bbox); }
 
 int coco_match_top() { return CA_TOP; }
 
@@ -316,24 +324,18 @@ int launch_coco_match(const CocoMatchArgs& q, int B, int H, int W, void* ws, hip
     if ((a8 & 7) || (a4 & 3)) return fail("coco match: a 64-bit tensor that is not 8-byte aligned, or a 32-bit one that is not 4-byte aligned");
     const long HW = (long)H * W;
     const int wpr = (W + 31) / 32, pw = (int)mn_plane_words(H, W), P = CA_TOP + n_gt;
-    char* p = static_cast<char*>(ws);
-    unsigned* planes = reinterpret_cast<unsigned*>(p);
-    if (!bbox) p += ca_align((size_t)B * P * pw * 4);
-    unsigned* inter = reinterpret_cast<unsigned*>(p);
-    unsigned* area = inter + (size_t)B * CA_TOP * n_gt;
-    const size_t zero_bytes = ((size_t)B * CA_TOP * n_gt + (size_t)B * P) * 4;
-    p += ca_align(zero_bytes);
-    double* boxes = reinterpret_cast<double*>(p);
+    CaWs w;
+    ca_layout(&w, ws, B, n_gt, H, W, bbox);
     {
         ProfScope prof("coco_rank", 4.0 * B * n_dt + 1.0 * B * n_gt, 0.0, st);
         hipLaunchKernelGGL(ca_rank_kernel, dim3(B), dim3(CA_MAX), 0, st, q.scores, q.gt_flags, n_dt, n_gt, q.counts, q.order, q.out_scores);
         QB_CHECK(hipGetLastError());
     }
-    if (launch_zero(inter, zero_bytes, st)) return -1;
+    if (launch_zero(w.inter, w.zero_bytes, st)) return -1;
     if (bbox) {
         ProfScope prof("coco_boxes", 32.0 * B * P, 0.0, st);
         hipLaunchKernelGGL(ca_box_kernel, dim3(P, B), dim3(256), 0, st, q.dt, q.gt, q.dt_boxes, q.gt_boxes, q.order, q.gt_flags, n_dt, n_gt, H, W,
-                           boxes);
+                           w.boxes);
         QB_CHECK(hipGetLastError());
     } else {
         {
@@ -341,22 +343,22 @@ int launch_coco_match(const CocoMatchArgs& q, int B, int H, int W, void* ws, hip
             const dim3 grid((pw + 255) / 256, P, B);
             const bool aligned = W % 16 == 0 && ((uintptr_t)q.dt & 15) == 0 && ((uintptr_t)q.gt & 15) == 0;
             if (aligned)
-                hipLaunchKernelGGL(ca_pack_kernel<true>, grid, dim3(256), 0, st, q.dt, q.gt, q.order, q.gt_flags, n_dt, n_gt, H, W, wpr, pw, planes, area);
+                hipLaunchKernelGGL(ca_pack_kernel<true>, grid, dim3(256), 0, st, q.dt, q.gt, q.order, q.gt_flags, n_dt, n_gt, H, W, wpr, pw, w.planes, w.area);
             else
-                hipLaunchKernelGGL(ca_pack_kernel<false>, grid, dim3(256), 0, st, q.dt, q.gt, q.order, q.gt_flags, n_dt, n_gt, H, W, wpr, pw, planes, area);
+                hipLaunchKernelGGL(ca_pack_kernel<false>, grid, dim3(256), 0, st, q.dt, q.gt, q.order, q.gt_flags, n_dt, n_gt, H, W, wpr, pw, w.planes, w.area);
             QB_CHECK(hipGetLastError());
         }
         if (n_gt > 0) {
             const int ntg = (n_gt + CA_TILE - 1) / CA_TILE;
             ProfScope prof("coco_gram", 4.0 * B * pw * ((double)CA_TOP * ntg + (double)n_gt * CA_DT_TILES) + 4.0 * B * CA_TOP * n_gt, 0.0, st);
-            hipLaunchKernelGGL(ca_gram_kernel, dim3(CA_DT_TILES * ntg, (pw + CA_CHUNK - 1) / CA_CHUNK, B), dim3(256), 0, st, planes, inter, n_gt, pw);
+            hipLaunchKernelGGL(ca_gram_kernel, dim3(CA_DT_TILES * ntg, (pw + CA_CHUNK - 1) / CA_CHUNK, B), dim3(256), 0, st, w.planes, w.inter, n_gt, pw);
             QB_CHECK(hipGetLastError());
         }
     }
     {
         ProfScope prof("coco_iou", 12.0 * B * CA_TOP * n_gt, 0.0, st);
         const long n = (long)P + (long)CA_TOP * n_gt;
-        hipLaunchKernelGGL(ca_iou_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, bbox, inter, area, boxes, q.counts, q.gt_flags,
+        hipLaunchKernelGGL(ca_iou_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, bbox, w.inter, w.area, w.boxes, q.counts, q.gt_flags,
                            q.gt_area, n_gt, q.dt_area, q.gt_area_used, q.iou);
         QB_CHECK(hipGetLastError());
     }

@@ -83,6 +83,21 @@ int device_cus();         // compute units of the CURRENT device (cached per dev
 void set_error(const std::string& msg);
 int fail(const std::string& msg);
 
+// A device workspace is one block that a file's xx_layout(XxWs* out, void* ws, dims...) walks ONCE: it hands out the field pointers and
+// returns the offset it ends at, so the size (xx_ws_bytes = the walk with nulls) and the pointers cannot drift apart.  Fields start on
+// 256-byte boundaries; base == nullptr measures only (every pointer comes back null).
+inline size_t ws_align(size_t v) { return (v + 255) / 256 * 256; }
+struct WsWalk {
+    char* base;
+    size_t off = 0;
+    // `count` elements at the current offset; pad = false: the next field follows without padding
+    template <class T> T* take(size_t count, bool pad = true) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += pad ? ws_align(count * sizeof(T)) : count * sizeof(T);
+        return p;
+    }
+};
+
 // Stage profiler (benchmark use only).  Between quber_profile_begin and quber_profile_end every launcher brackets its
 // kernels with a HIP-event pair recorded on the launch stream, tagged with a stage name and the ALGORITHMIC bytes
 // (what the stage must read + write once) and FLOPs of the bracket; outside such a window a ProfScope costs one

@@ -324,13 +324,19 @@ __global__ void quadruple_kernel(const uint8_t* __restrict__ ws, long BHW, long 
 }
 
 static inline int words_per_row(int W) { return (W + 63) / 64; }
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // [SetStat x 2 (256 B)] [byte-wise path: 4 * B*H*W] [mask bit planes] [boundary bit planes]   (Nmax masks per set)
-size_t errmaps_ws_bytes(int B, int Nmax, int H, int W) {
-    const size_t planes = (size_t)B * 2 * Nmax * H * words_per_row(W) * sizeof(u64);
-    return 256 + al256((size_t)4 * B * H * W) + 2 * al256(planes);
+struct ErWs { SetStat* stat; uint8_t* bytews; u64* mbits; u64* bbits; };
+static size_t er_layout(ErWs* out, void* ws, int B, int Nmax, int H, int W) {
+    const size_t planes = (size_t)B * 2 * Nmax * H * words_per_row(W);
+    ErWs none, &r = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    r.stat = w.take<SetStat>(2);
+    r.bytews = w.take<uint8_t>((size_t)4 * B * H * W);
+    r.mbits = w.take<u64>(planes);
+    r.bbits = w.take<u64>(planes);
+    return w.off;
 }
+size_t errmaps_ws_bytes(int B, int Nmax, int H, int W) { return er_layout(nullptr, nullptr, B, Nmax, H, W); }
 
 int launch_errmaps(const uint8_t* init, int N, const uint8_t* gt, int Ng, int B, int Nmax, int H, int W, int d, uint8_t* ws,
                    uint8_t* out, hipStream_t st) {
@@ -339,12 +345,9 @@ int launch_errmaps(const uint8_t* init, int N, const uint8_t* gt, int Ng, int B,
     if (words_per_row(W) > ER_MAX_WPR) return fail("error maps: frames wider than 2048 pixels are not supported");
     const long HW = (long)H * W, BHW = (long)B * HW;
     const int wpr = words_per_row(W), Ntot = N + Ng;
-    SetStat* stat = reinterpret_cast<SetStat*>(ws);
-    uint8_t* bytews = ws + 256;
-    const size_t planes = al256((size_t)B * 2 * Nmax * H * wpr * sizeof(u64));
-    u64* mbits = reinterpret_cast<u64*>(bytews + al256((size_t)4 * BHW));
-    u64* bbits = reinterpret_cast<u64*>(reinterpret_cast<uint8_t*>(mbits) + planes);
-    if (int rc = launch_zero(stat, 2 * sizeof(SetStat), st)) return rc;
+    ErWs k;
+    er_layout(&k, ws, B, Nmax, H, W);
+    if (int rc = launch_zero(k.stat, 2 * sizeof(SetStat), st)) return rc;
     {   // every mask byte once in, one bit out
         ProfScope prof("errmaps_pack", (double)BHW * Ntot * (1.0 + 1.0 / 8), 0.0, st);
         const bool fast = (W & 15) == 0 && (((uintptr_t)init | (uintptr_t)gt) & 15) == 0;
@@ -354,34 +357,34 @@ int launch_errmaps(const uint8_t* init, int N, const uint8_t* gt, int Ng, int B,
             if (n == 0) continue;
             if (fast)
                 hipLaunchKernelGGL(errmaps_pack_kernel, dim3((unsigned)(((long)H * wpr * 4 + 256 * PACK_IT - 1) / (256 * PACK_IT)), n, B), dim3(256), 0, st,
-                                   src, n, H, W, wpr, mbits, n0, Ntot, stat + s);
+                                   src, n, H, W, wpr, k.mbits, n0, Ntot, k.stat + s);
             else
                 hipLaunchKernelGGL(errmaps_pack_ballot_kernel, dim3((unsigned)(((long)H * wpr + 3) / 4), n, B), dim3(256), 0, st,
-                                   src, n, H, W, wpr, mbits, n0, Ntot, stat + s);
+                                   src, n, H, W, wpr, k.mbits, n0, Ntot, k.stat + s);
         }
     }
     QB_CHECK(hipGetLastError());
     if (Ntot > 0) {   // bit planes in, boundary bit planes out
         ProfScope prof("errmaps_erode", (double)B * Ntot * H * wpr * 16.0, 0.0, st);
         const size_t sm = (size_t)2 * (ER_ROWS + 2 * d) * wpr * sizeof(u64);
-        hipLaunchKernelGGL(errmaps_erode_kernel, dim3((H + ER_ROWS - 1) / ER_ROWS, Ntot, B), dim3(256), sm, st, mbits, H, wpr, d,
-                           bbits, stat);
+        hipLaunchKernelGGL(errmaps_erode_kernel, dim3((H + ER_ROWS - 1) / ER_ROWS, Ntot, B), dim3(256), sm, st, k.mbits, H, wpr, d,
+                           k.bbits, k.stat);
     }
     QB_CHECK(hipGetLastError());
     {   // both bit-plane sets in, eight one-hot byte planes out
         ProfScope prof("errmaps_quadruple", (double)BHW * (8.0 + Ntot * 2.0 / 8), 0.0, st);
         hipLaunchKernelGGL(errmaps_quadruple_bits_kernel, dim3((unsigned)(((long)H * wpr * 4 + 255) / 256), B), dim3(256), 0, st,
-                           mbits, bbits, N, Ng, H, W, wpr, stat, out);
+                           k.mbits, k.bbits, N, Ng, H, W, wpr, k.stat, out);
     }
     QB_CHECK(hipGetLastError());
     // grey-level masks only (each kernel returns at once otherwise)
     const size_t sm = (size_t)(ET_H + 2 * d) * (ET_W + 2 * d) + (size_t)(ET_H + 2 * d) * ET_W;
     dim3 grid((W + ET_W - 1) / ET_W, (H + ET_H - 1) / ET_H, B);
-    hipLaunchKernelGGL(fg_boundary_kernel, grid, dim3(256), sm, st, gt, Ng, H, W, d, bytews, bytews + 2 * BHW, stat);
-    hipLaunchKernelGGL(fg_boundary_kernel, grid, dim3(256), sm, st, init, N, H, W, d, bytews + BHW, bytews + 3 * BHW, stat);
+    hipLaunchKernelGGL(fg_boundary_kernel, grid, dim3(256), sm, st, gt, Ng, H, W, d, k.bytews, k.bytews + 2 * BHW, k.stat);
+    hipLaunchKernelGGL(fg_boundary_kernel, grid, dim3(256), sm, st, init, N, H, W, d, k.bytews + BHW, k.bytews + 3 * BHW, k.stat);
     int blocks = (int)((BHW + 255) / 256);
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(quadruple_kernel, dim3(blocks), dim3(256), 0, st, bytews, BHW, HW, out, stat);
+    hipLaunchKernelGGL(quadruple_kernel, dim3(blocks), dim3(256), 0, st, k.bytews, BHW, HW, out, k.stat);
     QB_CHECK(hipGetLastError());
     return 0;
 }

@@ -400,13 +400,25 @@ static inline int eb_wpr(int W) { return (W + 63) / 64; }
 size_t eval_batch_out_bytes(int batch, int cap) { return (size_t)batch * eb_layout(cap).bytes; }
 
 // ws: flags u32 [B][2][LAB_MAX] | score f64 [B][cap][cap] | mat f64 [B][cap][cap] | planes u64 [3][B][2 cap][H][wpr] (with_boundary) |
-//     lut u16 [B][2][LAB_MAX] | rows i32 [B] | cols i32 [B]
-size_t eval_batch_ws_bytes(int batch, int H, int W, int cap, int with_boundary) {
+//     lut u16 [B][2][LAB_MAX] | rows i32 [B] | cols i32 [B]; the fields follow each other without padding
+struct EbWs { unsigned* flags; double* score; double* mat; u64 *seg, *bmap, *dil; unsigned short* lut; int *rows, *cols; };
+static size_t eb_ws_layout(EbWs* out, void* ws, int batch, int H, int W, int cap, int with_boundary) {
     const size_t B = (size_t)batch, cc = (size_t)cap * cap;
-    size_t n = B * 2 * LAB_MAX * sizeof(unsigned) + 2 * B * cc * sizeof(double) + B * 2 * LAB_MAX * sizeof(unsigned short) + 2 * B * sizeof(int);
-    if (with_boundary) n += (size_t)3 * B * 2 * cap * H * eb_wpr(W) * sizeof(u64);
-    return (n + 7) & ~(size_t)7;
+    const size_t planes = with_boundary ? B * 2 * cap * H * eb_wpr(W) : 0;        // words of one of the three sets
+    EbWs none, &r = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    r.flags = w.take<unsigned>(B * 2 * LAB_MAX, false);
+    r.score = w.take<double>(B * cc, false);
+    r.mat = w.take<double>(B * cc, false);
+    r.seg = w.take<u64>(3 * planes, false);
+    r.bmap = r.seg ? r.seg + planes : nullptr;
+    r.dil = r.seg ? r.seg + 2 * planes : nullptr;
+    r.lut = w.take<unsigned short>(B * 2 * LAB_MAX, false);
+    r.rows = w.take<int>(2 * B, false);
+    r.cols = r.rows ? r.rows + B : nullptr;
+    return (w.off + 7) & ~(size_t)7;
 }
+size_t eval_batch_ws_bytes(int batch, int H, int W, int cap, int with_boundary) { return eb_ws_layout(nullptr, nullptr, batch, H, W, cap, with_boundary); }
 
 int launch_munkres_batch(const double* score, const int* rows, const int* cols, int batch, int cap, int placement, double* mat, int* assign,
                          long assign_stride, int* status, long status_stride, hipStream_t st) {
@@ -448,50 +460,41 @@ int launch_eval_batch(const int* pred, const int* gt, int batch, int H, int W, i
     const EbLayout L = eb_layout(cap);
     const size_t B = (size_t)batch, cc = (size_t)cap * cap;
     const long n = (long)H * W;
-    char* w = reinterpret_cast<char*>(ws);
     char* out = reinterpret_cast<char*>(out_);
-    unsigned* flags = reinterpret_cast<unsigned*>(w); w += B * 2 * LAB_MAX * sizeof(unsigned);
-    double* score = reinterpret_cast<double*>(w); w += B * cc * sizeof(double);
-    double* mat = reinterpret_cast<double*>(w); w += B * cc * sizeof(double);
-    u64* seg = reinterpret_cast<u64*>(w);
-    const size_t planes = with_boundary ? B * 2 * cap * H * wpr : 0;              // words of one of the three sets
-    u64 *bmap = seg + planes, *dil = bmap + planes;
-    w += 3 * planes * sizeof(u64);
-    unsigned short* lut = reinterpret_cast<unsigned short*>(w); w += B * 2 * LAB_MAX * sizeof(unsigned short);
-    int* rows = reinterpret_cast<int*>(w);
-    int* cols = rows + B;
+    EbWs w;
+    eb_ws_layout(&w, ws, batch, H, W, cap, with_boundary);
 
     // accumulators: the records (table, out-of-range flag; and every field a stage leaves alone reads 0) and the presence flags
     if (int rc = launch_zero(out, B * L.bytes, st)) return rc;
-    if (int rc = launch_zero(flags, B * 2 * LAB_MAX * sizeof(unsigned), st)) return rc;
+    if (int rc = launch_zero(w.flags, B * 2 * LAB_MAX * sizeof(unsigned), st)) return rc;
     int blocks = (int)((n + 255) / 256);
     if (blocks > 1024) blocks = 1024;
     {
         ProfScope prof("eval_labels", 16.0 * batch * (double)n, 0.0, st);
-        hipLaunchKernelGGL(eb_presence_kernel, dim3(blocks, batch), dim3(256), 0, st, pred, gt, n, flags, out, L);
-        hipLaunchKernelGGL(eb_rank_kernel, dim3(2, batch), dim3(1024), 0, st, flags, cap, lut, out, L);
-        hipLaunchKernelGGL(eb_contingency_kernel, dim3(blocks, batch), dim3(256), sizeof(unsigned) * 4096, st, pred, gt, n, lut, cap, out, L);
+        hipLaunchKernelGGL(eb_presence_kernel, dim3(blocks, batch), dim3(256), 0, st, pred, gt, n, w.flags, out, L);
+        hipLaunchKernelGGL(eb_rank_kernel, dim3(2, batch), dim3(1024), 0, st, w.flags, cap, w.lut, out, L);
+        hipLaunchKernelGGL(eb_contingency_kernel, dim3(blocks, batch), dim3(256), sizeof(unsigned) * 4096, st, pred, gt, n, w.lut, cap, out, L);
         QB_CHECK(hipGetLastError());
     }
     if (with_boundary) {
         ProfScope prof("eval_boundary", 8.0 * batch * (double)n, 0.0, st);
         hipLaunchKernelGGL(eb_pack_kernel, dim3((unsigned)(((long)H * wpr + 3) / 4), 2 * cap, batch), dim3(256), 0, st, pred, gt, H, W, wpr, cap,
-                           out, L, seg);
+                           out, L, w.seg);
         QB_CHECK(hipGetLastError());
         QB_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(eb_bmap_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      160 * 1024 - 64));
-        hipLaunchKernelGGL(eb_bmap_kernel, dim3(2 * cap, batch), dim3(1024), plane, st, seg, H, W, wpr, radius, cap, out, L, bmap, dil);
+        hipLaunchKernelGGL(eb_bmap_kernel, dim3(2 * cap, batch), dim3(1024), plane, st, w.seg, H, W, wpr, radius, cap, out, L, w.bmap, w.dil);
         QB_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(eb_pair_kernel, dim3(cap, cap, batch), dim3(256), 0, st, bmap, dil, H * wpr, cap, out, L);
+        hipLaunchKernelGGL(eb_pair_kernel, dim3(cap, cap, batch), dim3(256), 0, st, w.bmap, w.dil, H * wpr, cap, out, L);
         QB_CHECK(hipGetLastError());
     }
     {
         ProfScope prof("eval_score", 16.0 * batch * cc, 0.0, st);
-        hipLaunchKernelGGL(eb_score_kernel, dim3(batch), dim3(EB_T), 0, st, out, L, cap, score, rows, cols);
+        hipLaunchKernelGGL(eb_score_kernel, dim3(batch), dim3(EB_T), 0, st, out, L, cap, w.score, w.rows, w.cols);
         QB_CHECK(hipGetLastError());
     }
     const long stride = (long)(L.bytes / sizeof(int));
-    if (int rc = launch_munkres_batch(score, rows, cols, batch, cap, placement, mat, reinterpret_cast<int*>(out + L.assign), stride,
+    if (int rc = launch_munkres_batch(w.score, w.rows, w.cols, batch, cap, placement, w.mat, reinterpret_cast<int*>(out + L.assign), stride,
                                       reinterpret_cast<int*>(out + L.hdr) + 7, stride, st))
         return rc;
     {

@@ -537,30 +537,25 @@ __global__ __launch_bounds__(GM_SMAX) void gm_imp_finish_kernel(const unsigned* 
 // workspace, for `cap_b` frames of HW pixels
 struct GmWs { int* info; unsigned* hist; unsigned* flags; int* table; int* cnt; float* xs; float* mind; int* raw; float* part; };
 
-static size_t gm_align(size_t v) { return (v + 255) / 256 * 256; }
 static int gm_nblk(long HW) { return (int)((HW + GM_CHUNK - 1) / GM_CHUNK); }
 
-static GmWs gm_carve(void* ws, int cap_b, long HW) {
-    GmWs r;
-    char* p = static_cast<char*>(ws);
-    r.info = reinterpret_cast<int*>(p);        p += gm_align((size_t)cap_b * 4 * 4);
-    r.hist = reinterpret_cast<unsigned*>(p);   p += gm_align((size_t)cap_b * (GM_SMAX + 1) * 4);
-    r.flags = reinterpret_cast<unsigned*>(p);  p += gm_align((size_t)cap_b * 16 * 4);       // [2][cap_b][8]: before, after
-    r.table = reinterpret_cast<int*>(p);       p += gm_align((size_t)cap_b * (GM_SMAX + 1) * 4);
-    r.cnt = reinterpret_cast<int*>(p);         p += gm_align((size_t)cap_b * gm_nblk(HW) * 4);
-    r.xs = reinterpret_cast<float*>(p);        p += gm_align((size_t)cap_b * 3 * HW * 4);
-    r.mind = reinterpret_cast<float*>(p);      p += gm_align((size_t)cap_b * HW * 4);
-    r.raw = reinterpret_cast<int*>(p);         p += gm_align((size_t)cap_b * HW * 4);
-    r.part = reinterpret_cast<float*>(p);
-    return r;
+static size_t gm_layout(GmWs* out, void* ws, int cap_b, long HW) {
+    const size_t cb = (size_t)cap_b;
+    GmWs none, &r = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    r.info = w.take<int>(cb * 4);
+    r.hist = w.take<unsigned>(cb * (GM_SMAX + 1));
+    r.flags = w.take<unsigned>(cb * 16);                    // [2][cap_b][8]: before, after
+    r.table = w.take<int>(cb * (GM_SMAX + 1));
+    r.cnt = w.take<int>(cb * gm_nblk(HW));
+    r.xs = w.take<float>(cb * 3 * HW);
+    r.mind = w.take<float>(cb * HW);
+    r.raw = w.take<int>(cb * HW);
+    r.part = w.take<float>(cb * GM_G * GM_SMAX * 4);
+    return w.off;
 }
 
-size_t gms_ws_bytes(int cap_b, int H, int W) {
-    const long HW = (long)H * W;
-    return gm_align((size_t)cap_b * 16) + 2 * gm_align((size_t)cap_b * (GM_SMAX + 1) * 4) + gm_align((size_t)cap_b * 64) +
-           gm_align((size_t)cap_b * gm_nblk(HW) * 4) + gm_align((size_t)cap_b * 3 * HW * 4) + 2 * gm_align((size_t)cap_b * HW * 4) +
-           gm_align((size_t)cap_b * GM_G * GM_SMAX * 16);
-}
+size_t gms_ws_bytes(int cap_b, int H, int W) { return gm_layout(nullptr, nullptr, cap_b, (long)H * W); }
 
 // once per process, from the call that allocates the workspace: the IMP kernel may use more than the default 64 KiB of LDS
 int gms_prepare() {
@@ -598,7 +593,8 @@ int launch_gms_seeds(const float* votes, const uint8_t* fg, const int* first, co
     if (gm_check("gms seeds", B, cap_b, S, H, W, {votes, first, draws, idx}, ws)) return -1;
     if (info && ((uintptr_t)info & 3)) return fail("gms seeds: a 32-bit tensor that is not 4-byte aligned");
     const long HW = (long)H * W;
-    const GmWs w = gm_carve(ws, cap_b, HW);
+    GmWs w;
+    gm_layout(&w, ws, cap_b, HW);
     if (gm_compact(votes, fg, B, S, HW, sub, info, w, st)) return -1;
     ProfScope prof("gms_seeds", (double)S * B * HW / sub * 20.0, (double)S * B * HW / sub * 12.0, st);
     hipLaunchKernelGGL(gm_seed_kernel, dim3(B), dim3(1024), 0, st, w.xs, w.info, first, draws, HW, S, w.mind, idx);
@@ -614,7 +610,8 @@ int launch_gms_climb(const float* votes, const uint8_t* fg, const int* idx, cons
     if (iters < 0 || iters > 1000) return fail("gms climb: iters outside 0..1000");
     if (!(sigma > 0.f) || !std::isfinite(sigma)) return fail("gms climb: sigma must be positive");
     const long HW = (long)H * W;
-    const GmWs w = gm_carve(ws, cap_b, HW);
+    GmWs w;
+    gm_layout(&w, ws, cap_b, HW);
     if (sub < 1 || sub > 64) return fail("gms: subsample outside 1..64");
     if (compact && gm_compact(votes, fg, B, S, HW, sub, nullptr, w, st)) return -1;
     if (idx) {
@@ -662,7 +659,8 @@ int launch_gms_assign(const float* votes, const uint8_t* fg, const float* Z, con
     if (N < 1 || N > GM_NMAX) return fail("gms assign: n_masks outside 1..254");
     if (min_pixels < 0) return fail("gms assign: negative min_pixels");
     const long HW = (long)H * W;
-    const GmWs w = gm_carve(ws, cap_b, HW);
+    GmWs w;
+    gm_layout(&w, ws, cap_b, HW);
     if (launch_zero(w.hist, (size_t)cap_b * (GM_SMAX + 1) * 4, st)) return -1;
     {
         ProfScope prof("gms_assign", (double)B * HW * 17.0, 10.0 * B * (double)HW * S, st);
@@ -704,7 +702,8 @@ int launch_gms_imp(int* ids, int B, int n_ids, int ksize, int largest, int N, in
     const size_t lds = gms_imp_lds_bytes(H, W);
     if (lds > GM_LDS_MAX) return fail("gms imp: the two bit planes of a frame do not fit the LDS (2 * H * ceil(W / 32) * 4 bytes > 152 KiB)");
     const long HW = (long)H * W;
-    const GmWs w = gm_carve(ws, cap_b, HW);
+    GmWs w;
+    gm_layout(&w, ws, cap_b, HW);
     unsigned *before = w.flags, *after = w.flags + (size_t)cap_b * 8;
     if (launch_zero(after, (size_t)cap_b * 8 * 4, st)) return -1;
     {

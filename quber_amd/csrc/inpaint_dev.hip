@@ -456,14 +456,31 @@ __global__ void tel_reset_kernel(const Tel a) {
     }
 }
 
-inline size_t al(size_t n) { return (n + 255) & ~(size_t)255; }
+// the workspace pointers of `a` (null: measure only) for B frames with their one-pixel border
+size_t tel_layout(Tel* out, void* ws, int B, int H, int W) {
+    const size_t px = (size_t)B * H * W, pp = (size_t)B * (H + 2) * (W + 2);
+    Tel none{}, &a = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    a.zero = w.take<uint8_t>(px);
+    a.img = w.take<uint8_t>(pp);
+    a.m = w.take<uint8_t>(pp);
+    a.f = w.take<uint8_t>(pp);
+    a.ring = w.take<uint8_t>(pp);
+    a.parent = w.take<int>(pp);
+    a.T = w.take<float>(pp);
+    a.cnt = w.take<int>(pp);
+    a.bbox = w.take<int>(pp * 4);
+    a.heap_in = w.take<DNode>(pp);
+    a.heap_out = w.take<DNode>(pp);
+    a.comp_root = w.take<int>(pp);
+    a.comp_off = w.take<int>(pp);
+    a.counters = w.take<int>(16);
+    return w.off;
+}
 
 }  // namespace
 
-size_t inpaint_depth_ws_bytes(int B, int H, int W) {
-    const size_t px = (size_t)B * H * W, pp = (size_t)B * (H + 2) * (W + 2);
-    return al(px) + al(pp) * 4 + al(pp * 4) * 3 + al(pp * 16) + al(pp * sizeof(DNode)) * 2 + al(pp * 4) * 2 + al(64);
-}
+size_t inpaint_depth_ws_bytes(int B, int H, int W) { return tel_layout(nullptr, nullptr, B, H, W); }
 
 // depth3 / out3: device u8 [B][H][W][3]
 int launch_inpaint_depth(const uint8_t* depth3, int B, int H, int W, int kernel, void* ws, size_t ws_bytes, uint8_t* out3, hipStream_t st) {
@@ -475,21 +492,7 @@ int launch_inpaint_depth(const uint8_t* depth3, int B, int H, int W, int kernel,
     a.B = B; a.H = H; a.W = W; a.R = H + 2; a.C = W + 2; a.range = std::max(1, std::min(100, kernel));
     a.depth3 = depth3; a.out3 = out3;
     const size_t px = (size_t)B * H * W, pp = (size_t)B * a.R * a.C;
-    char* w = reinterpret_cast<char*>(ws);
-    a.zero = reinterpret_cast<uint8_t*>(w); w += al(px);
-    a.img = reinterpret_cast<uint8_t*>(w); w += al(pp);
-    a.m = reinterpret_cast<uint8_t*>(w); w += al(pp);
-    a.f = reinterpret_cast<uint8_t*>(w); w += al(pp);
-    a.ring = reinterpret_cast<uint8_t*>(w); w += al(pp);
-    a.parent = reinterpret_cast<int*>(w); w += al(pp * 4);
-    a.T = reinterpret_cast<float*>(w); w += al(pp * 4);
-    a.cnt = reinterpret_cast<int*>(w); w += al(pp * 4);
-    a.bbox = reinterpret_cast<int*>(w); w += al(pp * 16);
-    a.heap_in = reinterpret_cast<DNode*>(w); w += al(pp * sizeof(DNode));
-    a.heap_out = reinterpret_cast<DNode*>(w); w += al(pp * sizeof(DNode));
-    a.comp_root = reinterpret_cast<int*>(w); w += al(pp * 4);
-    a.comp_off = reinterpret_cast<int*>(w); w += al(pp * 4);
-    a.counters = reinterpret_cast<int*>(w);
+    tel_layout(&a, ws, B, H, W);
     static const hipError_t lds_ok = hipFuncSetAttribute((const void*)tel_march_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WIN_BYTES);
     QB_CHECK(lds_ok);
     if (int rc = launch_zero(a.counters, 64, st)) return rc;

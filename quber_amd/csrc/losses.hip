@@ -362,36 +362,31 @@ __global__ __launch_bounds__(64) void ls_finish_kernel(const double* __restrict_
 // layout for `cap_b` frames: mom | centres | partials | above partials | histograms | select states | foreground plane
 struct LsWs { unsigned long long* mom; LtCentre* cen; double* part; double* apart; unsigned* hist; unsigned long long* state; double* fgp; };
 
-static size_t ls_align(size_t v) { return (v + 255) / 256 * 256; }
 static int ls_blocks(long HW) { return (int)((HW + LS_CHUNK - 1) / LS_CHUNK); }
 
-static LsWs ls_carve(void* ws, int cap_b, int H, int W) {
+static size_t ls_layout(LsWs* out, void* ws, int cap_b, int H, int W) {
     const long HW = (long)H * W;
-    const size_t nblk = (size_t)ls_blocks(HW);
-    LsWs r;
-    char* p = static_cast<char*>(ws);
-    r.mom = reinterpret_cast<unsigned long long*>(p);    p += ls_align((size_t)cap_b * LS_MAXID * 24);
-    r.cen = reinterpret_cast<LtCentre*>(p);              p += ls_align((size_t)cap_b * LS_MAXID * sizeof(LtCentre));
-    r.part = reinterpret_cast<double*>(p);               p += ls_align((size_t)cap_b * nblk * LS_NACC * 8);
-    r.apart = reinterpret_cast<double*>(p);              p += ls_align((size_t)cap_b * nblk * 8);
-    r.hist = reinterpret_cast<unsigned*>(p);             p += ls_align((size_t)cap_b * LS_BINS * 4);
-    r.state = reinterpret_cast<unsigned long long*>(p);  p += ls_align((size_t)cap_b * 32);
-    r.fgp = reinterpret_cast<double*>(p);
-    return r;
+    const size_t cb = (size_t)cap_b, nblk = (size_t)ls_blocks(HW);
+    LsWs none, &r = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    r.mom = w.take<unsigned long long>(cb * LS_MAXID * 3);
+    r.cen = w.take<LtCentre>(cb * LS_MAXID);
+    r.part = w.take<double>(cb * nblk * LS_NACC);
+    r.apart = w.take<double>(cb * nblk);
+    r.hist = w.take<unsigned>(cb * LS_BINS);
+    r.state = w.take<unsigned long long>(cb * 4);
+    r.fgp = w.take<double>(cb * HW);
+    return w.off;
 }
 
-size_t losses_ws_bytes(int cap_b, int H, int W) {
-    const long HW = (long)H * W;
-    const size_t nblk = (size_t)ls_blocks(HW);
-    return ls_align((size_t)cap_b * LS_MAXID * 24) + ls_align((size_t)cap_b * LS_MAXID * sizeof(LtCentre)) + ls_align((size_t)cap_b * nblk * LS_NACC * 8) +
-           ls_align((size_t)cap_b * nblk * 8) + ls_align((size_t)cap_b * LS_BINS * 4) + ls_align((size_t)cap_b * 32) + ls_align((size_t)cap_b * HW * 8);
-}
+size_t losses_ws_bytes(int cap_b, int H, int W) { return ls_layout(nullptr, nullptr, cap_b, H, W); }
 
 // ws: losses_ws_bytes(cap_b >= B, H, W) bytes.  1 <= sigma <= 20 (the table and the peaks fit the 64 KB of LDS a launch gets without asking), n <= 254
 int launch_loss_targets(const int* labels, int B, int n, int H, int W, int sigma, int small_area, float small_weight, int legacy_f32,
                         const float* gauss, float* targets, double* points, int* area, void* ws, int cap_b, hipStream_t st) {
     if (B <= 0) return 0;
-    const LsWs w = ls_carve(ws, cap_b, H, W);
+    LsWs w;
+    ls_layout(&w, ws, cap_b, H, W);
     const long HW = (long)H * W;
     ProfScope prof("loss_targets", 28.0 * B * HW, 0.0, st);                       // the label map in, six f32 planes out
     if (n > 0) {
@@ -414,7 +409,8 @@ int launch_loss_targets(const int* labels, int B, int n, int H, int W, int sigma
 int launch_losses(const float* logits, int P, const float* targets, const uint8_t* expl, const ::quber_loss_spec& sp, int ncls, long k, int B, int H,
                   int W, double* out, void* ws, int cap_b, hipStream_t st) {
     if (B <= 0) return 0;
-    const LsWs w = ls_carve(ws, cap_b, H, W);
+    LsWs w;
+    ls_layout(&w, ws, cap_b, H, W);
     const long HW = (long)H * W;
     const int nblk = ls_blocks(HW);
     const bool select = sp.top_k != 1.0;

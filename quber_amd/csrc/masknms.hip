@@ -220,27 +220,22 @@ __global__ __launch_bounds__(256) void mn_write_kernel(const int* __restrict__ r
 // workspace layout, for frames of `cap_b` x `cap_n` masks: planes | inter, vis (zeroed together) | rankmap | rank_mask, out_of_rank, kept
 struct MnWs { unsigned* planes; unsigned* inter; unsigned* vis; int* rankmap; int* rank_mask; int* out_of_rank; int* kept; size_t zero_bytes; };
 
-static size_t mn_align(size_t v) { return (v + 255) / 256 * 256; }
-
-static MnWs mn_carve(void* ws, int B, int N, int H, int W) {
-    MnWs r;
-    char* p = static_cast<char*>(ws);
-    r.planes = reinterpret_cast<unsigned*>(p);      p += mn_align((size_t)B * N * mn_plane_words(H, W) * 4);
-    r.inter = reinterpret_cast<unsigned*>(p);
-    r.vis = r.inter + (size_t)B * N * N;
-    r.zero_bytes = ((size_t)B * N * N + (size_t)B * N) * 4;
-    p += mn_align(r.zero_bytes);
-    r.rankmap = reinterpret_cast<int*>(p);          p += mn_align((size_t)B * H * W * 4);
-    r.rank_mask = reinterpret_cast<int*>(p);        p += mn_align((size_t)B * N * 4);
-    r.out_of_rank = reinterpret_cast<int*>(p);      p += mn_align((size_t)B * N * 4);
-    r.kept = reinterpret_cast<int*>(p);
-    return r;
+static size_t mn_layout(MnWs* out, void* ws, int B, int N, int H, int W) {
+    const size_t bn = (size_t)B * N;
+    MnWs none, &r = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    r.planes = w.take<unsigned>(bn * mn_plane_words(H, W));
+    r.inter = w.take<unsigned>(bn * N + bn);
+    r.vis = r.inter ? r.inter + bn * N : nullptr;
+    r.zero_bytes = (bn * N + bn) * 4;
+    r.rankmap = w.take<int>((size_t)B * H * W);
+    r.rank_mask = w.take<int>(bn);
+    r.out_of_rank = w.take<int>(bn);
+    r.kept = w.take<int>((size_t)B);
+    return w.off;
 }
 
-size_t mask_nms_ws_bytes(int B, int N, int H, int W) {
-    return mn_align((size_t)B * N * mn_plane_words(H, W) * 4) + mn_align(((size_t)B * N * N + (size_t)B * N) * 4) + mn_align((size_t)B * H * W * 4) +
-           2 * mn_align((size_t)B * N * 4) + mn_align((size_t)B * 4);
-}
+size_t mask_nms_ws_bytes(int B, int N, int H, int W) { return mn_layout(nullptr, nullptr, B, N, H, W); }
 
 int mask_nms_max() { return MN_MAX; }
 
@@ -261,7 +256,8 @@ int launch_mask_nms(const uint8_t* masks, const float* scores, int B, int N, int
     if (((uintptr_t)ids & 3) || ((uintptr_t)source & 3) || ((uintptr_t)out_scores & 3) || ((uintptr_t)report & 3) || ((uintptr_t)scores & 3))
         return fail("mask nms: a 32-bit tensor that is not 4-byte aligned");
     const int wpr = (W + 31) / 32, pw = (int)mn_plane_words(H, W);
-    const MnWs w = mn_carve(ws, B, N, H, W);
+    MnWs w;
+    mn_layout(&w, ws, B, N, H, W);
     const double px = (double)B * N * HW;
     {
         ProfScope prof("mask_nms_pack", px + 4.0 * B * N * pw, 0.0, st);

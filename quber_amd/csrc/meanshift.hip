@@ -343,28 +343,23 @@ __global__ __launch_bounds__(256) void ms_write_kernel(const int* __restrict__ r
 // workspace, for `cap_b` frames of n pixels: slots, hist, pos (cleared by the entries that use them) | mind | raw | table | part
 struct MsWs { unsigned long long* slots; unsigned* hist; unsigned* pos; float* mind; int* raw; int* table; float* part; };
 
-static size_t ms_align(size_t v) { return (v + 255) / 256 * 256; }
-
-static MsWs ms_carve(void* ws, int cap_b, long n) {
-    MsWs r;
-    char* p = static_cast<char*>(ws);
-    r.slots = reinterpret_cast<unsigned long long*>(p);  p += ms_align((size_t)cap_b * MS_SMAX * 8);
-    r.hist = reinterpret_cast<unsigned*>(p);
-    r.pos = r.hist + (size_t)cap_b * MS_SMAX;            p += ms_align((size_t)cap_b * MS_SMAX * 8);
-    r.mind = reinterpret_cast<float*>(p);                p += ms_align((size_t)cap_b * n * 4);
-    r.raw = reinterpret_cast<int*>(p);                   p += ms_align((size_t)cap_b * n * 4);
-    r.table = reinterpret_cast<int*>(p);                 p += ms_align((size_t)cap_b * (MS_SMAX + 1) * 4);
-    r.part = reinterpret_cast<float*>(p);
-    return r;
-}
-
 static int ms_blocks(long n) { return (int)std::min<long>((n + MS_TP - 1) / MS_TP, MS_G); }
 
-size_t meanshift_ws_bytes(int cap_b, int H, int W) {
-    const long n = (long)H * W;
-    return 2 * ms_align((size_t)cap_b * MS_SMAX * 8) + 2 * ms_align((size_t)cap_b * n * 4) + ms_align((size_t)cap_b * (MS_SMAX + 1) * 4) +
-           ms_align((size_t)cap_b * ms_blocks(n) * MS_SMAX * MS_C * 4);
+static size_t ms_layout(MsWs* out, void* ws, int cap_b, long n) {
+    const size_t cb = (size_t)cap_b;
+    MsWs none, &r = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    r.slots = w.take<unsigned long long>(cb * MS_SMAX);
+    r.hist = w.take<unsigned>(cb * MS_SMAX * 2);
+    r.pos = r.hist ? r.hist + cb * MS_SMAX : nullptr;
+    r.mind = w.take<float>(cb * n);
+    r.raw = w.take<int>(cb * n);
+    r.table = w.take<int>(cb * (MS_SMAX + 1));
+    r.part = w.take<float>(cb * ms_blocks(n) * MS_SMAX * MS_C);
+    return w.off;
 }
+
+size_t meanshift_ws_bytes(int cap_b, int H, int W) { return ms_layout(nullptr, nullptr, cap_b, (long)H * W); }
 
 static int ms_check(const char* what, int B, int S, int H, int W, std::initializer_list<const void*> ptrs, const void* ws) {
     if (B <= 0) return fail(std::string(what) + ": empty batch");
@@ -384,7 +379,8 @@ static int ms_check(const char* what, int B, int S, int H, int W, std::initializ
 int launch_meanshift_seeds(const float* X, const int* first, int B, int S, int H, int W, int* idx, void* ws, int cap_b, hipStream_t st) {
     if (ms_check("meanshift seeds", B, S, H, W, {X, first, idx}, ws)) return -1;
     const int n = H * W;
-    const MsWs w = ms_carve(ws, cap_b, n);
+    MsWs w;
+    ms_layout(&w, ws, cap_b, n);
     if (launch_zero(w.slots, (size_t)B * S * 8, st)) return -1;
     ProfScope prof("meanshift_seeds", (double)S * B * n * (MS_C + 2) * 4.0, 2.0 * S * B * n * MS_C, st);
     for (int k = 0; k < S; ++k)
@@ -401,7 +397,8 @@ int launch_meanshift_climb(const float* X, const int* idx, float* Z, int B, int 
     if (iters < 0 || iters > 1000) return fail("meanshift climb: iters outside 0..1000");
     if (!(kappa >= 0.f) || kappa > MS_KAPPA_MAX) return fail("meanshift climb: kappa outside 0..64");
     const int n = H * W;
-    const MsWs w = ms_carve(ws, cap_b, n);
+    MsWs w;
+    ms_layout(&w, ws, cap_b, n);
     if (idx) {
         hipLaunchKernelGGL(ms_gather_kernel, dim3(S, B), dim3(64), 0, st, X, idx, Z, n, S);
         QB_CHECK(hipGetLastError());
@@ -438,7 +435,8 @@ int launch_meanshift_assign(const float* X, const float* Z, const int* seed_labe
     if (depth_z && ((uintptr_t)depth_z & 3)) return fail("meanshift assign: a 32-bit tensor that is not 4-byte aligned");
     if (depth_z && !(thresh >= 0.f && thresh <= 1.f)) return fail("meanshift assign: depth threshold outside 0..1");
     const long n = (long)H * W;
-    const MsWs w = ms_carve(ws, cap_b, n);
+    MsWs w;
+    ms_layout(&w, ws, cap_b, n);
     if (launch_zero(w.hist, (size_t)cap_b * MS_SMAX * 8, st)) return -1;
     {
         ProfScope prof("meanshift_assign", (double)B * n * (MS_C + 2) * 4.0, 2.0 * B * (double)n * S * MS_C, st);

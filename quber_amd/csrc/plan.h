@@ -38,6 +38,20 @@ struct Profiler {
 };
 extern thread_local Profiler* g_prof;     // the profiler of the open quber_profile_begin / _end window of this thread, or null
 
+// a device buffer of the context that its entry allocates on first use and keeps (ws_reserve, api.hip)
+struct LazyWs { void* p = nullptr; size_t bytes = 0; };
+enum LazyId {
+    WS_PERTURB,     // bit planes of quber_perturb_masks in its device-memory placement: grown on demand
+    WS_MASKNMS,     // bit planes, pair table, rank map and per-frame tables of quber_mask_nms: for max_batch frames
+    WS_COCOAP,      // bit planes, pair table, areas and boxes of quber_coco_match: grown on demand
+    WS_SCENE,       // bit planes, pair and touch tables, member sets, prefix sums of quber_scene_perturb: grown on demand
+    WS_MEANSHIFT,   // seed slots, histograms, running minimum, raw labels, block partials of the mean-shift entries (meanshift.hip): for max_batch frames
+    WS_GMS,         // counts, compacted points, running minimum, raw labels, tables, block partials of the Gaussian mean-shift entries (gms.hip): for max_batch frames
+    WS_ZOOM,        // extents, keep flags, depth keys, paint order, key map of the zoom-in entries (zoom.hip): for max_batch frames
+    WS_LOSSES,      // moments, centres, block partials, histograms, foreground plane of the loss entries (losses.hip): for max_batch frames
+    WS_COUNT
+};
+
 constexpr int GN_SLOTS = 64;
 inline size_t gn_slot_doubles(int max_batch) { return (size_t)2 * 32 * max_batch * 4; }
 
@@ -75,18 +89,7 @@ struct quber_ctx {
     uint8_t* err_ws = nullptr;
     void* post_ws = nullptr;
     void* cleanup_ws = nullptr;   // parent map, per-root tables, per-instance keys of the connected-component clean-up (cleanup.hip)
-    void* perturb_ws = nullptr;   // bit planes of quber_perturb_masks in its device-memory placement: allocated on first use, grown on demand
-    size_t perturb_ws_bytes = 0;
-    void* masknms_ws = nullptr;   // bit planes, pair table, rank map and per-frame tables of quber_mask_nms: allocated by its first call
-    size_t masknms_ws_bytes = 0;
-    void* cocoap_ws = nullptr;    // bit planes, pair table, areas and boxes of quber_coco_match: allocated on first use, grown on demand
-    size_t cocoap_ws_bytes = 0;
-    void* scene_ws = nullptr;     // bit planes, pair and touch tables, member sets, prefix sums of quber_scene_perturb: allocated on first use, grown on demand
-    size_t scene_ws_bytes = 0;
-    void* meanshift_ws = nullptr; // seed slots, histograms, running minimum, raw labels, block partials of the mean-shift entries (meanshift.hip): allocated by their first call
-    void* gms_ws = nullptr;       // counts, compacted points, running minimum, raw labels, tables, block partials of the Gaussian mean-shift entries (gms.hip): allocated by their first call
-    void* zoom_ws = nullptr;      // extents, keep flags, depth keys, paint order, key map of the zoom-in entries (zoom.hip): allocated by their first call
-    void* losses_ws = nullptr;    // moments, centres, block partials, histograms, foreground plane of the loss entries (losses.hip): allocated by their first call
+    quber::LazyWs lazy[quber::WS_COUNT];   // the workspaces that are not part of quber_create (ws_reserve, api.hip); quber_destroy frees every one
     double* gn_stats = nullptr;   // [GN_SLOTS][launch group <= 4][max_batch][32 groups][sum, sum of squares]
     int gn_slots = 0;
     float* splitk_ws = nullptr;

@@ -492,11 +492,20 @@ __global__ void extract_masks_generic_kernel(const float* __restrict__ pan, cons
 }
 
 // workspace layout (bytes): cand f32 B*HW | idmap u8 B*HW | area u32 B*256 | lut f32 B*256 | stats B*cap
-static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-size_t postprocess_ws_bytes(int B, int H, int W, int cap) {
-    const size_t HW = (size_t)H * W;
-    return al(B * HW * 4) + al(B * HW) + al((size_t)B * 256 * 4) * 2 + al((size_t)B * cap * sizeof(InstStat)) + al((size_t)B * sizeof(CandList));
+struct PpWs { float* cand; uint8_t* idmap; unsigned* area; float* lut; InstStat* stats; CandList* lists; };
+static size_t pp_layout(PpWs* out, void* ws, int B, int H, int W, int cap) {
+    const size_t b = (size_t)B, HW = (size_t)H * W;
+    PpWs none, &r = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    r.cand = w.take<float>(b * HW);
+    r.idmap = w.take<uint8_t>(b * HW);
+    r.area = w.take<unsigned>(b * 256);
+    r.lut = w.take<float>(b * 256);
+    r.stats = w.take<InstStat>(b * cap);
+    r.lists = w.take<CandList>(b);
+    return w.off;
 }
+size_t postprocess_ws_bytes(int B, int H, int W, int cap) { return pp_layout(nullptr, nullptr, B, H, W, cap); }
 
 int launch_postprocess(const float* logits, int nch, int B, int H, int W, const PostCfg& c, void* ws, float* pan,
                        int* count, float* labels, float* scores, float* boxes, int* centers, int* ncenters,
@@ -506,46 +515,41 @@ int launch_postprocess(const float* logits, int nch, int B, int H, int W, const 
     if ((c.nms_kernel & 1) == 0 || c.nms_kernel > 15) return fail("postprocess: NMS kernel must be odd and <= 15");
     if ((long)H * W < c.top_k) return fail("postprocess: frame smaller than top_k");
     const size_t HW = (size_t)H * W;
-    char* w = reinterpret_cast<char*>(ws);
-    float* cand = reinterpret_cast<float*>(w); w += al(B * HW * 4);
-    uint8_t* idmap = reinterpret_cast<uint8_t*>(w); w += al(B * HW);
-    unsigned* area = reinterpret_cast<unsigned*>(w); w += al((size_t)B * 256 * 4);
-    float* lut = reinterpret_cast<float*>(w); w += al((size_t)B * 256 * 4);
-    InstStat* stats = reinterpret_cast<InstStat*>(w); w += al((size_t)B * c.cap * sizeof(InstStat));
-    CandList* lists = reinterpret_cast<CandList*>(w);
+    PpWs w;
+    pp_layout(&w, ws, B, H, W, c.cap);
 
     const int r = (c.nms_kernel - 1) / 2;
     const int P = NT + 2 * r;
     const double px = (double)B * HW;
-    if (int rc = launch_zero(lists, (size_t)B * sizeof(CandList), st)) return rc;      // (the counts; the slots behind them ride along)
+    if (int rc = launch_zero(w.lists, (size_t)B * sizeof(CandList), st)) return rc;      // (the counts; the slots behind them ride along)
     {   // a8: centre plane in, candidate map out
         ProfScope prof("post_nms", 8.0 * px, 0.0, st);
         hipLaunchKernelGGL(nms_kernel, dim3((W + NT - 1) / NT, (H + NT - 1) / NT, B), dim3(256), sizeof(float) * (P * P + P * NT), st,
-                           logits, nch, H, W, c.threshold, r, cand, lists);
+                           logits, nch, H, W, c.threshold, r, w.cand, w.lists);
     }
     {   // a8: k-th largest candidate + ordered compaction (one block per frame; reads the candidate map)
         ProfScope prof("post_select", 4.0 * px, 0.0, st);
-        hipLaunchKernelGGL(select_kernel, dim3(B), dim3(1024), 0, st, cand, (int)HW, W, c.top_k, c.cap, centers, ncenters, lists);
+        hipLaunchKernelGGL(select_kernel, dim3(B), dim3(1024), 0, st, w.cand, (int)HW, W, c.top_k, c.cap, centers, ncenters, w.lists);
     }
-    if (int rc = launch_zero(area, (size_t)B * 256 * 4, st)) return rc;
+    if (int rc = launch_zero(w.area, (size_t)B * 256 * 4, st)) return rc;
     {   // a9: fg + 2 offset planes in, id map out
         ProfScope prof("post_group", 13.0 * px, 0.0, st);
         hipLaunchKernelGGL(group_kernel, dim3((int)((HW + GP_PIX - 1) / GP_PIX), B), dim3(256), 0, st, logits, nch, H, W, c.cap, centers, ncenters,
-                           idmap, area);
+                           w.idmap, w.area);
     }
     {
         ProfScope prof("post_relabel", 2048.0 * B, 0.0, st);
-        hipLaunchKernelGGL(relabel_kernel, dim3(B), dim3(256), 0, st, area, ncenters, c.min_area, c.stuff_area,
-                           c.label_divisor, c.cap, lut, count, labels, stats);
+        hipLaunchKernelGGL(relabel_kernel, dim3(B), dim3(256), 0, st, w.area, ncenters, c.min_area, c.stuff_area,
+                           c.label_divisor, c.cap, w.lut, count, labels, w.stats);
     }
     {   // a10 / a11: id map + fg plane in, label map out, per-instance sums
         ProfScope prof("post_paint_stats", 9.0 * px, 0.0, st);
         hipLaunchKernelGGL(paint_stats_kernel<uint8_t>, dim3((int)((HW + PS_PIX - 1) / PS_PIX), B), dim3(256), 0, st, logits, nch, H, W, c.cap,
-                           c.label_divisor, idmap, lut, pan, stats);
+                           c.label_divisor, w.idmap, w.lut, pan, w.stats);
     }
     {
         ProfScope prof("post_finalize", 64.0 * B * c.cap, 0.0, st);
-        hipLaunchKernelGGL(finalize_kernel, dim3(B), dim3(256), 0, st, logits, nch, H, W, c.cap, count, stats, scores,
+        hipLaunchKernelGGL(finalize_kernel, dim3(B), dim3(256), 0, st, logits, nch, H, W, c.cap, count, w.stats, scores,
                            boxes);
     }
     QB_CHECK(hipGetLastError());

@@ -53,29 +53,28 @@ struct ScWs {
     int* fin;             // [B][M][SC_FIN]
 };
 
-static size_t sc_align(size_t v) { return (v + 255) / 256 * 256; }
-
-static size_t sc_carve(ScWs* r, void* ws, int B, int S, int M, int H, int W) {
+static size_t sc_layout(ScWs* out, void* ws, int B, int S, int M, int H, int W) {
     const size_t pw = (size_t)mn_plane_words(H, W), b = (size_t)B, s = (size_t)(S > 0 ? S : 1), m = (size_t)M;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = static_cast<char*>(ws) + o; o += sc_align(bytes); return p; };
-    char* p;
-    p = take(b * s * pw * 4);            if (r) r->src = reinterpret_cast<unsigned*>(p);
-    p = take(b * s * s * 4);             if (r) r->inter = reinterpret_cast<unsigned*>(p);
-    p = take(b * m * m);                 if (r) { r->touch = reinterpret_cast<uint8_t*>(p); r->zero_bytes = sc_align(b * s * s * 4) + sc_align(b * m * m); }
-    p = take(b * m * pw * 4);            if (r) r->dil = reinterpret_cast<unsigned*>(p);
-    p = take(b * m * pw * 4);            if (r) r->comp = reinterpret_cast<unsigned*>(p);
-    p = take(b * m * 8 * 4);             if (r) r->memb = reinterpret_cast<unsigned*>(p);
-    p = take(b * m * 4);                 if (r) r->area = reinterpret_cast<unsigned*>(p);
-    p = take(b * m * 2 * 4);             if (r) r->ent = reinterpret_cast<int*>(p);
-    p = take(b * SC_CNT * 4);            if (r) r->cnt = reinterpret_cast<int*>(p);
-    p = take(b * m * (size_t)(H + 1) * 4); if (r) r->rowpre = reinterpret_cast<int*>(p);
-    p = take(b * m * (size_t)(W + 1) * 4); if (r) r->colpre = reinterpret_cast<int*>(p);
-    p = take(b * m * SC_FIN * 4);        if (r) r->fin = reinterpret_cast<int*>(p);
-    return o;
+    ScWs none, &r = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    r.src = w.take<unsigned>(b * s * pw);
+    const size_t inter_bytes = ws_align(b * s * s * 4);             // touch starts on a boundary of its own
+    r.zero_bytes = inter_bytes + ws_align(b * m * m);
+    r.inter = reinterpret_cast<unsigned*>(w.take<uint8_t>(r.zero_bytes));
+    r.touch = r.inter ? reinterpret_cast<uint8_t*>(r.inter) + inter_bytes : nullptr;
+    r.dil = w.take<unsigned>(b * m * pw);
+    r.comp = w.take<unsigned>(b * m * pw);
+    r.memb = w.take<unsigned>(b * m * 8);
+    r.area = w.take<unsigned>(b * m);
+    r.ent = w.take<int>(b * m * 2);
+    r.cnt = w.take<int>(b * SC_CNT);
+    r.rowpre = w.take<int>(b * m * (size_t)(H + 1));
+    r.colpre = w.take<int>(b * m * (size_t)(W + 1));
+    r.fin = w.take<int>(b * m * SC_FIN);
+    return w.off;
 }
 
-size_t scene_ws_bytes(int B, int S, int M, int H, int W) { return sc_carve(nullptr, nullptr, B, S, M, H, W); }
+size_t scene_ws_bytes(int B, int S, int M, int H, int W) { return sc_layout(nullptr, nullptr, B, S, M, H, W); }
 int scene_max() { return SC_MAX; }
 
 __device__ __forceinline__ int sc_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
@@ -501,7 +500,7 @@ int launch_scene_perturb(const ScenePerturbArgs& q, int B, int H, int W, void* w
     const long HW = (long)H * W;
     const double lim = (double)HW * q.min_mask_ratio;
     ScWs w;
-    sc_carve(&w, ws_mem, B, S, M, H, W);
+    sc_layout(&w, ws_mem, B, S, M, H, W);
     const int Sk = S > 0 ? S : 1;                            // (S = 0: no source exists, L1 = 0 and no kernel below reads one)
     const int chunks = (pw + SC_CHUNK - 1) / SC_CHUNK;
     if (S > 0 && launch_zero(w.inter, w.zero_bytes, st)) return -1;

@@ -384,29 +384,23 @@ __global__ __launch_bounds__(ZM_T) void zm_write_kernel(const int* __restrict__ 
 // ncrop | keymap
 struct ZmWs { unsigned long long* ksum; unsigned* ext; unsigned* kcnt; unsigned* vis; uint8_t* keep; int* outof; int* order; int* ncrop; int* keymap; };
 
-static size_t zm_align(size_t v) { return (v + 255) / 256 * 256; }
-
-static ZmWs zm_carve(void* ws, int cap_b, int H, int W) {
+static size_t zm_layout(ZmWs* out, void* ws, int cap_b, int H, int W) {
     const size_t tc = (size_t)cap_b * ZM_MAXID, keys = tc * (ZM_MAXID + 1);
-    ZmWs r;
-    char* p = static_cast<char*>(ws);
-    r.ksum = reinterpret_cast<unsigned long long*>(p);  p += tc * 8;
-    r.ext = reinterpret_cast<unsigned*>(p);             p += tc * 16;
-    r.kcnt = reinterpret_cast<unsigned*>(p);            p += tc * 4;
-    r.vis = reinterpret_cast<unsigned*>(p);             p += zm_align(keys * 4);
-    r.keep = reinterpret_cast<uint8_t*>(p);             p += zm_align(keys);
-    r.outof = reinterpret_cast<int*>(p);                p += zm_align(keys * 4);
-    r.order = reinterpret_cast<int*>(p);                p += zm_align(tc * 4);
-    r.ncrop = reinterpret_cast<int*>(p);                p += zm_align((size_t)cap_b * 4);
-    r.keymap = reinterpret_cast<int*>(p);
-    return r;
+    ZmWs none, &r = out ? *out : none;
+    WsWalk w{static_cast<char*>(ws)};
+    r.ksum = w.take<unsigned long long>(tc, false);         // ksum .. vis: one range, cleared by one launch
+    r.ext = w.take<unsigned>(tc * 4, false);
+    r.kcnt = w.take<unsigned>(tc, false);
+    r.vis = w.take<unsigned>(keys);
+    r.keep = w.take<uint8_t>(keys);
+    r.outof = w.take<int>(keys);
+    r.order = w.take<int>(tc);
+    r.ncrop = w.take<int>((size_t)cap_b);
+    r.keymap = w.take<int>((size_t)cap_b * H * W);
+    return w.off;
 }
 
-size_t zoom_ws_bytes(int cap_b, int H, int W) {
-    const size_t tc = (size_t)cap_b * ZM_MAXID, keys = tc * (ZM_MAXID + 1);
-    return tc * 28 + zm_align(keys * 4) + zm_align(keys) + zm_align(keys * 4) + zm_align(tc * 4) + zm_align((size_t)cap_b * 4) +
-           zm_align((size_t)cap_b * H * W * 4);
-}
+size_t zoom_ws_bytes(int cap_b, int H, int W) { return zm_layout(nullptr, nullptr, cap_b, H, W); }
 
 static int zm_extents(const int* ids, int B, int n, int H, int W, unsigned* ext, hipStream_t st) {
     const long HW = (long)H * W;
@@ -418,7 +412,8 @@ static int zm_extents(const int* ids, int B, int n, int H, int W, unsigned* ext,
 // ws: zoom_ws_bytes(>= B, H, W) bytes
 int launch_zoom_rois(const int* ids, int B, int n_ids, int H, int W, float padding, int* rois, void* ws, int cap_b, hipStream_t st) {
     if (B <= 0 || n_ids == 0) return 0;
-    const ZmWs w = zm_carve(ws, cap_b, H, W);
+    ZmWs w;
+    zm_layout(&w, ws, cap_b, H, W);
     ProfScope prof("zoom_rois", 4.0 * B * H * W + 32.0 * B * n_ids, 0.0, st);
     if (launch_zero(w.ext, (size_t)B * n_ids * 16, st)) return -1;
     if (zm_extents(ids, B, n_ids, H, W, w.ext, st)) return -1;
@@ -446,7 +441,8 @@ int launch_zoom_paste(const int* crop_ids, const float* crop_scores, const unsig
                       int* out_ids, uint8_t* out_masks, int* source, float* out_scores, float* boxes, int* report, void* ws, int cap_b,
                       hipStream_t st) {
     if (B <= 0) return 0;
-    const ZmWs w = zm_carve(ws, cap_b, H, W);
+    ZmWs w;
+    zm_layout(&w, ws, cap_b, H, W);
     const long HW = (long)H * W;
     const size_t tc = (size_t)cap_b * ZM_MAXID, keys = (size_t)T * (C + 1);
     const int SS = S * S;

@@ -5,12 +5,13 @@ import numpy as np
 import pytest
 import torch
 
-from quber_amd import engine
+from quber_amd import _lib, engine
+from quber_amd.eval import coco_ap
 from quber_amd.maskrefiner.predictor import MaskRefinerPredictor
 from quber_amd.perturb import Perturb
-from quber_amd.scene import ScenePerturb
+from quber_amd.scene import ScenePerturb, scene_draws
 from test_perturb_cpu import perturb_batch_np
-from test_scene_cpu import GPU_COUNTS, GPU_FRAMES, MIN_RATIO, gpu_batch, hand_cases, random_scene, scene_perturb_np
+from test_scene_cpu import ACT, GPU_COUNTS, GPU_FRAMES, MIN_RATIO, gpu_batch, hand_cases, random_scene, scene_perturb_np
 
 pytestmark = pytest.mark.gpu
 
@@ -196,6 +197,94 @@ def test_bad_arguments_are_refused_and_launch_nothing():
     torch.cuda.synchronize()
     assert b1 > before and eng.lib.quber_workspace_bytes(eng.h) == b1
     _same(tuple(v[k].cpu().numpy() for k in ("out", "info", "report")), s["want"])
+
+
+# ---- the workspaces that grow on demand ----
+GROW_FRAME = (33, 65)                   # rows that are not whole words, planes padded to 4 words, a pixel count that is no multiple of 16
+
+
+def _scene_call(B, N, P, M, seed):
+    """-> the arguments of _run behind the engine: B frames of N ground truths and P proposals at GROW_FRAME, tables at capacity M."""
+    h, w = GROW_FRAME
+    gt, props, per = np.zeros((B, N, h, w), np.uint8), np.zeros((B, P, h, w), np.uint8), []
+    for b in range(B):
+        sc = random_scene(seed + b, GROW_FRAME, N, P)
+        gt[b], props[b] = sc["gt"], sc["props"]
+        per.append(scene_draws(np.random.RandomState(seed + b + 7), P, M, h, w, *ACT))
+    draws = {k: np.ascontiguousarray(np.stack([d[k] for d in per])) for k in TABLES}
+    return gt, props, np.full(B, N, np.int32), np.full(B, P, np.int32), draws, M, MIN_RATIO
+
+
+def _coco_call(B, n_dt, n_gt, seed):
+    """-> dt u8 [B,n_dt,h,w], scores f32 [B,n_dt], gt u8 [B,n_gt,h,w]: rectangles, the first detections shifted ground truths."""
+    h, w = GROW_FRAME
+    rng = np.random.RandomState(seed)
+
+    def rects(n):
+        m = np.zeros((B, n, h, w), np.uint8)
+        for plane in m.reshape(-1, h, w):
+            y, x = rng.randint(0, h - 8), rng.randint(0, w - 8)
+            plane[y:y + rng.randint(4, h - y), x:x + rng.randint(4, w - x)] = 1
+        return m
+
+    gt, dt = rects(n_gt), rects(n_dt)
+    k = min(n_dt, n_gt)
+    dt[:, :k] = np.roll(gt[:, :k], 2, 3)
+    return dt, rng.random_sample((B, n_dt)).astype(np.float32), gt
+
+
+def _coco_run(eng, dt, scores, gt):
+    """quber_coco_match (segm, every ground truth present, computed areas) -> its ten outputs on the host."""
+    B, n_dt, n_gt = dt.shape[0], dt.shape[1], gt.shape[1]
+    T, A, TOP = len(coco_ap.IOU_THRS), len(coco_ap.AREA_RNG), coco_ap.TOP
+    outs = [torch.full(shape, FILL, dtype=dtype, device="cuda") for dtype, shape in (
+        (torch.int32, (B, 2)), (torch.int32, (B, TOP)), (torch.float32, (B, TOP)), (torch.float64, (B, TOP)), (torch.float64, (B, n_gt)),
+        (torch.float64, (B, TOP, n_gt)), (torch.uint8, (B, A, T, TOP)), (torch.uint8, (B, A, T, TOP)), (torch.uint8, (B, A, n_gt)),
+        (torch.int32, (B, A, n_gt)))]
+    ins = [dev(dt), dev(scores), dev(gt), torch.zeros((B, n_gt), dtype=torch.uint8, device="cuda"), dev(coco_ap.IOU_THRS), dev(coco_ap.AREA_RNG)]
+    P = engine._ptr
+    _lib.check(eng.lib.quber_coco_match(eng.h, P(ins[0]), P(ins[1]), None, n_dt, P(ins[2]), P(ins[3]), None, None, n_gt, B, 0, P(ins[4]), T, P(ins[5]), A,
+                                        *[P(o) for o in outs], engine._stream()))
+    torch.cuda.synchronize()
+    return tuple(o.cpu().numpy() for o in outs)
+
+
+def _bitwise(got, want, what):
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (what, i)
+
+
+def test_growing_workspaces_of_scene_perturb_and_coco_match():
+    """The two entries whose workspace grows with the call (the third, quber_perturb_masks, has its own test in test_gpu_perturb.py), on
+    an engine of max_batch 2: a small call, a larger one, the small one again.  The third result equals the first bit for bit - the
+    small layout inside the larger buffer; quber_workspace_bytes rises by the layout total of the first call, then to the total of the
+    larger one, and stays; an engine that has only ever seen the larger call computes the same."""
+    h, w = GROW_FRAME
+    make = lambda: engine.Engine(engine.make_config(h, w, max_batch=2, max_instances=64, with_network=False), "cuda:0")
+    ws = lambda e, which, b, n, m: int(e.lib.quber_debug_ws_bytes(which, b, n, m, h, w, 0))
+    small_s, large_s = _scene_call(1, 2, 1, 4, 500), _scene_call(2, 5, 4, 16, 600)
+    small_c, large_c = _coco_call(1, 3, 2, 700), _coco_call(2, 9, 17, 800)
+    eng, fresh = make(), make()
+    try:
+        for what, run, small, large, need_small, need_large in (
+                ("scene", lambda e, a: _run(e, *a), small_s, large_s, ws(eng, 2, 1, 3, 4), ws(eng, 2, 2, 9, 16)),
+                ("coco", lambda e, a: _coco_run(e, *a), small_c, large_c, ws(eng, 1, 1, 2, 0), ws(eng, 1, 2, 17, 0))):
+            assert 0 < need_small < need_large, what
+            b0 = eng.workspace_bytes()
+            first = run(eng, small)
+            assert eng.workspace_bytes() == b0 + need_small, what
+            second = run(eng, large)
+            assert eng.workspace_bytes() == b0 + need_large, what       # the small buffer was freed, not kept beside the new one
+            third = run(eng, small)
+            assert eng.workspace_bytes() == b0 + need_large, what       # never shrinks, allocates nothing
+            _bitwise(third, first, what + ": the small call after the larger one")
+            f0 = fresh.workspace_bytes()
+            _bitwise(run(fresh, large), second, what + ": a fresh engine on the larger call")
+            assert fresh.workspace_bytes() == f0 + need_large, what
+            assert any(a.any() for a in first[:1]) and any(a.any() for a in second[:1]), what      # the calls did something
+    finally:
+        eng.close()
+        fresh.close()
 
 
 # ---- end to end ----
