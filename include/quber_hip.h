@@ -42,7 +42,10 @@ typedef struct quber_config {
                                         1: the refiner network; 4: the Depth Seeding Network of UOIS-Net-3D (uois/src/networks.py
                                            UNetESP_Encoder / UNetESP_Decoder, uois/src/segmentation.py:72-127; feature_dim is read off the first
                                            convolution's weight; H and W multiples of 16; runs through quber_dsn_forward, not quber_forward;
-                                           csrc/plan_dsn.hip, option key 53); 3: the CGNet foreground network of the UOAIS base model
+                                           csrc/plan_dsn.hip, option key 53); 5: the Region Refinement Network of UOIS-Net-3D
+                                           (uois/src/networks.py UNet_Encoder / UNet_Decoder, uois/src/segmentation.py:248-266; feature_dim
+                                           is read off the first convolution's weight; height = width = the crop side, a multiple of 16;
+                                           runs through quber_rrn_forward; csrc/plan_rrn.hip, option key 54); 3: the CGNet foreground network of the UOAIS base model
                                            (foreground_segmentation/cgnet.py, classes = 2, in_channel = 4; quber_forward then maps
                                            (bgr, depth) to [B][2][H][W] logits, H and W multiples of 8; csrc/plan_cgnet.hip, option key 52);
                                            2: the LMFFNet foreground network of the post-filter
@@ -839,6 +842,10 @@ double quber_forward_flops_padding(quber_ctx* ctx);
  *         esp_branches (csrc/dsn.hip): the five dilated 3x3 convolutions of t on v_mfma_f32_16x16x4_f32, the running sums d2, d2 + d4, ... kept in the
  *         accumulators, the residual, the store and per-tile GroupNorm sums; 0 = five convolution launches into temporaries + esp_merge.  The same
  *         convolutions; a running sum is continued in the accumulator instead of rounded and added (profiles/dsn_ab.md decides the default).
+ * key 54 (1; plan) Region Refinement Network contexts (with_network = 5): decoder.last_conv and fg_module, with nothing non-linear between them, as ONE
+ *         3x3 feature_dim -> 1 filter, w'[c][ky][kx] = sum_o wfg[o] W[o][c][ky][kx], b' = sum_o wfg[o] bias[o] (float64 on the host, rounded once), run by
+ *         rrn_head3 (csrc/rrn.hip) on decoder.layer5's output from LDS tiles with a halo; 0 = the convolution with its bias, then the 1x1 head kernel.
+ *         The collapsed form rounds the filter once more and the features once less (profiles/rrn_ab.md decides the default).
  * Process-only keys (quber_set_tuning): key 2 = give the stand-alone conv ops a split-K workspace (value != 0) or drop it (0);
  * key 11 = stand-alone conv op: dilated 3x3 layers in tap-major K order with the zero-padding filter rows skipped;
  * key 12 = stand-alone conv ops: quber_config.compute_dtype of the launch (1 = bf16 / 2 = fp16 operands, 3 = bf16x3);
@@ -1037,6 +1044,59 @@ int quber_op_esp_merge(const float* dev_d1, int32_t d1_cs, const float* dev_d2, 
 int quber_op_esp_stats(const double* dev_partials, int32_t batch, int32_t tiles, int32_t groups, double* dev_stats, void* stream);
 int quber_op_dsn_head(const float* dev_f, int32_t f_cs, int32_t batch, int32_t h, int32_t w, int32_t c, const float* dev_clean, const float* dev_wfg,
                       const float* dev_wcd, float* dev_logits, float* dev_offsets, float* dev_votes, uint8_t* dev_classes, uint8_t* dev_fg, void* stream);
+
+/* Region Refinement Network of UOIS-Net-3D on a with_network = 5 context: n crops of side S = height = width -> foreground logits, refined masks.
+ *   dev_rgb_crop f32 [n][3][S][S] planar, standardised (what quber_rrn_crop writes), dev_mask_crop u8 [n][S][S] (non-zero = the initial mask); the
+ *   network's input is their concatenation, the mask as 0.0 / 1.0 (segmentation.py:262-264).  n in 1..max_batch; GroupNorm is per sample, so a
+ *   caller may chunk its crops in any way (the reference's step_size is only that).
+ *   -> dev_logits f32 [n][S][S] (fg_module of the decoder's features), dev_refined u8 [n][S][S] = (logit > logit_threshold), 0 / 1.  Either may be
+ *      NULL, not both.  logit_threshold = float32(log(t / (1 - t))) of the probability threshold t, computed by the host; exactly 0 for t = 0.5.
+ *      Stated deviation: the reference compares float32 sigmoid(logit) > t, which differs for |logit| below about 1e-7 at t = 0.5.
+ *   Everything runs on `stream`; no host copy, no memset node, no allocation: the call can be captured into a graph.
+ *   quber_forward and quber_dsn_forward refuse such a context, and quber_rrn_forward every other. */
+int quber_rrn_forward(quber_ctx* ctx, const float* dev_rgb_crop, const uint8_t* dev_mask_crop, int32_t n, float logit_threshold, float* dev_logits,
+                      uint8_t* dev_refined, void* stream);
+/* the same forward with a HIP-event pair around every op of the plan (benchmark use; tools/rrn_ab.py): synchronises `stream`, then writes the milliseconds
+ * of op i (quber_op_info) to op_ms[i], quber_num_ops doubles on the host */
+int quber_rrn_forward_profiled(quber_ctx* ctx, const float* dev_rgb_crop, const uint8_t* dev_mask_crop, int32_t n, float logit_threshold, float* dev_logits,
+                               uint8_t* dev_refined, void* stream, double* op_ms);
+/* rrn_preprocess / rrn_postprocess of uois/src/segmentation.py:329-423 on the device, on any context of the FRAME size (one without a network will do; these
+ * two are their own test hooks).  slots i32 [n_slots][2] = (frame, id), ascending by frame, at most 254 per frame; rois i32 [batch][n_ids][4] = (x0, y0, x1, y1)
+ * inclusive as quber_zoom_rois writes them (the padded box of rrn_preprocess is the same expression).  A slot whose frame or id is out of range, or whose
+ * ROI is empty or leaves the frame, is no crop: zero crops, nothing painted.
+ *   quber_rrn_crop    dev_bytes u8 [batch][H][W][3] (the image as the caller holds it), dev_ids i32 [batch][H][W] (compact: 0 none, 1..n_ids), dev_table f32
+ *                     [3][256]: table[c][v] = float32((v / 255. - mean[c]) / std[c]) computed by the host in float64 - byte channel c takes mean[c]; the
+ *                     reference standardises the BGR bytes of cv2.imread with its RGB-ordered means (eval/base_model.py:460-462), and so does a caller
+ *                     that hands over BGR bytes.  -> dev_rgb_crop f32 [n_slots][3][S][S]: the standardised ROI resized bilinearly with align_corners
+ *                     (F.upsample_bilinear) in float32, per axis sc = float32(n - 1) / float32(S - 1), src = float32(dst) * sc, i0 = min(int(src), n - 1),
+ *                     i1 = min(i0 + 1, n - 1), l1 = src - i0, l0 = 1 - l1, out = l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d), every operation
+ *                     rounded on its own; dev_mask_crop u8 [n_slots][S][S] = (ids == id) at the nearest index min(int(floorf(float32(dst) *
+ *                     (float32(in) / float32(out)))), in - 1) (F.upsample_nearest), 0 / 1.  2 <= crop <= 512.  No allocation.
+ *   quber_rrn_paste   dev_refined u8 [n_slots][S][S] (non-zero = refined foreground), dev_z f32 [batch][H][W] (depth; NaN counts as 0) -> every crop
+ *                     resized back to its ROI by the nearest index; dev_keys f32 [n_slots] = float32(sum / count) of z under the resized mask, the sum
+ *                     in float64 from block partials added in a fixed order (0 for a slot without a refined pixel, which paints nothing, and for one whose z holds both infinities); a frame's slots
+ *                     painted in descending key, equal keys in ascending slot order (the stable sorted(reverse=True)); the surviving initial ids compacted in
+ *                     ascending order (np.unique) -> dev_out_ids i32 [batch][H][W], dev_out_masks u8 [batch][n_masks][H][W] of 0 / 255 (n_masks 1..254; a
+ *                     final id above n_masks has no plane), dev_source i32 [batch][n_masks] = the initial id of each refined mask, 0 beyond the count,
+ *                     dev_report i32 [batch][4] = (refined masks, initial masks that vanished, pixels painted, pixels painted over).  Every output is
+ *                     overwritten by every call; no memset node, no host copy, no floating-point atomics: two runs give the same bits.  Its workspace is
+ *                     allocated by the first call on a context (for max_batch frames) and kept: that call cannot be captured into a graph. */
+int quber_rrn_crop(quber_ctx* ctx, const uint8_t* dev_bytes, const int32_t* dev_ids, const int32_t* dev_slots, const int32_t* dev_rois, const float* dev_table,
+                   int32_t batch, int32_t n_ids, int32_t n_slots, int32_t crop, float* dev_rgb_crop, uint8_t* dev_mask_crop, void* stream);
+int quber_rrn_paste(quber_ctx* ctx, const uint8_t* dev_refined, const int32_t* dev_slots, const int32_t* dev_rois, const float* dev_z, int32_t batch,
+                    int32_t n_ids, int32_t n_slots, int32_t crop, int32_t n_masks, int32_t* dev_out_ids, uint8_t* dev_out_masks, int32_t* dev_source,
+                    float* dev_keys, int32_t* dev_report, void* stream);
+/* The network-side kernels of csrc/rrn.hip on explicit fp32 views - test hooks: the network reaches them only through quber_rrn_forward.  A refused view
+ * returns an error and launches nothing; no op allocates or synchronises.
+ *   quber_op_rrn_pack    planar crops f32 [batch][3][h][w] + mask u8 [batch][h][w] -> dev_x8 NHWC with 8 channels (c0, c1, c2, mask != 0, four zeros)
+ *   quber_op_rrn_head    features NHWC (c a multiple of 4 on a stride f_cs) -> logit = wfg [c] . f, a chain of c fused multiply-adds; dev_logits f32 /
+ *                        dev_refined u8 = (logit > thr), [batch][h][w], either may be NULL
+ *   quber_op_rrn_head3   the same outputs from a 3x3 filter dev_w9 [9][c] (tap-major) + bias with zero padding: 16 x 16 tiles staged in LDS with a halo */
+int quber_op_rrn_pack(const float* dev_rgb, const uint8_t* dev_mask, int32_t batch, int32_t h, int32_t w, float* dev_x8, void* stream);
+int quber_op_rrn_head(const float* dev_f, int32_t f_cs, int32_t batch, int32_t h, int32_t w, int32_t c, const float* dev_wfg, float thr, float* dev_logits,
+                      uint8_t* dev_refined, void* stream);
+int quber_op_rrn_head3(const float* dev_f, int32_t f_cs, int32_t batch, int32_t h, int32_t w, int32_t c, const float* dev_w9, float bias, float thr,
+                       float* dev_logits, uint8_t* dev_refined, void* stream);
 
 /* The kernels of the CGNet foreground network (csrc/cgnet.hip), each on explicit fp32 NHWC views - test hooks: the network reaches them only
  * through quber_forward of a with_network = 3 context.  A view is (pointer to its first channel, cs = elements between two pixels); c = 64

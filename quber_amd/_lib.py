@@ -155,6 +155,14 @@ SIGNATURES = {
     "quber_op_esp_merge": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "quber_op_esp_stats": (C.c_int, [_P, _I, _I, _I, _P, _P]),
     "quber_op_dsn_head": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # the Region Refinement Network (csrc/rrn.hip, csrc/plan_rrn.hip), its crop / paste and its kernels on explicit fp32 views (tests/test_gpu_rrn.py)
+    "quber_rrn_forward": (C.c_int, [_P, _P, _P, _I, C.c_float, _P, _P, _P]),
+    "quber_rrn_forward_profiled": (C.c_int, [_P, _P, _P, _I, C.c_float, _P, _P, _P, _P]),
+    "quber_rrn_crop": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "quber_rrn_paste": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "quber_op_rrn_pack": (C.c_int, [_P, _P, _I, _I, _I, _P, _P]),
+    "quber_op_rrn_head": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, C.c_float, _P, _P, _P]),
+    "quber_op_rrn_head3": (C.c_int, [_P, _I, _I, _I, _I, _I, _P, C.c_float, C.c_float, _P, _P, _P]),
     # the CGNet kernels on explicit fp32 views (tests/test_gpu_cgnet.py): pointer, cs per view
     "quber_op_cgnet_tiles": (C.c_int32, [_I, _I, _I]),
     "quber_op_cgnet_joint": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I] + [_P] * 10 + [_I, _P]),

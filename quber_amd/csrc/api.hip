@@ -24,6 +24,10 @@ int quber::check_cfg(const quber_config& c) {
         if (c.height < 16 || c.width < 16 || c.height % 16 || c.width % 16) return fail("the Depth Seeding Network needs height and width to be multiples of 16");
         return c.max_batch >= 1 ? 0 : fail("max_batch must be >= 1");
     }
+    if (c.with_network == 5) {
+        if (c.height != c.width || c.height < 16 || c.height % 16) return fail("the Region Refinement Network needs square crops whose side is a multiple of 16");
+        return c.max_batch >= 1 ? 0 : fail("max_batch must be >= 1");
+    }
     if (c.max_batch < 1) return fail("max_batch must be >= 1");
     if (c.max_instances < 1) return fail("max_instances must be >= 1");
     if (c.resnet_depth != 50 && c.resnet_depth != 101 && c.resnet_depth != 152) return fail("resnet_depth must be 50, 101 or 152");
@@ -129,6 +133,7 @@ int quber_create(const quber_config* cfg, quber_ctx** out) {
         if (cfg->with_network == 2) build_lmff(dry);
         else if (cfg->with_network == 3) build_cgnet(dry);
         else if (cfg->with_network == 4) build_dsn(dry);
+        else if (cfg->with_network == 5) build_rrn(dry);
         else dry.build();
     }
     *out = c;
@@ -172,12 +177,13 @@ int quber_finalize_weights(quber_ctx* c) {
     quber::TuneScope tscope(&c->tune);          // the plan is shaped by THIS context's options
     Builder b(c, false);
     c->flops = c->wino_flops = c->wino_saved = c->wino_pad = 0.0;
-    if (c->cfg.with_network >= 2 && c->cfg.with_network <= 4) {
+    if (c->cfg.with_network >= 2 && c->cfg.with_network <= 5) {
         c->splitk_floats = (size_t)4 << 20;
         c->splitk_ws = (float*)b.dalloc_bytes(sizeof(float) * c->splitk_floats);
         if (c->cfg.with_network == 2) build_lmff(b);
         else if (c->cfg.with_network == 3) build_cgnet(b);
-        else build_dsn(b);
+        else if (c->cfg.with_network == 4) build_dsn(b);
+        else build_rrn(b);
     } else {
         b.build();
     }
@@ -340,6 +346,7 @@ static int forward_begin(quber_ctx* c, const char* who, std::optional<quber::Tun
     if (!c->finalized) return fail(std::string(who) + " before quber_finalize_weights");
     scope.emplace(&c->tune);
     if (c->cfg.with_network == 4) return fail(std::string(who) + ": a Depth Seeding Network context runs through quber_dsn_forward");
+    if (c->cfg.with_network == 5) return fail(std::string(who) + ": a Region Refinement Network context runs through quber_rrn_forward");
     if (lmff_own && c->cfg.with_network >= 2) return 1;
     if (!bgr || (!depth && c->cfg.streams == 2) || !offs || !logits || !rest_ok) return fail(null_msg);
     c->cur_out = logits;
@@ -390,18 +397,8 @@ int quber_forward(quber_ctx* c, const uint8_t* bgr, const uint8_t* depth, const 
     return 0;
 }
 
-// quber_dsn_forward / quber_dsn_forward_profiled: the checks, the pointers the plan's first and last op read, every op in plan order; op_ms (profiled form): an
-// event pair around every op, read after one synchronisation
-static int dsn_run(quber_ctx* c, const char* who, const float* xyz, int batch, int flags, float* fg_logits, float* offsets, float* votes, uint8_t* fg_classes, uint8_t* fg,
-                   hipStream_t st, double* op_ms) {
-    if (check_batch(c, batch)) return -1;
-    if (c->cfg.with_network != 4) return fail(std::string(who) + ": the context was not created with with_network = 4");
-    if (!c->finalized) return fail(std::string(who) + " before quber_finalize_weights");
-    if (!xyz) return fail(std::string(who) + ": null xyz");
-    if (flags & ~1) return fail(std::string(who) + ": unknown flag bits");
-    quber::TuneScope tscope(&c->tune);
-    c->dsn_xyz = xyz; c->dsn_flags = flags;
-    c->dsn_logits = fg_logits; c->dsn_offsets = offsets; c->dsn_votes = votes; c->dsn_classes = fg_classes; c->dsn_fg = fg;
+// every op of a U-Net plan (plan_dsn.hip, plan_rrn.hip) in plan order; op_ms (the profiled forms): an event pair around every op, read after one synchronisation
+static int run_ops(quber_ctx* c, int batch, hipStream_t st, double* op_ms) {
     const size_t n = c->ops.size();
     if (op_ms && c->prof_events.size() < 2 * n) {
         const size_t old = c->prof_events.size();
@@ -426,6 +423,20 @@ static int dsn_run(quber_ctx* c, const char* who, const float* xyz, int batch, i
     return 0;
 }
 
+// quber_dsn_forward / quber_dsn_forward_profiled: the checks, the pointers the plan's first and last op read, then run_ops
+static int dsn_run(quber_ctx* c, const char* who, const float* xyz, int batch, int flags, float* fg_logits, float* offsets, float* votes, uint8_t* fg_classes, uint8_t* fg,
+                   hipStream_t st, double* op_ms) {
+    if (check_batch(c, batch)) return -1;
+    if (c->cfg.with_network != 4) return fail(std::string(who) + ": the context was not created with with_network = 4");
+    if (!c->finalized) return fail(std::string(who) + " before quber_finalize_weights");
+    if (!xyz) return fail(std::string(who) + ": null xyz");
+    if (flags & ~1) return fail(std::string(who) + ": unknown flag bits");
+    quber::TuneScope tscope(&c->tune);
+    c->dsn_xyz = xyz; c->dsn_flags = flags;
+    c->dsn_logits = fg_logits; c->dsn_offsets = offsets; c->dsn_votes = votes; c->dsn_classes = fg_classes; c->dsn_fg = fg;
+    return run_ops(c, batch, st, op_ms);
+}
+
 int quber_dsn_forward(quber_ctx* c, const float* xyz, int32_t batch, int32_t flags, float* fg_logits, float* offsets, float* votes, uint8_t* fg_classes, uint8_t* fg,
                       void* stream) {
     return dsn_run(c, "quber_dsn_forward", xyz, batch, flags, fg_logits, offsets, votes, fg_classes, fg, (hipStream_t)stream, nullptr);
@@ -435,6 +446,30 @@ int quber_dsn_forward_profiled(quber_ctx* c, const float* xyz, int32_t batch, in
                                uint8_t* fg, void* stream, double* op_ms) {
     if (!op_ms) return fail("quber_dsn_forward_profiled: null op_ms");
     return dsn_run(c, "quber_dsn_forward_profiled", xyz, batch, flags, fg_logits, offsets, votes, fg_classes, fg, (hipStream_t)stream, op_ms);
+}
+
+// quber_rrn_forward / quber_rrn_forward_profiled: the same for a Region Refinement Network context
+static int rrn_run(quber_ctx* c, const char* who, const float* rgb_crop, const uint8_t* mask_crop, int n, float thr, float* logits, uint8_t* refined, hipStream_t st,
+                   double* op_ms) {
+    if (check_batch(c, n)) return -1;
+    if (c->cfg.with_network != 5) return fail(std::string(who) + ": the context was not created with with_network = 5");
+    if (!c->finalized) return fail(std::string(who) + " before quber_finalize_weights");
+    if (!rgb_crop || !mask_crop) return fail(std::string(who) + ": null crops");
+    if (!logits && !refined) return fail(std::string(who) + ": neither logits nor refined masks requested");
+    if (!(thr == thr)) return fail(std::string(who) + ": logit_threshold is not a number");
+    quber::TuneScope tscope(&c->tune);
+    c->rrn_rgb = rgb_crop; c->rrn_mask = mask_crop; c->rrn_thr = thr; c->rrn_logits = logits; c->rrn_refined = refined;
+    return run_ops(c, n, st, op_ms);
+}
+
+int quber_rrn_forward(quber_ctx* c, const float* rgb_crop, const uint8_t* mask_crop, int32_t n, float logit_threshold, float* logits, uint8_t* refined, void* stream) {
+    return rrn_run(c, "quber_rrn_forward", rgb_crop, mask_crop, n, logit_threshold, logits, refined, (hipStream_t)stream, nullptr);
+}
+
+int quber_rrn_forward_profiled(quber_ctx* c, const float* rgb_crop, const uint8_t* mask_crop, int32_t n, float logit_threshold, float* logits, uint8_t* refined,
+                               void* stream, double* op_ms) {
+    if (!op_ms) return fail("quber_rrn_forward_profiled: null op_ms");
+    return rrn_run(c, "quber_rrn_forward_profiled", rgb_crop, mask_crop, n, logit_threshold, logits, refined, (hipStream_t)stream, op_ms);
 }
 
 int quber_forward_profiled(quber_ctx* c, const uint8_t* bgr, const uint8_t* depth, const float* offs, int32_t batch,
@@ -832,9 +867,9 @@ static int zoom_ws(quber_ctx* c) {           // the only allocation of the three
     return ws_reserve(c, c->lazy[WS_ZOOM], zoom_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width));
 }
 
-static int zoom_aligned4(std::initializer_list<const void*> ps) {
+static int zoom_aligned4(std::initializer_list<const void*> ps, const char* who = "zoom") {
     for (const void* p : ps)
-        if ((uintptr_t)p & 3) return fail("zoom: a 32-bit tensor that is not 4-byte aligned");
+        if ((uintptr_t)p & 3) return fail(std::string(who) + ": a 32-bit tensor that is not 4-byte aligned");
     return 0;
 }
 
@@ -881,6 +916,35 @@ int quber_zoom_paste(quber_ctx* c, const int32_t* crop_ids, const float* crop_sc
     return launch_zoom_paste(crop_ids, crop_scores, table, area, depth_crop, slots, rois, batch, n_ids, n_slots, crop, n_crop_ids, min_overlap,
                              max_inst, c->cfg.height, c->cfg.width, out_ids, out_masks, source, out_scores, boxes, report, c->lazy[WS_ZOOM].p,
                              c->cfg.max_batch, (hipStream_t)stream);
+}
+
+// ---- Region Refinement Network: crops in, refined masks back (rrn.hip); usable on a context without a network ----
+int quber_rrn_crop(quber_ctx* c, const uint8_t* bytes, const int32_t* ids, const int32_t* slots, const int32_t* rois, const float* table, int32_t batch,
+                   int32_t n_ids, int32_t n_slots, int32_t crop, float* rgb_crop, uint8_t* mask_crop, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_ids < 0 || n_ids > 254) return fail("rrn crop: n_ids outside 0..254");
+    if (n_slots < 0 || n_slots > c->cfg.max_batch * 254) return fail("rrn crop: n_slots outside 0..254 * max_batch");
+    if (crop < 2 || crop > 512) return fail("rrn crop: crop outside 2..512");
+    if (n_slots == 0) return 0;
+    if (!bytes || !ids || !slots || !rois || !table || !rgb_crop || !mask_crop) return fail("rrn crop: null tensor");
+    if (zoom_aligned4({ids, slots, rois, table, rgb_crop}, "rrn crop")) return -1;
+    return launch_rrn_crop(bytes, ids, slots, rois, table, batch, n_ids, n_slots, crop, c->cfg.height, c->cfg.width, rgb_crop, mask_crop, (hipStream_t)stream);
+}
+
+int quber_rrn_paste(quber_ctx* c, const uint8_t* refined, const int32_t* slots, const int32_t* rois, const float* z, int32_t batch, int32_t n_ids,
+                    int32_t n_slots, int32_t crop, int32_t n_masks, int32_t* out_ids, uint8_t* out_masks, int32_t* source, float* keys, int32_t* report,
+                    void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_ids < 0 || n_ids > 254) return fail("rrn paste: n_ids outside 0..254");
+    if (n_slots < 0 || n_slots > c->cfg.max_batch * 254) return fail("rrn paste: n_slots outside 0..254 * max_batch");
+    if (crop < 2 || crop > 512) return fail("rrn paste: crop outside 2..512");
+    if (n_masks < 1 || n_masks > 254) return fail("rrn paste: n_masks outside 1..254");
+    if (!z || !out_ids || !out_masks || !source || !report) return fail("rrn paste: null tensor");
+    if (n_slots > 0 && (!refined || !slots || !rois || !keys)) return fail("rrn paste: null tensor");
+    if (zoom_aligned4({slots, rois, z, out_ids, source, keys, report}, "rrn paste")) return -1;
+    if (ws_reserve(c, c->lazy[WS_RRN], rrn_paste_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width))) return -1;   // made by the first call, and kept
+    return launch_rrn_paste(refined, slots, rois, z, batch, n_ids, n_slots, crop, n_masks, c->cfg.height, c->cfg.width, out_ids, out_masks, source, keys, report,
+                            c->lazy[WS_RRN].p, c->cfg.max_batch, (hipStream_t)stream);
 }
 
 // ---- validation losses: targets, loss record (losses.hip); usable on a context without a network ----

@@ -561,6 +561,21 @@ int quber_op_dsn_head(const float* f, int32_t f_cs, int32_t B, int32_t h, int32_
     return launch_dsn_head(lview(f, B, h, w, c, f_cs), B, clean, wfg, wcd, logits, offsets, votes, classes, fg, (hipStream_t)stream);
 }
 
+// ---- the Region Refinement Network kernels of rrn.hip on explicit fp32 views (tests): arguments -> View -> launcher, nothing else ----
+int quber_op_rrn_pack(const float* rgb, const uint8_t* mask, int32_t B, int32_t h, int32_t w, float* x8, void* stream) {
+    return launch_rrn_pack(rgb, mask, B, h, w, x8, (hipStream_t)stream);
+}
+
+int quber_op_rrn_head(const float* f, int32_t f_cs, int32_t B, int32_t h, int32_t w, int32_t c, const float* wfg, float thr, float* logits, uint8_t* refined,
+                      void* stream) {
+    return launch_rrn_head(lview(f, B, h, w, c, f_cs), B, wfg, thr, logits, refined, (hipStream_t)stream);
+}
+
+int quber_op_rrn_head3(const float* f, int32_t f_cs, int32_t B, int32_t h, int32_t w, int32_t c, const float* w9, float bias, float thr, float* logits,
+                       uint8_t* refined, void* stream) {
+    return launch_rrn_head3(lview(f, B, h, w, c, f_cs), B, w9, bias, thr, logits, refined, (hipStream_t)stream);
+}
+
 int quber_op_maxpool3x3s2(const float* x, int32_t B, int32_t h, int32_t w, int32_t c, float* y, void* stream) {
     if (c % 4) return fail("maxpool: channels must be a multiple of 4");
     return launch_maxpool3x3s2(mkview(x, B, h, w, c), mkview(y, B, (h + 1) / 2, (w + 1) / 2, c), B, 1, (hipStream_t)stream);

@@ -233,6 +233,8 @@ struct Tuning {
     int cgnet_fused = 1;         // key 52 (plan): CGNet (plan_cgnet.hip): a context-guided block as cg_joint + cg_apply (cgnet.hip); 0 = 1x1 convolution, two depthwise launches, cg_sums, cg_apply
     int dsn_fused = 0;           // key 53 (plan): Depth Seeding Network (plan_dsn.hip): the five dilated convolutions of an ESP module, their running sums, the residual and the GroupNorm sums
                                  //   as one kernel, esp_branches (dsn.hip); 0 = five convolution launches + esp_merge
+    int rrn_head = 1;            // key 54 (plan): Region Refinement Network (plan_rrn.hip): 1 = decoder.last_conv and fg_module as one collapsed 3x3 filter, rrn_head3 (rrn.hip);
+                                 //   0 = the convolution with its bias, then the 1x1 head kernel
     int h8_min_tiles = 224;      // key 32 (launch): fewest tiles (all groups) of a launch that takes it (one block per CU: a launch of fewer tiles leaves CUs idle)
 };
 extern Tuning g_tune;
@@ -337,6 +339,18 @@ int launch_esp_merge(const View d[5], const View* x, const View& out, int B, int
 int launch_esp_stats(const double* partials, int B, int tiles, int groups, double* stats, hipStream_t st);
 int launch_dsn_head(const View& f, int B, const float* clean, const float* wfg, const float* wcd, float* logits, float* offsets, float* votes, uint8_t* classes,
                     uint8_t* fg, hipStream_t st);
+
+// Region Refinement Network of UOIS-Net-3D (rrn.hip): its ends (planar crops -> NHWC-8; the 1x1 head on decoder.last_conv's output, or the collapsed 3x3 head w9
+// [9][C] + bias on decoder.layer5's output; logits f32 / refined u8 = logit > thr, [B][H][W], either may be null) and the gather / scatter around it (the tensors
+// of quber_rrn_crop / quber_rrn_paste, include/quber_hip.h, under their names; ws: rrn_paste_ws_bytes(cap_b >= B, H, W) bytes)
+int launch_rrn_crop(const uint8_t* img, const int* ids, const int* slots, const int* rois, const float* table, int B, int n_ids, int T, int S, int H, int W,
+                    float* rgb_crop, uint8_t* mask_crop, hipStream_t st);
+int launch_rrn_pack(const float* rgb, const uint8_t* mask, int B, int H, int W, float* x8, hipStream_t st);
+int launch_rrn_head(const View& f, int B, const float* wfg, float thr, float* logits, uint8_t* refined, hipStream_t st);
+int launch_rrn_head3(const View& f, int B, const float* w9, float bias, float thr, float* logits, uint8_t* refined, hipStream_t st);
+int launch_rrn_paste(const uint8_t* refined, const int* slots, const int* rois, const float* z, int B, int n_ids, int T, int S, int N, int H, int W,
+                     int* out_ids, uint8_t* out_masks, int* source, float* keys, int* report, void* ws, int cap_b, hipStream_t st);
+size_t rrn_paste_ws_bytes(int cap_b, int H, int W);
 
 int launch_boundary_overlap(const int* pred, const int* gt, int H, int W, const int* labels, int n_pred, int n_gt, int radius,
                             void* ws, unsigned* out, hipStream_t st);

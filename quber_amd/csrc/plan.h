@@ -48,6 +48,7 @@ enum LazyId {
     WS_MEANSHIFT,   // seed slots, histograms, running minimum, raw labels, block partials of the mean-shift entries (meanshift.hip): for max_batch frames
     WS_GMS,         // counts, compacted points, running minimum, raw labels, tables, block partials of the Gaussian mean-shift entries (gms.hip): for max_batch frames
     WS_ZOOM,        // extents, keep flags, depth keys, paint order, key map of the zoom-in entries (zoom.hip): for max_batch frames
+    WS_RRN,         // block partials, counts, paint order, owner map, id tables of quber_rrn_paste (rrn.hip): for max_batch frames
     WS_LOSSES,      // moments, centres, block partials, histograms, foreground plane of the loss entries (losses.hip): for max_batch frames
     WS_COUNT
 };
@@ -120,6 +121,12 @@ struct quber_ctx {
     size_t dsn_stats_bytes = 0;
     float *dsn_logits = nullptr, *dsn_offsets = nullptr, *dsn_votes = nullptr;
     uint8_t *dsn_classes = nullptr, *dsn_fg = nullptr;
+    // Region Refinement Network contexts (with_network = 5; their GroupNorm sums are dsn_stats): set by quber_rrn_forward
+    const float* rrn_rgb = nullptr;
+    const uint8_t* rrn_mask = nullptr;
+    float rrn_thr = 0.f;
+    float* rrn_logits = nullptr;
+    uint8_t* rrn_refined = nullptr;
     double flops = 0.0;
     double wino_flops = 0.0;      // algorithmic FLOPs (batch 1) of the layers that take the Winograd path
     double wino_saved = 0.0;      // ... and the part of them the path does not execute
@@ -190,6 +197,7 @@ struct Builder {
 void build_lmff(Builder& b);     // LMFFNet (plan_lmff.hip)
 void build_cgnet(Builder& b);    // CGNet (plan_cgnet.hip)
 void build_dsn(Builder& b);      // Depth Seeding Network of UOIS-Net-3D (plan_dsn.hip)
+void build_rrn(Builder& b);      // Region Refinement Network of UOIS-Net-3D (plan_rrn.hip)
 
 int check_cfg(const quber_config& c);
 bool op_set_tuning(int key, int value);      // api_ops.hip: the process-only keys 2, 11, 12, 26 of quber_set_tuning; false: not one of them

@@ -30,7 +30,7 @@ constexpr TuneKey TUNE_KEYS[] = {
     {39, &Tuning::h8_norm, true},               {41, &Tuning::aspp_lanes, true},
     {42, &Tuning::small_n_64, false},           {43, &Tuning::zone_cols, false},
     {51, &Tuning::wino_pack, true},              {52, &Tuning::cgnet_fused, true},
-    {53, &Tuning::dsn_fused, true},
+    {53, &Tuning::dsn_fused, true},              {54, &Tuning::rrn_head, true},
 };
 int* tuning_field(Tuning& t, int key) {
     for (const TuneKey& k : TUNE_KEYS)

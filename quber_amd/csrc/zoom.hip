@@ -18,18 +18,9 @@
 //           pixel, source, scores, report) -> write (id map and the 0 / 255 planes) -> extents of the final map -> boxes.
 // Integer arithmetic except the three named float32 expressions (padding, nearest index, overlap ratio), each evaluated with the
 // correctly rounded intrinsics so that no contraction changes them.
-#include "common.h"
+#include "zoom_dev.h"
 
 namespace quber {
-
-constexpr int ZM_MAXID = 254;                // ids of a compact map; crops per frame
-constexpr int ZM_T = 256;
-
-// F.interpolate(mode="nearest"): the source index of destination index `dst` for a resize from `in` to `out` samples
-__device__ __forceinline__ int zm_near(int dst, int in, int out) {
-    const float scale = __fdiv_rn((float)in, (float)out);
-    return min((int)floorf(__fmul_rn((float)dst, scale)), in - 1);
-}
 
 // ---- extents --------------------------------------------------------------------------------------------------------------------------
 // grid (ceil(HW / 256), B).  ext u32 [B][n][4], zero on entry: max over the pixels of id j + 1 of (W - x, H - y, x + 1, y + 1).
@@ -79,25 +70,6 @@ __global__ __launch_bounds__(ZM_T) void zm_box_kernel(const unsigned* __restrict
     float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
     if (e[2]) r = make_float4((float)(W - (int)e[0]), (float)(H - (int)e[1]), (float)e[2], (float)e[3]);
     boxes[(size_t)k * 4 + 0] = r.x; boxes[(size_t)k * 4 + 1] = r.y; boxes[(size_t)k * 4 + 2] = r.z; boxes[(size_t)k * 4 + 3] = r.w;
-}
-
-// ---- slots ----------------------------------------------------------------------------------------------------------------------------
-struct ZmSlot { int b, id, x0, y0, w, h; bool ok; };
-
-// slot t -> its frame, first-pass id and ROI; ok = 0 for a slot that is no crop (frame or id out of range, a ROI that is empty or leaves
-// the frame)
-__device__ __forceinline__ ZmSlot zm_slot(const int* __restrict__ slots, const int* __restrict__ rois, int t, int B, int n_ids, int H, int W) {
-    ZmSlot s;
-    s.b = slots[2 * t];
-    s.id = slots[2 * t + 1];
-    s.x0 = s.y0 = 0; s.w = s.h = 0;
-    s.ok = s.b >= 0 && s.b < B && s.id >= 1 && s.id <= n_ids;
-    if (s.ok) {
-        const int* r = rois + ((size_t)s.b * n_ids + s.id - 1) * 4;
-        s.x0 = r[0]; s.y0 = r[1]; s.w = r[2] - r[0] + 1; s.h = r[3] - r[1] + 1;
-        s.ok = s.x0 >= 0 && s.y0 >= 0 && s.w >= 1 && s.h >= 1 && r[2] < W && r[3] < H;
-    }
-    return s;
 }
 
 // ---- crop -----------------------------------------------------------------------------------------------------------------------------

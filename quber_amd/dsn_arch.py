@@ -89,9 +89,10 @@ def strip_module_prefix(sd):
     return OrderedDict((k[len("module."):] if k.startswith("module.") else k, v) for k, v in sd.items())
 
 
-def load_checkpoint(path_or_dict):
+def load_checkpoint(path_or_dict, specs=None, what="Depth Seeding Network"):
     """A path to the reference's checkpoint (a dict with the state dict under 'model'), such a dict, or a bare state dict ->
-    {key: float32 numpy array}, keys checked against ``param_specs`` of the feature_dim the first convolution has."""
+    {key: float32 numpy array}, keys checked against ``param_specs`` of the feature_dim the first convolution has.  specs: another
+    network's ``param_specs`` with the same first key (rrn_arch), `what` its name in the messages."""
     ck = path_or_dict
     if not isinstance(ck, dict):
         import torch
@@ -103,8 +104,8 @@ def load_checkpoint(path_or_dict):
         sd[k] = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
     first = "encoder.layer1.layer1.conv1.weight"
     if first not in sd:
-        raise KeyError(f"not a Depth Seeding Network state dict: '{first}' is missing")
-    specs = param_specs(int(sd[first].shape[0]))
+        raise KeyError(f"not a {what} state dict: '{first}' is missing")
+    specs = (specs or param_specs)(int(sd[first].shape[0]))
     missing = [k for k in specs if k not in sd]
     if missing:
         raise KeyError(f"state dict lacks {len(missing)} keys, first '{missing[0]}'")

@@ -845,6 +845,56 @@ class Engine:
                                                  _ptr(o["boxes"]), _ptr(o["report"]), _stream()))
         return o
 
+    # ---- Region Refinement Network: crops in, refined masks back (csrc/rrn.hip; INTEGRATION.md "Refined initial masks of the third family") ----
+    def rrn_crop(self, bytes_, ids, slots, rois, table, crop, out=None):
+        """bytes_ u8 [B,H,W,3], ids i32 [B,H,W], slots i32 [T,2] = (frame, id), rois i32 [B,n_ids,4] (zoom_rois), table f32 [3,256]
+        (region.standardize_table), all on the device -> (rgb_crop f32 [T,3,S,S], mask_crop u8 [T,S,S] of 0 / 1), S = crop: rrn_preprocess -
+        the standardised ROI of every slot resized bilinearly (align_corners, float32, every operation rounded), its own mask by the nearest
+        rule.  out: such a pair to write into."""
+        B, T, S = ids.shape[0], slots.shape[0], int(crop)
+        n_ids = rois.shape[1]
+        assert bytes_.dtype == torch.uint8 and bytes_.is_contiguous() and bytes_.shape == (B, self.H, self.W, 3)
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.shape == (B, self.H, self.W)
+        assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape == (T, 2)
+        assert rois.dtype == torch.int32 and rois.is_contiguous() and rois.shape == (B, n_ids, 4)
+        assert table.dtype == torch.float32 and table.is_contiguous() and table.shape == (3, 256)
+        rc, mc = out if out is not None else (None, None)
+        rc = torch.empty((T, 3, S, S), dtype=torch.float32, device=self.device) if rc is None else rc
+        mc = torch.empty((T, S, S), dtype=torch.uint8, device=self.device) if mc is None else mc
+        assert rc.dtype == torch.float32 and rc.is_contiguous() and rc.shape == (T, 3, S, S)
+        assert mc.dtype == torch.uint8 and mc.is_contiguous() and mc.shape == (T, S, S)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_rrn_crop(self.h, _ptr(bytes_), _ptr(ids), _ptr(slots), _ptr(rois), _ptr(table), B, n_ids, T, S, _ptr(rc), _ptr(mc),
+                                               _stream()))
+        return rc, mc
+
+    def rrn_paste(self, refined, slots, rois, z, batch, n_masks, out=None):
+        """refined u8 [T,S,S] (non-zero = foreground), slots i32 [T,2] ascending by frame, rois i32 [B,n_ids,4], z f32 [B,H,W] (NaN counts as 0)
+        -> {"ids": i32 [B,H,W], "masks": u8 [B,n_masks,H,W] of 0 / 255, "source": i32 [B,n_masks] (the initial id of each refined mask, 0
+        behind the count), "keys": f32 [T] (mean z under each resized mask), "report": i32 [B,4] = refined masks, initial masks that
+        vanished, pixels painted, pixels painted over}: rrn_postprocess, ids compacted in ascending order.  out: such a dict to write
+        into.  Nothing is copied to the host; the first call on an engine allocates the workspace and cannot be captured into a graph."""
+        B, T, N = int(batch), slots.shape[0], int(n_masks)
+        S = refined.shape[1] if T else 2
+        n_ids, dev = rois.shape[1], self.device
+        if T:
+            assert refined.dtype == torch.uint8 and refined.is_contiguous() and refined.shape == (T, S, S)
+        assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape == (T, 2)
+        assert rois.dtype == torch.int32 and rois.is_contiguous() and rois.shape == (B, n_ids, 4)
+        assert z.dtype == torch.float32 and z.is_contiguous() and z.shape == (B, self.H, self.W)
+        spec = {"ids": ((B, self.H, self.W), torch.int32), "masks": ((B, N, self.H, self.W), torch.uint8), "source": ((B, N), torch.int32),
+                "keys": ((T,), torch.float32), "report": ((B, 4), torch.int32)}
+        o = {} if out is None else out
+        for k, (shape, dt) in spec.items():
+            if o.get(k) is None:
+                o[k] = torch.empty(shape, dtype=dt, device=dev)
+            assert o[k].dtype == dt and o[k].is_contiguous() and o[k].shape == shape, k
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_rrn_paste(self.h, _ptr(refined if T else None), _ptr(slots if T else None), _ptr(rois if T else None), _ptr(z), B,
+                                                n_ids, T, S, N, _ptr(o["ids"]), _ptr(o["masks"]), _ptr(o["source"]), _ptr(o["keys"] if T else None),
+                                                _ptr(o["report"]), _stream()))
+        return o
+
     # ---- validation losses: training targets, loss record (csrc/losses.hip; INTEGRATION.md "Validation losses") ----
     def loss_targets(self, gt_labels, n_gt, spec=None, out=None):
         """gt_labels i32 [B,H,W] (device; 0 = none, 1..n_gt, anything else counts as 0), spec: a losses.Losses (default: the reference's

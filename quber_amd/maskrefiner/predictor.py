@@ -60,6 +60,19 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
     foreground count.  Every dict gains ``seeding_fg`` (u8 [H,W]: 0 background, 1 table, 2 objects) and ``seeding_report`` (i64 [3]: the
     pixels of each class).  ``xyz=`` is a ``ValueError`` without ``seeding=``, together with ``center_votes=`` / ``fg=`` / masks, with a
     ``cluster=`` that is not a ``GaussianMeanShift``, and in ``enqueue_batch`` / ``predict_stream``.
+  * ``region=RegionRefinement(weights_or_path, padding=0.25, threshold=0.5, crop=224, chunk=20)`` beside ``cluster=GaussianMeanShift()``:
+    the third stage of UOIS-Net-3D, its Region Refinement Network (``rrn_preprocess``, ``RRNWrapper.run_on_batch``, ``rrn_postprocess``,
+    uois/src/segmentation.py:294-423, :516-560) on the device (csrc/rrn.hip, csrc/plan_rrn.hip, quber_amd/region; INTEGRATION.md "Refined
+    initial masks of the third family"), right after the clustering and before ``nms`` / ``scene`` / ``perturb`` / the encoding: every
+    clustered mask is cropped with a padded box from the frame's bytes (standardised as the reference does), refined by the network in
+    chunks of ``chunk`` crops, and painted back far objects first; the refined, compacted masks replace the clustered ones as THE initial
+    masks.  z is plane 2 of ``xyz=`` under ``seeding=``; otherwise ``depth_z=`` (f32 [H,W] per frame) is required beside
+    ``center_votes=`` / ``fg=``.  The per-frame cluster counts are read back once to build the crop list (the seeded path already reads
+    three counts per frame).  Every dict gains ``region_masks`` (u8 [count,H,W], 0 / 255, disjoint), ``region_ids`` (i32 [H,W]),
+    ``region_source`` (i64 [count]: the cluster id each refined mask came from), ``region_rois`` (i32 [clusters,4]) and ``region_report``
+    (i64 [4]: refined masks, clusters that vanished, pixels painted, pixels painted over); the ``cluster_*`` entries keep the masks
+    before the network.  A ``ValueError`` without a ``GaussianMeanShift``, without a z plane, and - as ``cluster=`` - in ``enqueue_batch``
+    / ``predict_stream``.  Default: none - nothing imported, allocated or launched, today's keys.
   * ``zoom=ZoomIn(crop=224, padding=0.25, min_overlap=0.5)``: the second, zoomed-in pass of the reference's base models (``crop_rois`` /
     ``match_label_crop``, eval/base_model.py:843-961) without leaving the device (csrc/zoom.hip; INTEGRATION.md "Zoom-in refinement"):
     every instance of pass 1 - run with all configured options, through post-processing and ``cleanup`` - is cropped with a padded box,
@@ -216,6 +229,7 @@ class PassResult:
     cl: dict = None
     ls: dict = None
     sn: dict = None
+    rg: dict = None        # what region_masks() returned (the Region Refinement Network stage), or None
     own_nm: object = None
     masks: object = None
     slots: int = 0
@@ -381,6 +395,20 @@ class RefinerModel:
         d_masks[:B].copy_(cl["masks"])
         return cl
 
+    def region_masks(self, eng, bgr, d_masks, cl, region_in, B):
+        """region: the clustered masks of the first B frames are cropped, refined by the Region Refinement Network and painted back
+        (RegionRefinement.refine), and d_masks[:B] are REPLACED by the refined, compacted masks - the pass's initial masks from here on.
+        region_in = (the RegionRefinement, z f32 [B,H,W] on the device).  One small read-back, the per-frame cluster counts, builds the
+        slot list.  -> what RegionRefinement.refine returns, or None."""
+        if region_in is None:
+            return None
+        region, z = region_in
+        counts = cl["report"][:B, 0].cpu().numpy()
+        rg = region.refine(eng, bgr[:B], cl["ids"], d_masks.shape[1], counts, z)
+        rg["counts"] = counts
+        d_masks[:B].copy_(rg["masks"])
+        return rg
+
     def scene_masks(self, eng, d_masks, scene_in, nm, B):
         """scene: the first B frames of d_masks u8 [>= B,M,H,W] (device), M = scene.max_masks, are FILLED with the instance list the scene
         perturbation makes of scene_in = (ground truth u8 [B,N,H,W] - after nms when that is set -, n_gt i32 [B], proposals u8 [B,P,H,W],
@@ -538,8 +566,9 @@ class RefinerModel:
             explicit = eng.error_maps(init, gt_masks)
         return {"rec": eng.losses(logits, tg["targets"], explicit, self.losses, heads=heads), "targets": tg, "heads": heads, "explicit": explicit}
 
-    def device_pass(self, eng, bgr, depth, masks, scores, B, *, may_stop, bufs=None, own=None, slots=None, gt=None, cluster_in=None, scene_in=None):
-        """Enqueues cluster (cluster_in: see cluster_masks) -> nms -> scene (scene_in: see scene_masks; nms then runs on ITS ground truth) -> perturb -> encode (tta: mirror, encode) -> forward -> postprocess ->
+    def device_pass(self, eng, bgr, depth, masks, scores, B, *, may_stop, bufs=None, own=None, slots=None, gt=None, cluster_in=None, scene_in=None,
+                    region_in=None):
+        """Enqueues cluster (cluster_in: see cluster_masks) -> region (region_in: see region_masks) -> nms -> scene (scene_in: see scene_masks; nms then runs on ITS ground truth) -> perturb -> encode (tta: mirror, encode) -> forward -> postprocess ->
         refine -> track -> decode for B frames on the current stream -> PassResult.  bgr / depth (or None) u8 [f*B,H,W,3] and masks u8 [f*B,N,H,W] on the device, f = 2 under tta
         with the frames in the first halves; scores f32 [B,N] (required with nms).  Nothing is read back unless may_stop and
         until_converged (refine()).  bufs: predict_one's _FrameStaging - its offsets, post tables, iteration buffers and overlap tables
@@ -547,6 +576,7 @@ class RefinerModel:
         of every frame are extracted between track and decode, where the stream has always launched that."""
         N = masks.shape[1]
         cl = self.cluster_masks(eng, masks, cluster_in, B)
+        rg = self.region_masks(eng, bgr, masks, cl, region_in, B)
         sn = None
         if self.scene is not None:
             if scene_in is None:
@@ -565,7 +595,7 @@ class RefinerModel:
         logits, post, it = self.refine(eng, bgr, depth, logits, post, B, may_stop, bufs.iter_bufs if bufs is not None else None)
         d_masks = masks[:B]
         ov = self.track(eng, d_masks, post, it, (bufs.overlap[0][:, :N], bufs.overlap[1]) if bufs is not None and self.track_initial else None)
-        rec = PassResult(eng, B, logits, post, d_masks=d_masks, own=[N] * B if own is None else own, it=it, ov=ov, pt=pt, nm=nm, cl=cl, sn=sn)
+        rec = PassResult(eng, B, logits, post, d_masks=d_masks, own=[N] * B if own is None else own, it=it, ov=ov, pt=pt, nm=nm, cl=cl, sn=sn, rg=rg)
         if slots is not None:
             rec.slots = min(max(1, slots), eng.cap)
             rec.masks = eng.extract_masks(post, rec.slots)
@@ -668,6 +698,13 @@ class RefinerModel:
             r["cluster_report"] = cl["report"][b].to(torch.int64)
             if "raw_ids" in cl:                              # a GaussianMeanShift: the map before the IMP, and the clusters' centres
                 r["cluster_raw_ids"], r["cluster_centers"] = cl["raw_ids"][b], cl["centers"][b, :n]
+        if rec.rg is not None:                               # the cluster_* entries above keep the masks before the network
+            rg, kc = rec.rg, int(rec.rg["counts"][b])
+            if "report_host" not in rg:                      # read here, with the pass's other results: nothing waits for it inside the pass
+                rg["report_host"] = rg["report"].cpu().numpy()
+            kr = int(min(rg["report_host"][b, 0], n))
+            r["region_masks"], r["region_ids"], r["region_source"] = rg["masks"][b, :kr], rg["ids"][b], rg["source"][b, :kr].to(torch.int64)
+            r["region_rois"], r["region_report"] = rg["rois"][b, :kc], torch.from_numpy(rg["report_host"][b].astype(np.int64))
         if rec.sn is not None:
             r["scene_masks"], r["scene_info"] = rec.sn["masks"][b, :n], rec.sn["info"][b, :n].to(torch.int64)
             r["scene_report"] = rec.sn["report"][b].to(torch.int64)
@@ -927,7 +964,7 @@ class RefinerModel:
 class MaskRefinerPredictor:
     def __init__(self, config_file=None, dataset_name="uoais_sim_val_panoptic", weights_file=None, device="cuda:0",
                  seed=0, state_dict=None, tta=False, decode_errors=False, iterations=1, until_converged=False, track_initial=False,
-                 cleanup=None, perturb=None, nms=None, zoom=None, losses=None, cluster=None, scene=None, options=None, seeding=None):
+                 cleanup=None, perturb=None, nms=None, zoom=None, losses=None, cluster=None, scene=None, options=None, seeding=None, region=None):
         # the options (module docstring), checked before anything is loaded; options: a RefineOptions in their place
         # seeding: None or a quber_amd.seeding.DepthSeeding - nothing is imported, allocated or launched for it without one
         if seeding is not None:
@@ -935,6 +972,14 @@ class MaskRefinerPredictor:
             if not isinstance(seeding, DepthSeeding):
                 raise ValueError(f"seeding={seeding!r}: expected None or a quber_amd.seeding.DepthSeeding")
         self.seeding = seeding
+        # region: None or a quber_amd.region.RegionRefinement - likewise
+        if region is not None:
+            from ..region import RegionRefinement
+            if not isinstance(region, RegionRefinement):
+                raise ValueError(f"region={region!r}: expected None or a quber_amd.region.RegionRefinement")
+            if not isinstance(cluster if options is None else options.cluster, GaussianMeanShift):
+                raise ValueError("region: the Region Refinement Network refines the masks of cluster=GaussianMeanShift()")
+        self.region = region
         self.options = options or RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
                                                       track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom,
                                                       losses=losses, cluster=cluster, scene=scene)
@@ -1046,6 +1091,20 @@ class MaskRefinerPredictor:
         from ..seeding import as_xyz_batch
         return as_xyz_batch(list(xyz), H, W, self.device)
 
+    def _region_z(self, B, H, W, seed_x, depth_z):
+        """region=: the checked z planes of a call before anything is launched - depth_z= as a host array f32 [B,H,W], or the point clouds
+        xyz= themselves (f32 [B,3,H,W] on the device: plane 2 is taken when the pass is enqueued); None without region=."""
+        if self.region is None:
+            return None
+        if seed_x is not None:
+            return seed_x
+        if depth_z is None or len(depth_z) != B:
+            raise ValueError("region: depth_z= of every frame (f32 [H,W]) is required beside center_votes= / fg=; with seeding= it is plane 2 of xyz=")
+        z = np.ascontiguousarray(np.stack([np.asarray(d) for d in depth_z]), dtype=np.float32)
+        if z.shape != (B, H, W):
+            raise ValueError(f"region: depth_z of shape {z.shape[1:]} per frame, expected ({H}, {W})")
+        return z
+
     def _seed(self, x):
         """xyz f32 [B,3,H,W] on the device -> (votes, fg, first, draws) for Engine.gms, all on the device, the class map u8 [B,H,W] and the
         class counts i64 [B,3] (host).  One D2H of 3 B + 1 integers: the draw of a frame's first seed needs its foreground count."""
@@ -1097,7 +1156,7 @@ class MaskRefinerPredictor:
         if scores_list is not None:
             raise ValueError("cluster: the clustering's masks have no scores; scores_list= was given")
         if isinstance(ms, GaussianMeanShift):
-            if embeddings is not None or depth_z is not None:
+            if embeddings is not None or (depth_z is not None and self.region is None):
                 raise ValueError("cluster: a GaussianMeanShift takes center_votes= and fg=, not embeddings= / depth_z=")
             return self._gms_inputs(B, H, W, center_votes, fg)
         if center_votes is not None or fg is not None:
@@ -1133,6 +1192,7 @@ class MaskRefinerPredictor:
         # (with xyz=: a placeholder until the network has run, below, once every other check has passed)
         cluster_in = () if seed_x is not None else self._cluster_inputs(B, H, W, masks_list, scores_list, embeddings, depth_z, center_votes, fg)
         gms = isinstance(self.cluster, GaussianMeanShift)
+        region_z = self._region_z(B, H, W, seed_x, depth_z)
         # rows of the mask tensor per frame; with cluster=: one plane per cluster there can be - the seeds' labels but the largest (a
         # GaussianMeanShift: a label per seed, each with min_pixels pixels of the frame)
         if cluster_in is None:
@@ -1187,7 +1247,9 @@ class MaskRefinerPredictor:
             if seed_x is None:
                 cluster_in = tuple(None if a is None else torch.from_numpy(a).to(self.device) for a in cluster_in)
         rec = model.device_pass(eng, bgr, depth, d_masks, None if sc is None else torch.from_numpy(sc).to(self.device), B, may_stop=True,
-                                own=counts, gt=gt, cluster_in=cluster_in, scene_in=scene_in)
+                                own=counts, gt=gt, cluster_in=cluster_in, scene_in=scene_in,
+                                region_in=None if self.region is None else (
+                                    self.region, seed_x[:, 2].contiguous() if seed_x is not None else torch.from_numpy(region_z).to(self.device)))
         outs = model.results(rec, (bgr, depth))
         if seeded is not None:
             for b, r in enumerate(outs):
