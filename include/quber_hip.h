@@ -1020,11 +1020,13 @@ int quber_dsn_forward_profiled(quber_ctx* ctx, const float* dev_xyz, int32_t bat
  *   quber_op_dsn_pack      planar xyz f32 [batch][3][h][w] -> dev_x8 NHWC with 8 channels (x, y, z, five zeros) and dev_clean planar; NaN -> 0, then
  *                          y negated when bit 0 of flags is set; either destination may be NULL
  *   quber_op_esp_tiles     tiles (runs of 64 pixels) per frame of the partials buffer f64 [batch][tiles][groups][2] = (sum, sum of squares)
- *   quber_op_esp_packed_floats / quber_op_esp_pack   the five OIHW filters (dilated1 [n1][n][3][3], the others [n][n][3][3]) -> the operand order
+ *   quber_op_esp_kernel    host only: ceil(n1 / 16), the instance of the one-kernel form that quber_op_esp_branches and the plan (option key 53 = 1)
+ *                          launch for n1 channels of dilated1, in 1..13; 0 where there is none (n1 < 1 or n1 > 208): both then refuse
+ *   quber_op_esp_packed_floats / quber_op_esp_pack  the five OIHW filters (dilated1 [n1][n][3][3], the others [n][n][3][3]) -> the operand order
  *                          of quber_op_esp_branches, a buffer of quber_op_esp_packed_floats(n1) floats
  *   quber_op_esp_branches  out = [x +] [d1 | d2 | d2 + d4 | (d2 + d4) + d8 | ((d2 + d4) + d8) + d16], dK = 3x3 of t with dilation = padding = K, zero
  *                          padding of t; t: n channels on a channel stride of at least 16 ceil(n1 / 16) in aligned groups of 4 - the channels
- *                          n .. 16 ceil(n1 / 16) are read and multiplied by zero: they must be finite; n1 in 1..32, 49..64, 97..112 or 193..208;
+ *                          n .. 16 ceil(n1 / 16) are read and multiplied by zero: they must be finite; n1 in 1..208 (quber_op_esp_kernel);
  *                          dev_x may be NULL; also writes the partials of out for `groups` norm groups (1..64, dividing c)
  *   quber_op_esp_merge     the same out and partials from the five convolutions as tensors (d1: n1 channels on d1_cs; the others n channels on d_cs),
  *                          added in the reference's order
@@ -1032,6 +1034,7 @@ int quber_dsn_forward_profiled(quber_ctx* ctx, const float* dev_xyz, int32_t bat
  *   quber_op_dsn_head      features NHWC (c a multiple of 4) -> logits = wfg [3][c] f, offsets = wcd [3][c] f, votes = dev_clean + offsets, classes =
  *                          the first maximal logit, fg = (class == 2); planar outputs as in quber_dsn_forward, any may be NULL */
 int32_t quber_op_esp_tiles(int32_t h, int32_t w);
+int quber_op_esp_kernel(int n1);
 int64_t quber_op_esp_packed_floats(int32_t n1);
 int quber_op_dsn_pack(const float* dev_xyz, int32_t batch, int32_t h, int32_t w, int32_t flags, float* dev_x8, float* dev_clean, void* stream);
 int quber_op_esp_pack(const float* dev_w1, const float* dev_w2, const float* dev_w4, const float* dev_w8, const float* dev_w16, int32_t n, int32_t n1,

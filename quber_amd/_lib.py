@@ -148,6 +148,7 @@ SIGNATURES = {
     "quber_dsn_forward": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "quber_dsn_forward_profiled": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "quber_op_esp_tiles": (C.c_int32, [_I, _I]),
+    "quber_op_esp_kernel": (C.c_int, [C.c_int]),
     "quber_op_esp_packed_floats": (C.c_int64, [_I]),
     "quber_op_dsn_pack": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "quber_op_esp_pack": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),

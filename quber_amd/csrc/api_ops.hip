@@ -523,7 +523,8 @@ int quber_op_cgnet_apply(const float* joi, int32_t joi_cs, const float* x, int32
 
 // ---- the Depth Seeding Network kernels of dsn.hip on explicit fp32 views (tests): arguments -> View -> launcher, nothing else ----
 int32_t quber_op_esp_tiles(int32_t h, int32_t w) { return (h < 1 || w < 1) ? 0 : esp_tiles(h, w); }
-int64_t quber_op_esp_packed_floats(int32_t n1) { return (n1 < 1 || n1 > 208) ? 0 : (int64_t)esp_packed_floats(n1); }
+int quber_op_esp_kernel(int n1) { return esp_kernel(n1); }
+int64_t quber_op_esp_packed_floats(int32_t n1) { return esp_kernel(n1) ? (int64_t)esp_packed_floats(n1) : 0; }
 
 int quber_op_dsn_pack(const float* xyz, int32_t B, int32_t h, int32_t w, int32_t flags, float* x8, float* clean, void* stream) {
     return launch_dsn_pack(xyz, B, h, w, flags, x8, clean, (hipStream_t)stream);

@@ -331,6 +331,7 @@ int launch_fg_overlap(const uint8_t* fg, int fh, int fw, const uint8_t* masks, i
 // launch_esp_merge; launch_esp_stats adds them in tile order into stats f64 [B][groups][2], the layout launch_gn_apply reads.  packed: esp_packed_floats(n1) floats
 int esp_tiles(int H, int W);
 int esp_nt(int n1);
+int esp_kernel(int n1);          // NT of the esp_branches_kernel<NT> instance launch_esp_branches has for n1 channels of d1, 0 = none (host only)
 size_t esp_packed_floats(int n1);
 int launch_dsn_pack(const float* xyz, int B, int H, int W, int flags, float* x8, float* clean, hipStream_t st);
 int launch_esp_pack(const float* const w[5], int n, int n1, float* packed, hipStream_t st);

@@ -27,6 +27,7 @@ namespace quber {
 namespace {
 
 constexpr int ESP_CHUNK = 64;         // pixels per tile: four waves of sixteen
+constexpr int ESP_NT_MAX = 13;        // widest esp_branches_kernel instance: 208 channels of d1
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -286,6 +287,8 @@ int esp_check(const char* who, const View& x, const View& out, bool has_x, int B
 
 int esp_tiles(int H, int W) { return (int)(((long)H * W + ESP_CHUNK - 1) / ESP_CHUNK); }
 int esp_nt(int n1) { return (n1 + 15) / 16; }
+// the NT of the esp_branches_kernel<NT> instance that takes n1 channels (launch_esp_branches dispatches on 1..13), 0 where there is none
+int esp_kernel(int n1) { return (n1 < 1 || n1 > 16 * ESP_NT_MAX) ? 0 : esp_nt(n1); }
 size_t esp_packed_floats(int n1) { return (size_t)5 * 9 * esp_nt(n1) * esp_nt(n1) * 256; }
 
 int launch_dsn_pack(const float* xyz, int B, int H, int W, int flags, float* x8, float* clean, hipStream_t st) {
@@ -299,7 +302,7 @@ int launch_dsn_pack(const float* xyz, int B, int H, int W, int flags, float* x8,
 }
 
 int launch_esp_pack(const float* const w[5], int n, int n1, float* packed, hipStream_t st) {
-    if (n < 1 || n1 < n || n1 > 208) return fail("esp_pack: n1 >= n >= 1, n1 at most 208");
+    if (n < 1 || n1 < n || !esp_kernel(n1)) return fail("esp_pack: n1 >= n >= 1, n1 at most 208");
     if (!packed || !aligned16(packed)) return fail("esp_pack: null or unaligned destination");
     for (int i = 0; i < 5; ++i)
         if (!w[i]) return fail("esp_pack: null filter");
@@ -310,8 +313,8 @@ int launch_esp_pack(const float* const w[5], int n, int n1, float* packed, hipSt
 
 int launch_esp_branches(const View& t, const View* x, const View& out, int B, int n, int n1, int groups, const float* packed, double* partials, int tiles, hipStream_t st) {
     if (esp_check("esp_branches", x ? *x : View(), out, x != nullptr, B, n, n1, groups, partials, tiles)) return -1;
-    const int NT = esp_nt(n1);
-    if (NT != 1 && NT != 2 && NT != 4 && NT != 7 && NT != 13) return fail("esp_branches: no kernel for this channel count (n1 in 1..32, 49..64, 97..112, 193..208)");
+    const int NT = esp_kernel(n1);
+    if (!NT) return fail("esp_branches: no kernel for this channel count (n1 in 1..208)");
     if (!t.p || !packed || t.H != out.H || t.W != out.W) return fail("esp_branches: null argument or views of different geometry");
     if (t.cs < 16 * NT || t.cs % 4 || !aligned16(t.p) || !aligned16(packed)) return fail("esp_branches: t needs a channel stride of at least 16 ceil(n1 / 16), in aligned groups of 4");
     if ((long)B * t.H * t.W * t.cs >= (1L << 31)) return fail("esp_branches: view too large");
@@ -320,13 +323,12 @@ int launch_esp_branches(const View& t, const View* x, const View& out, int B, in
     a.H = out.H; a.W = out.W; a.HW = out.H * out.W; a.n = n; a.n1 = n1; a.C = out.C; a.groups = groups; a.tiles = tiles; a.wp = packed; a.partials = partials;
     ProfScope prof("esp_branches", 4.0 * B * a.HW * (n + (x ? 2 : 1) * out.C), 2.0 * B * a.HW * 9.0 * n * (n1 + 4 * n), st);
     const dim3 grid(tiles, B);
-    switch (NT) {
-        case 1: hipLaunchKernelGGL(esp_branches_kernel<1>, grid, dim3(256), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(esp_branches_kernel<2>, grid, dim3(256), 0, st, a); break;
-        case 4: hipLaunchKernelGGL(esp_branches_kernel<4>, grid, dim3(256), 0, st, a); break;
-        case 7: hipLaunchKernelGGL(esp_branches_kernel<7>, grid, dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL(esp_branches_kernel<13>, grid, dim3(256), 0, st, a); break;
+#define ESP_CASE(N) case N: hipLaunchKernelGGL(esp_branches_kernel<N>, grid, dim3(256), 0, st, a); break;
+    switch (NT) {                              // every instance esp_kernel names
+        ESP_CASE(1) ESP_CASE(2) ESP_CASE(3) ESP_CASE(4) ESP_CASE(5) ESP_CASE(6) ESP_CASE(7) ESP_CASE(8) ESP_CASE(9) ESP_CASE(10) ESP_CASE(11) ESP_CASE(12) ESP_CASE(13)
+        default: return fail("esp_branches: no kernel for this channel count (n1 in 1..208)");
     }
+#undef ESP_CASE
     QB_CHECK(hipGetLastError());
     return 0;
 }

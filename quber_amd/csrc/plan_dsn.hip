@@ -29,6 +29,8 @@ struct DsnBuilder : UNetBuilder {
         const int G = fd;
         static const char* names[5] = {".dilated1", ".dilated2", ".dilated4", ".dilated8", ".dilated16"};
         if (fused) {
+            // a split launch_esp_branches has no kernel for is refused here, at finalize, not at the first forward
+            if (!dry && !esp_kernel(n1) && b.err.empty()) b.err = "DSN: esp_branches has no kernel for the " + std::to_string(n1) + " + 4 * " + std::to_string(nn) + " channels of " + n;
             const float* hwp[5];
             bool ok = !dry;
             for (int i = 0; i < 5; ++i) {

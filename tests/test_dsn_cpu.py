@@ -93,6 +93,25 @@ def test_plan_and_ops_lists():
     assert len(D.ops(True)) == 1 + 2 * 16 + 2 * 3 + 4 + 4 + 1 + 1 + 3 and len(D.ops(False)) == len(D.ops(True)) + 3 * 5
 
 
+def test_every_accepted_feature_dim_has_an_esp_kernel():
+    """the one-kernel form of an ESP module (option key 53 = 1) has an instance for the split of every module of every feature_dim the
+    plan accepts (a multiple of 4 in 8..64): quber_op_esp_kernel is what launch_esp_branches and the plan builder ask.  Host only."""
+    from quber_amd import _lib
+    lib = _lib.load()
+    seen = set()
+    for fd in range(8, 65, 4):
+        for c in (4 * fd, 8 * fd, 16 * fd):
+            n, n1 = dsn_arch.esp_split(c)
+            nt = lib.quber_op_esp_kernel(n1)
+            assert nt == (n1 + 15) // 16 and 1 <= nt <= 13, (fd, c, n1, nt)
+            assert lib.quber_op_esp_packed_floats(n1) == 5 * 9 * nt * nt * 256, (fd, c)
+            assert n1 + 4 * n == c and n1 >= n >= 1 and c % fd == 0, (fd, c)
+            seen.add(nt)
+    assert seen == set(range(1, 14))                                       # every instance belongs to some accepted width
+    assert [lib.quber_op_esp_kernel(n1) for n1 in (0, 1, 16, 17, 208, 209, -5)] == [0, 1, 1, 2, 13, 0, 0]
+    assert lib.quber_op_esp_packed_floats(0) == 0 and lib.quber_op_esp_packed_floats(209) == 0
+
+
 def test_first_maximum_wins():
     lg = torch.zeros((1, 3, 1, 4))
     lg[0, :, 0, 0] = torch.tensor([1.0, 2.0, 2.0])                         # a tie of the last two: class 1

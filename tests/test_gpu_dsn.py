@@ -2,7 +2,8 @@
 from the imported reference module and against the staged restatement tests/dsn_torch.py, for both plans (option key 53: the second
 half of an ESP module as one kernel / five convolution launches + esp_merge).
 
-Layer by layer (test_dsn_layers): one forward at batch 3 of a capacity-4 engine, then every launch is held to the staged restatement
+Layer by layer (test_dsn_layers): one forward at batch 3 of a capacity-4 engine (feature_dim 64, 96 x 128) or batch 2 of a capacity-3
+engine (every other feature_dim the plan accepts, 32 x 48: LAYER_CASES), then every launch is held to the staged restatement
 evaluated in float64 ON THE DEVICE'S OWN INPUTS of that launch.  Bars, from the arithmetic (u = 2^-24):
   pack, max pool, fg     exact: no arithmetic but a sign flip and comparisons
   dense convolutions     max |err| / max(1, max |ref|) < 2e-6, the bar of the exact-fp32 convolution kernels (tests/test_gpu_cgnet.py)
@@ -120,19 +121,21 @@ def _esp_slots(ds, x):
 
 # ---- layer by layer ----
 class _Forward:
-    """one forward at batch 3 of a capacity-4 engine with every tap read back as float64 NCHW"""
+    """one forward at batch n of a capacity-cap engine with every tap read back as float64 NCHW"""
 
-    def __init__(self, h, w, fused):
-        self.sd = dsn_arch.init_state_dict(seed=3)
-        raw = np.stack([D.synth_xyz(h, w, s) for s in (41, 42, 43)])
+    def __init__(self, h, w, fused, feature_dim=64, n=3, cap=4):
+        self.n = n
+        self.sd = dsn_arch.init_state_dict(seed=3, feature_dim=feature_dim)
+        raw = np.stack([D.synth_xyz(h, w, s) for s in (41, 42, 43)[:n]])
         raw[1, :, : h // 2] = np.nan                                  # one frame with half its pixels missing
         self.raw = torch.from_numpy(raw)
-        net = DsnEngine(self.sd, h, w, 4, fused=fused)
+        net = DsnEngine(self.sd, h, w, cap, fused=fused)
+        assert net.feature_dim == feature_dim and net.eng.get_option(53) == fused
         o = net.run(self.raw.cuda(), logits=True, offsets=True, votes=True, classes=True, fg=True)
         self.outs = {k: v.cpu() for k, v in o.items()}
         self.plan = net.eng.plan()
         names = {s.out for s in D.plan(fused) if s.out not in D.OUTPUTS} | set(D.CONCAT) | {n + ".conv1.buf" for n in D.ESP}
-        self.taps = {n: net.eng.debug_tensor(n, 3).cpu() for n in sorted(names)}
+        self.taps = {k: net.eng.debug_tensor(k, n).cpu() for k in sorted(names)}
         net.close()
 
     def get(self, name):
@@ -141,18 +144,28 @@ class _Forward:
         if name in D.OUTPUTS:
             t = self.outs[name]
             return t.double() if t.dtype == torch.float32 else t
-        t = self.taps[name].double()                                  # [3,H,W,C]
+        t = self.taps[name].double()                                  # [n,H,W,C]
         if name == "xyz":
-            return t.reshape(3, 3, -1, t.shape[2])
+            return t.reshape(self.n, 3, -1, t.shape[2])
         return t.permute(0, 3, 1, 2)
 
 
-@pytest.mark.parametrize("fused", [1, 0], ids=["fused", "unfused"])
-def test_dsn_layers(fused):
+# (h, w, feature_dim, fused, batch, capacity).  96 x 128 at 64 as ever; then every other feature_dim the plan accepts on 32 x 48 frames: the
+# one-kernel form (key 53 = 1) at each - with 64 that executes esp_branches_kernel<NT> for every NT in 1..13 - and the five convolution
+# launches + esp_merge at 8, 12 (no multiple of 8), 20 (n == n1, whole K slices: the row-skipping dilated route), 44 and 60
+LAYER_CASES = [(96, 128, 64, 1, 3, 4), (96, 128, 64, 0, 3, 4)] + [(32, 48, fd, 1, 2, 3) for fd in range(8, 64, 4)] + [(32, 48, fd, 0, 2, 3) for fd in (8, 12, 20, 44, 60)]
+LAYER_IDS = ["fused", "unfused"] + [f"fd{fd}-{'fused' if f else 'unfused'}-{h}x{w}" for h, w, fd, f, _, _ in LAYER_CASES[2:]]
+
+
+@pytest.mark.parametrize("h,w,feature_dim,fused,n,cap", LAYER_CASES, ids=LAYER_IDS)
+def test_dsn_layers(h, w, feature_dim, fused, n, cap):
     """96 x 128: the ESP modules run on 24 x 32, 12 x 16 and 6 x 8 maps - on the last only the centre taps of d8 and d16 fall inside the
-    map, on the second d16 reaches in from neither side; 24 * 32 = 768 pixels are 12 tiles, 6 * 8 = 48 less than one."""
-    h, w = 96, 128
-    fw = _Forward(h, w, fused)
+    map, on the second d16 reaches in from neither side; 24 * 32 = 768 pixels are 12 tiles, 6 * 8 = 48 less than one.
+    32 x 48, batch 2 of 3: the ESP modules run on 8 x 12, 4 x 6 and 2 x 3 maps - 96 pixels are a tile and a half, 24 and 6 less than one;
+    on the smallest map dilation 4, 8 and 16 reach only the centre tap.  The width decides the ESP split (n1 + 4 n, the kernel instance
+    NT = ceil(n1 / 16), pad channels of t or none) and the route of every convolution (Cin % 32, Cout % 32, Cin < 128)."""
+    fd = feature_dim
+    fw = _Forward(h, w, fused, fd, n, cap)
     sd = fw.sd
     w64 = _w(sd, torch.float64)
     steps = D.plan(bool(fused))
@@ -200,7 +213,7 @@ def test_dsn_layers(fused):
             failures.append(str(ex))
             note += " FAILED"
         kinds[st.kind] = kinds.get(st.kind, 0) + 1
-        print(f"PARITY-OP | {h}x{w} fused {fused} | {st.op} | {st.out} | {st.kind} | HIP {e_hip:.3e} | {note}")
+        print(f"PARITY-OP | {h}x{w} fd {fd} fused {fused} | {st.op} | {st.out} | {st.kind} | HIP {e_hip:.3e} | {note}")
     assert not failures, "\n".join(failures)
     # the plan's ops are the restatement's, in order and under the same names
     assert [n for n, _, _, _ in fw.plan] == D.ops(bool(fused))
@@ -210,19 +223,19 @@ def test_dsn_layers(fused):
     # a concatenation buffer holds exactly its two halves; the channels of t's stride behind the real ones are still exactly zero
     for name, parts in D.CONCAT.items():
         assert torch.equal(fw.get(name), torch.cat([fw.get(p) for p in parts], 1)), name
-    for n, c in zip(D.ESP, (256, 512, 1024)):
-        nn = dsn_arch.esp_split(c)[0]
-        buf = fw.taps[n + ".conv1.buf"]
-        assert buf.shape[3] % 16 == 0 and buf.shape[3] > nn, n
-        assert (buf[..., nn:].numpy().view(np.uint32) == 0).all(), f"{n}: pad channels {nn}.. of t were written"
-        assert float(buf[..., :nn].abs().max()) > 0, n
+    for name, c in zip(D.ESP, (4 * fd, 8 * fd, 16 * fd)):
+        nn, n1 = dsn_arch.esp_split(c)
+        buf = fw.taps[name + ".conv1.buf"]
+        assert buf.shape[3] == 16 * ((n1 + 15) // 16) and buf.shape[3] >= nn, name        # (fd 20 and 40: n == n1 == the stride, no pad channels)
+        assert (buf[..., nn:].numpy().view(np.uint32) == 0).all(), f"{name}: pad channels {nn}.. of t were written"
+        assert float(buf[..., :nn].abs().max()) > 0, name
     assert fw.get("X").shape[1] == 8
-    # end to end, all three frames
+    # end to end, every frame
     lg, off = fw.outs["fg_logits"], fw.outs["center_offsets"]
     for name, got, (hip, o32, r32) in zip(("fg_logits", "center_offsets"), (lg, off), _oracle_errors((lg, off), fw.raw, sd)):
         assert float((got - r32).abs().max()) < TOL
-        for i in range(3):
-            print(f"PARITY-E2E | batch 3 of 4, {h}x{w} fused {fused} {name} frame {i} | HIP {hip[i]:.3e} | torch-fp32 {o32[i]:.3e} | ratio {hip[i] / o32[i]:.2f}")
+        for i in range(n):
+            print(f"PARITY-E2E | batch {n} of {cap}, {h}x{w} fd {fd} fused {fused} {name} frame {i} | HIP {hip[i]:.3e} | torch-fp32 {o32[i]:.3e} | ratio {hip[i] / o32[i]:.2f}")
         assert (hip <= 2 * o32).all(), (name, hip, o32)
 
 
@@ -243,7 +256,9 @@ def _view(rng, B, h, w, c, cs, c0, fill):
     return buf, torch.from_numpy(data).double().permute(0, 3, 1, 2)
 
 
-ESP_CASES = [(20, 20, 36), (64, 20, 36), (256, 20, 36), (20, 6, 8), (64, 6, 8), (256, 6, 8)]
+ESP_CASES = [(20, 20, 36), (64, 20, 36), (256, 20, 36), (20, 6, 8), (64, 6, 8), (256, 6, 8),
+             (128, 20, 36), (128, 6, 8), (192, 20, 36), (640, 6, 8), (960, 6, 8)]
+ESP_GROUPS = {20: 10, 64: 64, 256: 64, 128: 64, 192: 48, 640: 40, 960: 60}          # norm groups: a divisor of C, at most 64
 
 
 @pytest.mark.parametrize("c,h,w", ESP_CASES, ids=[f"c{c}-{h}x{w}" for c, h, w in ESP_CASES])
@@ -251,11 +266,14 @@ def test_esp_hooks(c, h, w):
     """20 x 36: dilation 16 reaches into the map from both sides in both axes (rows 0..3 and 16..19 see a tap 16 rows away), 720 pixels
     are 11 tiles and a quarter; 6 x 8: only the centre taps of d8 / d16 fall inside, 48 pixels are three waves of one tile.  C = 20
     (n = n1 = 4), 64 (12 / 16), 256 (51 / 52: t on a stride of 64 + 8 behind 4 foreign channels, the channels 51.. holding 1e3).  Batch 2
-    of capacity 3; the module's input and output are channel slices of wider buffers."""
+    of capacity 3; the module's input and output are channel slices of wider buffers.  C = 128 (25 / 28) and 192 (38 / 40) run the kernel
+    instances NT = 2 and 3, 640 (128 / 128) and 960 (192 / 192) NT = 8 and 12 with n == n1 a multiple of 16: t has no pad channels, the
+    first foreign one follows the last real one."""
     lib = _lib.load()
     rng = np.random.default_rng(c * 1000 + h)
     n, n1 = dsn_arch.esp_split(c)
-    groups = {20: 10, 64: 64, 256: 64}[c]
+    groups = ESP_GROUPS[c]
+    assert c % groups == 0 and groups <= 64 and lib.quber_op_esp_kernel(n1) == (n1 + 15) // 16
     B, cap = 2, 3
     nt16 = 16 * ((n1 + 15) // 16)
     t_cs, t_c0 = nt16 + 12, 4

@@ -120,11 +120,19 @@ class _Forward:
         return self.taps[name].double().permute(0, 3, 1, 2)
 
 
-@pytest.mark.parametrize("head", [0, 1], ids=["conv+1x1", "collapsed"])
-def test_rrn_layers(head):
-    """S = 32, feature_dim 8: the maps are 32, 16, 8, 4 and 2 pixels wide; batch 3 of a capacity-4 engine."""
-    S, fd = 32, 8
+_HEADS = ("conv+1x1", "collapsed")
+LAYER_CASES = [(fd, head) for fd in (8, 12, 20, 44, 60) for head in (0, 1)]
+LAYER_IDS = [_HEADS[head] if fd == 8 else f"fd{fd}-{_HEADS[head]}" for fd, head in LAYER_CASES]
+
+
+@pytest.mark.parametrize("feature_dim,head", LAYER_CASES, ids=LAYER_IDS)
+def test_rrn_layers(feature_dim, head):
+    """S = 32: the maps are 32, 16, 8, 4 and 2 pixels wide; batch 3 of a capacity-4 engine.  feature_dim 8, and widths that route the
+    convolutions otherwise: 12 and 44 (channel counts that are no multiple of 8), 20 (whole K slices of 32 from 160 channels on), 60
+    (the last staged chunk of rr_head3_kernel is 12 channels)."""
+    S, fd = 32, feature_dim
     fw = _Forward(S, fd, head, 3, 4)
+    assert int(fw.sd["encoder.layer1.layer1.conv1.weight"].shape[0]) == fd
     w64 = _w(fw.sd, torch.float64)
     failures, kinds = [], {}
     for st in R.plan(head):
@@ -209,10 +217,11 @@ def _st():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-@pytest.mark.parametrize("S,fd", [(16, 8), (48, 8), (16, 24), (16, 64), (48, 64)], ids=lambda v: str(v))
+@pytest.mark.parametrize("S,fd", [(16, 8), (48, 8), (16, 24), (16, 64), (48, 64), (16, 12), (16, 44), (48, 60)], ids=lambda v: str(v))
 def test_rrn_head_hooks(S, fd):
     """rrn_head3 and rrn_head on a channel slice of a wider buffer holding 1e3 elsewhere, batch 2 of 3, the input shifted by 40: a kernel that pads
     with anything but zero, reads the next frame's rows or a foreign channel misses the bound by orders of magnitude.  48 is three tiles of 16; 24 channels are a staged chunk of 16 and one of 8;
+    12, 44 and 60 channels end in a staged chunk of 12: three quads, so the staging loop's split of its index into (pixel, quad) is a division by 3;
     the frames behind the batch and the other outputs stay untouched."""
     lib = _lib.load()
     rng = np.random.default_rng(S * 100 + fd)
