@@ -1013,12 +1013,26 @@ int quber_dsn_forward(quber_ctx* ctx, const float* dev_xyz, int32_t batch, int32
  * of op i (quber_op_info) to op_ms[i], quber_num_ops doubles on the host */
 int quber_dsn_forward_profiled(quber_ctx* ctx, const float* dev_xyz, int32_t batch, int32_t flags, float* dev_fg_logits, float* dev_offsets,
                                float* dev_votes, uint8_t* dev_fg_classes, uint8_t* dev_fg, void* stream, double* op_ms);
+/* quber_dsn_forward from a depth image: dev_z f32 [B][H][W] in metres (NaN / inf / 0 / negative pass through the arithmetic) and cam = (fx, fy, cx, cy)
+ * on the host, read during the call.  The plan's first op back-projects and packs in one kernel; the point cloud never exists as a tensor of its own.
+ *   convention 0 "pinhole" (eval/base_model.py:489-495): float64, x = ((col - cx) / fx) * z, y = ((row - cy) / fy) * z, rounded to float32 once
+ *   convention 1 "uois" (compute_xyz): float32 with the camera rounded to float32 first, x = ((col - cx) * z) / fx, y = (((H - 1 - row) - cy) * z) / fy
+ * every operation rounded on its own (quber_amd/camera.py xyz_np is the contract).  NaN -> 0 and bit 0 of flags apply to the result, as in
+ * quber_dsn_forward; the outputs are those of quber_dsn_forward.  The camera must be finite, the focal lengths other than zero. */
+int quber_dsn_forward_depth(quber_ctx* ctx, const float* dev_z, int32_t batch, int32_t flags, const double* cam, int32_t convention, float* dev_fg_logits,
+                            float* dev_offsets, float* dev_votes, uint8_t* dev_fg_classes, uint8_t* dev_fg, void* stream);
+int quber_dsn_forward_depth_profiled(quber_ctx* ctx, const float* dev_z, int32_t batch, int32_t flags, const double* cam, int32_t convention,
+                                     float* dev_fg_logits, float* dev_offsets, float* dev_votes, uint8_t* dev_fg_classes, uint8_t* dev_fg, void* stream,
+                                     double* op_ms);
 
 /* The kernels of the Depth Seeding Network (csrc/dsn.hip), each on explicit fp32 views - test hooks: the network reaches them only through
  * quber_dsn_forward.  An NHWC view is (pointer to its first channel, cs = elements between two pixels).  An ESP module of c channels splits them as
  * n = c / 5 (integer), n1 = c - 4 n.  A refused view returns an error and launches nothing; no op allocates or synchronises.
  *   quber_op_dsn_pack      planar xyz f32 [batch][3][h][w] -> dev_x8 NHWC with 8 channels (x, y, z, five zeros) and dev_clean planar; NaN -> 0, then
  *                          y negated when bit 0 of flags is set; either destination may be NULL
+ *   quber_op_xyz_from_depth  depth f32 [batch][h][w] + cam (fx, fy, cx, cy; host) -> dev_xyz_raw planar f32 [batch][3][h][w] with NaN kept, and / or the
+ *                          two outputs quber_op_dsn_pack makes of it (conventions and flags: quber_dsn_forward_depth); any destination may be NULL, not all;
+ *                          no multiple-of-16 rule
  *   quber_op_esp_tiles     tiles (runs of 64 pixels) per frame of the partials buffer f64 [batch][tiles][groups][2] = (sum, sum of squares)
  *   quber_op_esp_kernel    host only: ceil(n1 / 16), the instance of the one-kernel form that quber_op_esp_branches and the plan (option key 53 = 1)
  *                          launch for n1 channels of dilated1, in 1..13; 0 where there is none (n1 < 1 or n1 > 208): both then refuse
@@ -1037,6 +1051,8 @@ int32_t quber_op_esp_tiles(int32_t h, int32_t w);
 int quber_op_esp_kernel(int n1);
 int64_t quber_op_esp_packed_floats(int32_t n1);
 int quber_op_dsn_pack(const float* dev_xyz, int32_t batch, int32_t h, int32_t w, int32_t flags, float* dev_x8, float* dev_clean, void* stream);
+int quber_op_xyz_from_depth(const float* dev_z, int32_t batch, int32_t h, int32_t w, const double* cam, int32_t convention, int32_t flags, float* dev_xyz_raw,
+                            float* dev_x8, float* dev_clean, void* stream);
 int quber_op_esp_pack(const float* dev_w1, const float* dev_w2, const float* dev_w4, const float* dev_w8, const float* dev_w16, int32_t n, int32_t n1,
                       float* dev_packed, void* stream);
 int quber_op_esp_branches(const float* dev_t, int32_t t_cs, const float* dev_x, int32_t x_cs, float* dev_out, int32_t out_cs, int32_t batch, int32_t h,

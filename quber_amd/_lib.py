@@ -147,10 +147,13 @@ SIGNATURES = {
     # the Depth Seeding Network (csrc/dsn.hip, csrc/plan_dsn.hip) and its kernels on explicit fp32 views (tests/test_gpu_dsn.py)
     "quber_dsn_forward": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "quber_dsn_forward_profiled": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "quber_dsn_forward_depth": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "quber_dsn_forward_depth_profiled": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "quber_op_esp_tiles": (C.c_int32, [_I, _I]),
     "quber_op_esp_kernel": (C.c_int, [C.c_int]),
     "quber_op_esp_packed_floats": (C.c_int64, [_I]),
     "quber_op_dsn_pack": (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "quber_op_xyz_from_depth": (C.c_int, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "quber_op_esp_pack": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "quber_op_esp_branches": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "quber_op_esp_merge": (C.c_int, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),

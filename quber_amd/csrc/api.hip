@@ -424,15 +424,25 @@ static int run_ops(quber_ctx* c, int batch, hipStream_t st, double* op_ms) {
 }
 
 // quber_dsn_forward / quber_dsn_forward_profiled: the checks, the pointers the plan's first and last op read, then run_ops
+// (z + cam + convention in place of xyz: quber_dsn_forward_depth)
 static int dsn_run(quber_ctx* c, const char* who, const float* xyz, int batch, int flags, float* fg_logits, float* offsets, float* votes, uint8_t* fg_classes, uint8_t* fg,
-                   hipStream_t st, double* op_ms) {
+                   hipStream_t st, double* op_ms, const float* z = nullptr, const double* cam = nullptr, int convention = 0) {
     if (check_batch(c, batch)) return -1;
     if (c->cfg.with_network != 4) return fail(std::string(who) + ": the context was not created with with_network = 4");
     if (!c->finalized) return fail(std::string(who) + " before quber_finalize_weights");
-    if (!xyz) return fail(std::string(who) + ": null xyz");
+    if (!xyz && !z) return fail(std::string(who) + (cam ? ": null depth" : ": null xyz"));
     if (flags & ~1) return fail(std::string(who) + ": unknown flag bits");
+    if (z) {
+        if (!cam) return fail(std::string(who) + ": null camera");
+        if (convention != 0 && convention != 1) return fail(std::string(who) + ": convention 0 (pinhole) or 1 (uois)");
+        for (int i = 0; i < 4; ++i) {
+            if (!std::isfinite(cam[i]) || (i < 2 && cam[i] == 0.0)) return fail(std::string(who) + ": the camera must be finite with focal lengths other than zero");
+            c->dsn_cam[i] = cam[i];
+        }
+        c->dsn_convention = convention;
+    }
     quber::TuneScope tscope(&c->tune);
-    c->dsn_xyz = xyz; c->dsn_flags = flags;
+    c->dsn_xyz = xyz; c->dsn_z = z; c->dsn_flags = flags;
     c->dsn_logits = fg_logits; c->dsn_offsets = offsets; c->dsn_votes = votes; c->dsn_classes = fg_classes; c->dsn_fg = fg;
     return run_ops(c, batch, st, op_ms);
 }
@@ -446,6 +456,18 @@ int quber_dsn_forward_profiled(quber_ctx* c, const float* xyz, int32_t batch, in
                                uint8_t* fg, void* stream, double* op_ms) {
     if (!op_ms) return fail("quber_dsn_forward_profiled: null op_ms");
     return dsn_run(c, "quber_dsn_forward_profiled", xyz, batch, flags, fg_logits, offsets, votes, fg_classes, fg, (hipStream_t)stream, op_ms);
+}
+
+int quber_dsn_forward_depth(quber_ctx* c, const float* z, int32_t batch, int32_t flags, const double* cam, int32_t convention, float* fg_logits, float* offsets,
+                            float* votes, uint8_t* fg_classes, uint8_t* fg, void* stream) {
+    if (!z || !cam) return fail("quber_dsn_forward_depth: null depth or camera");
+    return dsn_run(c, "quber_dsn_forward_depth", nullptr, batch, flags, fg_logits, offsets, votes, fg_classes, fg, (hipStream_t)stream, nullptr, z, cam, convention);
+}
+
+int quber_dsn_forward_depth_profiled(quber_ctx* c, const float* z, int32_t batch, int32_t flags, const double* cam, int32_t convention, float* fg_logits,
+                                     float* offsets, float* votes, uint8_t* fg_classes, uint8_t* fg, void* stream, double* op_ms) {
+    if (!z || !cam || !op_ms) return fail("quber_dsn_forward_depth_profiled: null depth, camera or op_ms");
+    return dsn_run(c, "quber_dsn_forward_depth_profiled", nullptr, batch, flags, fg_logits, offsets, votes, fg_classes, fg, (hipStream_t)stream, op_ms, z, cam, convention);
 }
 
 // quber_rrn_forward / quber_rrn_forward_profiled: the same for a Region Refinement Network context

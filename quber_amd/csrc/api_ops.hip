@@ -529,6 +529,10 @@ int64_t quber_op_esp_packed_floats(int32_t n1) { return esp_kernel(n1) ? (int64_
 int quber_op_dsn_pack(const float* xyz, int32_t B, int32_t h, int32_t w, int32_t flags, float* x8, float* clean, void* stream) {
     return launch_dsn_pack(xyz, B, h, w, flags, x8, clean, (hipStream_t)stream);
 }
+int quber_op_xyz_from_depth(const float* z, int32_t B, int32_t h, int32_t w, const double* cam, int32_t convention, int32_t flags, float* xyz_raw, float* x8, float* clean,
+                            void* stream) {
+    return launch_xyz_from_depth(z, B, h, w, cam, convention, flags, xyz_raw, x8, clean, (hipStream_t)stream);
+}
 
 int quber_op_esp_pack(const float* w1, const float* w2, const float* w4, const float* w8, const float* w16, int32_t n, int32_t n1, float* packed, void* stream) {
     const float* const w[5] = {w1, w2, w4, w8, w16};

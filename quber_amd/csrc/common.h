@@ -334,6 +334,8 @@ int esp_nt(int n1);
 int esp_kernel(int n1);          // NT of the esp_branches_kernel<NT> instance launch_esp_branches has for n1 channels of d1, 0 = none (host only)
 size_t esp_packed_floats(int n1);
 int launch_dsn_pack(const float* xyz, int B, int H, int W, int flags, float* x8, float* clean, hipStream_t st);
+// depth f32 [B][H][W] + camera (fx, fy, cx, cy) -> raw planar xyz (NaN kept), and / or what launch_dsn_pack makes of it; convention 0 pinhole (float64), 1 uois (float32)
+int launch_xyz_from_depth(const float* z, int B, int H, int W, const double cam[4], int convention, int flags, float* raw, float* x8, float* clean, hipStream_t st);
 int launch_esp_pack(const float* const w[5], int n, int n1, float* packed, hipStream_t st);
 int launch_esp_branches(const View& t, const View* x, const View& out, int B, int n, int n1, int groups, const float* packed, double* partials, int tiles, hipStream_t st);
 int launch_esp_merge(const View d[5], const View* x, const View& out, int B, int n, int n1, int groups, double* partials, int tiles, hipStream_t st);

@@ -21,6 +21,7 @@
 //                         votes = cleaned xyz + offsets, class = first maximal logit, fg = (class == 2).
 // No kernel waits for another workgroup.
 #include "common.h"
+#include <cmath>
 
 namespace quber {
 
@@ -58,6 +59,52 @@ __global__ void dsn_pack_kernel(const float* __restrict__ xyz, long HW, int B, i
             float* d = clean + b * 3 * HW + p;
 #pragma unroll
             for (int c = 0; c < 3; ++c) d[c * HW] = v[c];
+        }
+    }
+}
+
+// depth -> organised point cloud, the contract of quber_amd/camera.py xyz_np: every operation of the two pinned expressions is one
+// round-to-nearest intrinsic, so no contraction or reassociation can touch them
+//   convention 0 "pinhole" (eval/base_model.py:489-495): float64, ((col - cx) / fx) * z and ((row - cy) / fy) * z, rounded to float32 once
+//   convention 1 "uois" (compute_xyz): float32, ((col - cx) * z) / fx and (((H - 1 - row) - cy) * z) / fy, the camera rounded to float32 first
+// raw (NaN kept), x8 and clean (dsn_pack_kernel's outputs: NaN -> 0 per component, then y negated with bit 0 of flags): any may be null
+struct XyzCam { double fx, fy, cx, cy; };
+
+template <int CONV>
+__global__ void xyz_from_depth_kernel(const float* __restrict__ z, int H, int W, int B, int flags, const XyzCam cam, float* __restrict__ raw,
+                                      float* __restrict__ x8, float* __restrict__ clean) {
+    const long HW = (long)H * W, total = (long)B * HW;
+    const float fxf = (float)cam.fx, fyf = (float)cam.fy, cxf = (float)cam.cx, cyf = (float)cam.cy;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long b = i / HW, p = i - b * HW;
+        const int row = (int)(p / W), col = (int)(p - (long)row * W);
+        const float zz = z[i];
+        float v[3];
+        if (CONV == 0) {
+            const double zd = (double)zz;
+            v[0] = __double2float_rn(__dmul_rn(__ddiv_rn(__dsub_rn((double)col, cam.cx), cam.fx), zd));
+            v[1] = __double2float_rn(__dmul_rn(__ddiv_rn(__dsub_rn((double)row, cam.cy), cam.fy), zd));
+        } else {
+            v[0] = __fdiv_rn(__fmul_rn(__fsub_rn((float)col, cxf), zz), fxf);
+            v[1] = __fdiv_rn(__fmul_rn(__fsub_rn((float)(H - 1 - row), cyf), zz), fyf);
+        }
+        v[2] = zz;
+        const long base = b * 3 * HW + p;
+        if (raw) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) raw[base + c * HW] = v[c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = v[c] != v[c] ? 0.f : v[c];
+        if (flags & 1) v[1] = -v[1];
+        if (x8) {
+            float4* dst = reinterpret_cast<float4*>(x8 + i * 8);
+            dst[0] = make_float4(v[0], v[1], v[2], 0.f);
+            dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (clean) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) clean[base + c * HW] = v[c];
         }
     }
 }
@@ -297,6 +344,24 @@ int launch_dsn_pack(const float* xyz, int B, int H, int W, int flags, float* x8,
     if (x8 && !aligned16(x8)) return fail("dsn_pack: the packed output must be 16-byte aligned");
     ProfScope prof("dsn_pack", 4.0 * B * H * W * (3 + 8 + 3), 0.0, st);
     hipLaunchKernelGGL(dsn_pack_kernel, dim3(grid1d((long)B * H * W)), dim3(256), 0, st, xyz, (long)H * W, B, flags, x8, clean);
+    QB_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_xyz_from_depth(const float* z, int B, int H, int W, const double cam[4], int convention, int flags, float* raw, float* x8, float* clean, hipStream_t st) {
+    if (!z || !cam || (!raw && !x8 && !clean)) return fail("xyz_from_depth: null argument");
+    if (B < 1 || H < 1 || W < 1 || (long)B * H * W * 8 >= (1L << 31)) return fail("xyz_from_depth: empty or too large");
+    if (convention != 0 && convention != 1) return fail("xyz_from_depth: convention 0 (pinhole, float64) or 1 (uois, float32)");
+    if (flags & ~1) return fail("xyz_from_depth: unknown flag bits");
+    if (x8 && !aligned16(x8)) return fail("xyz_from_depth: the packed output must be 16-byte aligned");
+    for (int i = 0; i < 4; ++i)
+        if (!std::isfinite(cam[i])) return fail("xyz_from_depth: the camera (fx, fy, cx, cy) must be finite");
+    if (cam[0] == 0.0 || cam[1] == 0.0) return fail("xyz_from_depth: a focal length of zero");
+    const XyzCam c{cam[0], cam[1], cam[2], cam[3]};
+    ProfScope prof("xyz_from_depth", 4.0 * B * H * W * (1 + (raw ? 3 : 0) + (x8 ? 8 : 0) + (clean ? 3 : 0)), 0.0, st);
+    const dim3 grid(grid1d((long)B * H * W));
+    if (convention == 0) hipLaunchKernelGGL(xyz_from_depth_kernel<0>, grid, dim3(256), 0, st, z, H, W, B, flags, c, raw, x8, clean);
+    else hipLaunchKernelGGL(xyz_from_depth_kernel<1>, grid, dim3(256), 0, st, z, H, W, B, flags, c, raw, x8, clean);
     QB_CHECK(hipGetLastError());
     return 0;
 }

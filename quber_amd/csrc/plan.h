@@ -115,6 +115,9 @@ struct quber_ctx {
     float* cur_out = nullptr;
     // Depth Seeding Network contexts (with_network = 4): what the plan's first and last op read, set by quber_dsn_forward
     const float* dsn_xyz = nullptr;
+    const float* dsn_z = nullptr;   // quber_dsn_forward_depth: the depth planes the first op back-projects with dsn_cam instead of reading dsn_xyz
+    double dsn_cam[4] = {};         // fx, fy, cx, cy
+    int dsn_convention = 0;
     int dsn_flags = 0;
     float* dsn_clean = nullptr;   // [Bmax][3][H][W]: xyz with NaN -> 0 and the y flag applied
     double* dsn_stats = nullptr;  // GroupNorm sums of every norm of the plan, cleared by its first op

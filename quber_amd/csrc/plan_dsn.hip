@@ -87,6 +87,8 @@ struct DsnBuilder : UNetBuilder {
         op("pack", OP_OTHER, 2, [=](int B, hipStream_t st) {
             int rc = launch_zero(ctx->dsn_stats, ctx->dsn_stats_bytes, st);
             if (rc) return rc;
+            if (ctx->dsn_z)             // the point cloud exists only as the packed input and the cleaned planes
+                return launch_xyz_from_depth(ctx->dsn_z, B, ctx->cfg.height, ctx->cfg.width, ctx->dsn_cam, ctx->dsn_convention, ctx->dsn_flags, nullptr, ctx->X.p, ctx->dsn_clean, st);
             return launch_dsn_pack(ctx->dsn_xyz, B, ctx->cfg.height, ctx->cfg.width, ctx->dsn_flags, ctx->X.p, ctx->dsn_clean, st);
         });
         tap("X", X);

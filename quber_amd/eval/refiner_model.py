@@ -132,7 +132,11 @@ class MaskRefiner:
     def __init__(self, config_file=None, weights_file=None, dataset="OSD", device="cuda:0", foreground_filter=False,
                  lmffnet_weights="./foreground_segmentation/rgbd_lmffnet.pth", inpaint="host", tta=False,
                  decode_errors=False, iterations=1, until_converged=False, track_initial=False, cleanup=None, perturb=None,
-                 nms=None, zoom=None, losses=None, scene=None, initial_filter=None):
+                 nms=None, zoom=None, losses=None, scene=None, initial_filter=None, cluster=None, seeding=None, region=None, camera=None):
+        # cluster / seeding / region: the predictor's base-model stages (a GaussianMeanShift, a quber_amd.seeding.DepthSeeding, a
+        # quber_amd.region.RegionRefinement).  With seeding= set predict(rgb_path, depth_path) makes its own initial masks: the point cloud
+        # comes from the .pcd beside the depth file (quber_amd/eval/base_model.py: the reference's path rules) or, with camera= (a
+        # quber_amd.camera.Camera of the 640 x 480 frame), from the depth file itself; they come back as output["cluster_*"] / ["region_*"]
         # initial_filter: None | "cgnet" | a quber_amd.foreground.predictor.CGNet - the UOAIS base model's foreground filter
         # (eval/base_model.py:209-216) applied to initial_masks (and mask_scores) in _load, before anything else reads them:
         # predict() and predict_stream() alike; the foreground map and the kept indices come back as output["initial_fg"] / ["initial_keep"]
@@ -145,8 +149,18 @@ class MaskRefiner:
         # takes initial_masks as the frame's ground truth and predict(..., proposals=) as its pool of segments: predict_stream refuses it
         options = RefineOptions.parse(tta=tta, decode_errors=decode_errors, iterations=iterations, until_converged=until_converged,
                                       track_initial=track_initial, cleanup=cleanup, perturb=perturb, nms=nms, zoom=zoom, losses=losses,
-                                      scene=scene)
-        self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, options=options)
+                                      scene=scene, cluster=cluster)
+        if camera is not None and seeding is None:
+            raise ValueError("camera= needs seeding= (a quber_amd.seeding.DepthSeeding)")
+        if seeding is not None and dataset == "armbench":
+            raise ValueError("seeding: the Depth Seeding Network reads a point cloud; the armbench path has no depth")
+        self.camera = camera
+        if camera is not None:
+            from ..camera import Camera
+            if not isinstance(camera, Camera):
+                raise ValueError(f"camera={camera!r}: expected None or a quber_amd.camera.Camera")
+        self.refiner_predictor = MaskRefinerPredictor(config_file, weights_file=weights_file, device=device, options=options, seeding=seeding,
+                                                      region=region)
         self.dataset = dataset
         self.lmffnet = None
         # "host" / True (default): csrc/inpaint.hip on the calling (worker) thread; "device": csrc/inpaint_dev.hip, bit-equal, for hosts
@@ -260,9 +274,27 @@ class MaskRefiner:
             refined = np.asarray(out)
         return refined, output, elapsed, fg
 
-    def predict(self, rgb_path, depth_path, initial_masks, fg_mask=None, mask_scores=None, gt_labels=None, proposals=None):
+    def _predict_seeded(self, rgb_path, depth_path, gt_labels=None):
+        """seeding=: the whole base-model chain and the refiner in one predictor call; the geometry is read before the timer starts"""
+        from .base_model import load_geometry
+        fr = self._load(rgb_path, depth_path, np.zeros((0, H, W), np.uint8))
+        kind, geo = load_geometry(depth_path, self.dataset, self.camera, H, W)
+        kw = {"xyz": geo} if kind == "xyz" else {"depth_z": geo, "camera": self.camera}
+        start = time.time()
+        output = self.refiner_predictor.predict(fr["rgb"], fr["depth"], gt_labels=gt_labels, **kw)[0]
+        refined = output["instances"].to("cpu").pred_masks.numpy() if "instances" in output else []
+        return self._finish(fr, output, refined, start)
+
+    def predict(self, rgb_path, depth_path, initial_masks=None, fg_mask=None, mask_scores=None, gt_labels=None, proposals=None):
         # proposals (with scene=): u8 / bool [P,H,W] at the size of initial_masks - the pool the scene perturbation draws false positives
         # and over- / under-segmentations from; may be absent
+        # initial_masks=None (with seeding=): the Depth Seeding Network, the clustering and region= make them
+        if self.refiner_predictor.seeding is not None:
+            if initial_masks is not None or mask_scores is not None or proposals is not None:
+                raise ValueError("seeding: the base-model chain makes the initial masks; initial_masks / mask_scores / proposals were given as well")
+            return self._predict_seeded(rgb_path, depth_path, gt_labels)
+        if initial_masks is None:
+            raise ValueError("initial_masks=None needs seeding= (a quber_amd.seeding.DepthSeeding)")
         fr = self._load(rgb_path, depth_path, initial_masks, mask_scores)
         if proposals is not None and self.dataset == "armbench" and len(proposals):
             h, w = fr["rgb"].shape[:2]
@@ -389,6 +421,8 @@ class MaskRefiner:
         logits in the last bits (split-K partitions follow the launch size), which tests/test_gpu_network.py bounds and explains."""
         if self.refiner_predictor.zoom is not None:
             raise ValueError("zoom: predict_stream has no zoomed form; call predict() per frame (or construct without zoom=)")
+        if self.refiner_predictor.seeding is not None:
+            raise ValueError("seeding: predict_stream has no seeding form; call predict() per frame (or construct without seeding=)")
         if self.refiner_predictor.scene is not None:
             raise ValueError("scene: predict_stream has no scene form; call predict() per frame (or construct without scene=)")
         from collections import deque

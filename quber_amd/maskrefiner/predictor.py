@@ -59,7 +59,10 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
     the host, bit for bit.  Only the three class counts per frame are read back: the seeded draw of a frame's first seed needs its
     foreground count.  Every dict gains ``seeding_fg`` (u8 [H,W]: 0 background, 1 table, 2 objects) and ``seeding_report`` (i64 [3]: the
     pixels of each class).  ``xyz=`` is a ``ValueError`` without ``seeding=``, together with ``center_votes=`` / ``fg=`` / masks, with a
-    ``cluster=`` that is not a ``GaussianMeanShift``, and in ``enqueue_batch`` / ``predict_stream``.
+    ``cluster=`` that is not a ``GaussianMeanShift``, and in ``enqueue_batch`` / ``predict_stream``.  ``camera=`` (a
+    ``quber_amd.camera.Camera``) with ``depth_z=`` (f32 [H,W] per frame, metres) takes the place of ``xyz=``: the network's first kernel
+    back-projects the depth image (INTEGRATION.md "From a depth image"), the dicts are those of ``xyz=xyz_np(depth_z, camera)``, and the
+    same refusals apply, plus a missing or misshapen ``depth_z``.
   * ``region=RegionRefinement(weights_or_path, padding=0.25, threshold=0.5, crop=224, chunk=20)`` beside ``cluster=GaussianMeanShift()``:
     the third stage of UOIS-Net-3D, its Region Refinement Network (``rrn_preprocess``, ``RRNWrapper.run_on_batch``, ``rrn_postprocess``,
     uois/src/segmentation.py:294-423, :516-560) on the device (csrc/rrn.hip, csrc/plan_rrn.hip, quber_amd/region; INTEGRATION.md "Refined
@@ -71,7 +74,8 @@ and, when any instance survives, ``instances`` with ``pred_masks`` bool [K,H,W],
     three counts per frame).  Every dict gains ``region_masks`` (u8 [count,H,W], 0 / 255, disjoint), ``region_ids`` (i32 [H,W]),
     ``region_source`` (i64 [count]: the cluster id each refined mask came from), ``region_rois`` (i32 [clusters,4]) and ``region_report``
     (i64 [4]: refined masks, clusters that vanished, pixels painted, pixels painted over); the ``cluster_*`` entries keep the masks
-    before the network.  A ``ValueError`` without a ``GaussianMeanShift``, without a z plane, and - as ``cluster=`` - in ``enqueue_batch``
+    before the network.  ``RegionRefinement(final_close_morphology=True, ksize=9)`` opens and closes every refined id afterwards (the
+    reference's pass of that name); ``region_report`` is then i64 [5], its last entry the ids the close removed.  A ``ValueError`` without a ``GaussianMeanShift``, without a z plane, and - as ``cluster=`` - in ``enqueue_batch``
     / ``predict_stream``.  Default: none - nothing imported, allocated or launched, today's keys.
   * ``zoom=ZoomIn(crop=224, padding=0.25, min_overlap=0.5)``: the second, zoomed-in pass of the reference's base models (``crop_rois`` /
     ``match_label_crop``, eval/base_model.py:843-961) without leaving the device (csrc/zoom.hip; INTEGRATION.md "Zoom-in refinement"):
@@ -388,7 +392,8 @@ class RefinerModel:
         if cluster_in is None:
             raise ValueError("cluster: this call path has no embeddings (predict and predict_batch take embeddings=)")
         if isinstance(self.cluster, GaussianMeanShift):      # cluster_in = (votes f32 [B,3,H,W], fg u8 [B,H,W], first i32 [B], draws i32 [B,S])
-            cl = eng.gms(*cluster_in, self.cluster, d_masks.shape[1])
+            from ..uois_chain import cluster_stage
+            cl = cluster_stage(eng, self.cluster, cluster_in, d_masks.shape[1])
         else:
             emb, first, z = cluster_in
             cl = eng.meanshift(emb, first, self.cluster, d_masks.shape[1], z)
@@ -402,10 +407,9 @@ class RefinerModel:
         slot list.  -> what RegionRefinement.refine returns, or None."""
         if region_in is None:
             return None
+        from ..uois_chain import region_stage
         region, z = region_in
-        counts = cl["report"][:B, 0].cpu().numpy()
-        rg = region.refine(eng, bgr[:B], cl["ids"], d_masks.shape[1], counts, z)
-        rg["counts"] = counts
+        rg = region_stage(eng, region, bgr[:B], cl, d_masks.shape[1], z)
         d_masks[:B].copy_(rg["masks"])
         return rg
 
@@ -824,7 +828,8 @@ class RefinerModel:
         return self.frame_dict(rec, 0, k, masks_b, int(stg.pin_count[1]) if rec.it is not None else 0)
 
     # -- batched form on device-resident frames, split into "enqueue" and "collect" so that a caller can keep one batch in flight --
-    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None, d_scores=None, gt_labels=None, xyz=None):
+    def enqueue_batch(self, d_bgr, d_depth, d_masks, slots=32, capacity=0, halves=False, n_masks=None, d_scores=None, gt_labels=None, xyz=None,
+                      camera=None):
         """d_bgr / d_depth: u8 [B,H,W,3] (depth None for single-stream configs), d_masks: u8 [B,N,H,W] on the device.  Enqueues a1 ...
         a11 and the extraction of the first `slots` instance masks of every frame on the current stream WITHOUT synchronising;
         returns a handle for collect_batch().  halves=True (test-time augmentation only): the tensors are 2B-frame buffers
@@ -838,6 +843,8 @@ class RefinerModel:
             raise ValueError("zoom: enqueue_batch / predict_stream have no zoomed form; use predict or predict_batch")
         if xyz is not None:
             raise ValueError("xyz: enqueue_batch / predict_stream have no seeding form; use predict or predict_batch")
+        if camera is not None:
+            raise ValueError("camera: enqueue_batch / predict_stream have no seeding form; use predict or predict_batch")
         if self.cluster is not None:
             raise ValueError("cluster: enqueue_batch / predict_stream have no clustering form; use predict or predict_batch")
         if self.scene is not None:
@@ -1014,12 +1021,13 @@ class MaskRefinerPredictor:
 
     # -- reference signature (predictor.py:287) --
     def predict(self, rgb_img, depth_img=None, perturbed_masks=None, mask_scores=None, gt_labels=None, embeddings=None, depth_z=None,
-                center_votes=None, fg=None, proposals=None, xyz=None):
+                center_votes=None, fg=None, proposals=None, xyz=None, camera=None):
+        # camera (with seeding=, in place of xyz): a quber_amd.camera.Camera; depth_z (f32 [H,W], metres) is back-projected on the device
         # xyz (with seeding= and cluster=GaussianMeanShift(), in place of center_votes / fg): f32 [H,W,3] or [3,H,W], the organised point cloud
         # gt_labels (with losses=): the frame's ground-truth label map, integer [H,W], 0 = none, 1..n; the dict then carries `losses`
         # embeddings (with cluster=, in place of perturbed_masks): f32 [64,H,W]; depth_z: f32 [H,W], the depth filter's plane
         # center_votes, fg (with cluster=GaussianMeanShift(), in place of perturbed_masks): f32 [3,H,W] = xyz + offsets, and u8 / bool [H,W]
-        if self.cluster is not None or embeddings is not None or depth_z is not None or center_votes is not None or fg is not None or xyz is not None:
+        if self.cluster is not None or embeddings is not None or depth_z is not None or center_votes is not None or fg is not None or xyz is not None or camera is not None:
             if perturbed_masks is not None:
                 raise ValueError("cluster: embeddings= / center_votes= / xyz= take the place of the initial masks; both were given")
             if mask_scores is not None:
@@ -1028,7 +1036,7 @@ class MaskRefinerPredictor:
                                       gt_labels=None if gt_labels is None else [gt_labels],
                                       embeddings=None if embeddings is None else [embeddings], depth_z=None if depth_z is None else [depth_z],
                                       center_votes=None if center_votes is None else [center_votes], fg=None if fg is None else [fg],
-                                      xyz=None if xyz is None else [xyz])
+                                      xyz=None if xyz is None else [xyz], camera=camera)
         masks = np.zeros((0,) + rgb_img.shape[:2], np.uint8) if perturbed_masks is None else np.asarray(perturbed_masks)
         gts = None if gt_labels is None else [gt_labels]
         if self.scene is not None or proposals is not None:      # the general path; proposals (with scene=): u8 / bool [P,H,W], may be absent
@@ -1091,11 +1099,47 @@ class MaskRefinerPredictor:
         from ..seeding import as_xyz_batch
         return as_xyz_batch(list(xyz), H, W, self.device)
 
+    def _camera_inputs(self, B, H, W, camera, xyz, masks_list, scores_list, embeddings, depth_z, center_votes, fg):
+        """seeding= with camera=: the checked depth planes of a call as one device tensor f32 [B,H,W] (metres), before anything is
+        launched; None without camera=.  The Depth Seeding Network's first op back-projects them (csrc/dsn.hip xyz_from_depth_kernel)."""
+        if camera is None:
+            return None
+        from ..camera import Camera, check_depth_z
+        if not isinstance(camera, Camera):
+            raise ValueError(f"camera={camera!r}: expected a quber_amd.camera.Camera")
+        if self.seeding is None:
+            raise ValueError("camera= needs seeding= (a quber_amd.seeding.DepthSeeding)")
+        if not isinstance(self.cluster, GaussianMeanShift):
+            raise ValueError("camera: the Depth Seeding Network's votes go to cluster=GaussianMeanShift(); this predictor has " +
+                             ("no cluster=" if self.cluster is None else "a MeanShift"))
+        if xyz is not None:
+            raise ValueError("camera: the point cloud comes from depth_z=; xyz= was given as well")
+        if center_votes is not None or fg is not None:
+            raise ValueError("camera: the network makes the votes and the foreground; center_votes= / fg= were given as well")
+        if embeddings is not None:
+            raise ValueError("cluster: a GaussianMeanShift takes camera= and depth_z=, xyz= or center_votes= and fg=, not embeddings=")
+        if masks_list is not None:
+            raise ValueError("camera: the clustering makes the initial masks; masks were given as well")
+        if scores_list is not None:
+            raise ValueError("cluster: the clustering's masks have no scores; scores_list= was given")
+        if depth_z is None:
+            raise ValueError("camera: depth_z= of every frame (f32 [H,W], metres) is required beside camera=")
+        if len(depth_z) != B:
+            raise ValueError(f"camera: the depth planes of {len(depth_z)} frames for a batch of {B}")
+        if H % 16 or W % 16:
+            raise ValueError(f"camera: the Depth Seeding Network needs a height and width that are multiples of 16, not {H} x {W}")
+        if self.cluster.imp is not None and imp_plane_bytes(H, W) > IMP_LDS_BYTES:
+            raise ValueError(f"cluster: the IMP's two bit planes of a {H} x {W} frame do not fit the LDS; there is no global-memory fallback")
+        z = np.stack([check_depth_z(d, H, W, "camera: depth_z of frame %d" % b) for b, d in enumerate(depth_z)])
+        return torch.from_numpy(z).to(self.device)
+
     def _region_z(self, B, H, W, seed_x, depth_z):
         """region=: the checked z planes of a call before anything is launched - depth_z= as a host array f32 [B,H,W], or the point clouds
         xyz= themselves (f32 [B,3,H,W] on the device: plane 2 is taken when the pass is enqueued); None without region=."""
         if self.region is None:
             return None
+        if self.region.final_close_morphology and imp_plane_bytes(H, W) > IMP_LDS_BYTES:
+            raise ValueError(f"region: the two bit planes of a {H} x {W} frame that final_close_morphology works on do not fit the LDS")
         if seed_x is not None:
             return seed_x
         if depth_z is None or len(depth_z) != B:
@@ -1105,19 +1149,12 @@ class MaskRefinerPredictor:
             raise ValueError(f"region: depth_z of shape {z.shape[1:]} per frame, expected ({H}, {W})")
         return z
 
-    def _seed(self, x):
-        """xyz f32 [B,3,H,W] on the device -> (votes, fg, first, draws) for Engine.gms, all on the device, the class map u8 [B,H,W] and the
-        class counts i64 [B,3] (host).  One D2H of 3 B + 1 integers: the draw of a frame's first seed needs its foreground count."""
-        B, _, H, W = x.shape
-        votes, on, cls = self.seeding.engine_for(H, W, B, self.device).seed(x)
-        tally = torch.stack([(cls == k).sum((1, 2)) for k in range(3)], 1)
-        host = torch.cat([tally.reshape(-1), torch.isfinite(votes).all().to(torch.int64)[None]]).cpu().numpy()
-        if not host[-1]:
-            raise ValueError("seeding: the centre votes are not finite (xyz must be finite, or NaN where there is no depth)")
-        tally = host[:-1].reshape(B, 3)
-        first, draws = self.cluster.draws([self.cluster.n_sub(int(n)) for n in tally[:, 2]])
-        dev = lambda a: torch.from_numpy(a).to(self.device)
-        return (votes, on, dev(first), dev(draws.view(np.int32))), cls, tally
+    def _seed(self, x, camera=None):
+        """xyz f32 [B,3,H,W] on the device (with camera=: z f32 [B,H,W]) -> (votes, fg, first, draws) for Engine.gms, all on the device, the
+        class map u8 [B,H,W] and the class counts i64 [B,3] (host).  One D2H of 3 B + 1 integers: the draw of a frame's first seed needs its
+        foreground count."""
+        from ..uois_chain import seed_stage
+        return seed_stage(self.seeding, self.cluster, x, camera)
 
     def _scene_inputs(self, B, H, W, proposals):
         """scene=: the checked proposals of a call -> (u8 [B,P,H,W] with P = the longest list, zero rows behind a frame's own; their
@@ -1178,16 +1215,18 @@ class MaskRefinerPredictor:
         return emb, z
 
     def predict_batch(self, rgb_imgs, depth_imgs, masks_list, scores_list=None, gt_labels=None, embeddings=None, depth_z=None,
-                      center_votes=None, fg=None, proposals=None, xyz=None):
+                      center_votes=None, fg=None, proposals=None, xyz=None, camera=None):
         """rgb_imgs/depth_imgs: u8 [B,H,W,3] arrays; masks_list: B arrays u8/bool [N_b,H,W]; scores_list (required with nms=): B arrays
         [N_b] of finite scores; gt_labels (with losses=): the B ground-truth label maps, integer [B,H,W] or a list.  With cluster=:
         masks_list is None, embeddings: B arrays f32 [64,H,W], depth_z: B arrays f32 [H,W] (with depth_threshold); or, with a
         GaussianMeanShift, center_votes: B arrays f32 [3,H,W] and fg: B arrays u8 / bool [H,W] - or, with seeding=, xyz: B point clouds f32
-        [H,W,3] / [3,H,W] in their place.  With scene=: masks_list holds every frame's
+        [H,W,3] / [3,H,W] in their place, or camera= (a quber_amd.camera.Camera) and depth_z: B depth planes f32 [H,W] in metres, back-projected on
+        the device.  With scene=: masks_list holds every frame's
         GROUND TRUTH and proposals (optional) B arrays u8 / bool [P_b,H,W], the pool of segment proposals.  -> list of B dicts."""
         B, H, W = rgb_imgs.shape[:3]
         props = self._scene_inputs(B, H, W, proposals)
-        seed_x = self._xyz_inputs(B, H, W, xyz, masks_list, scores_list, embeddings, depth_z, center_votes, fg)
+        seed_z = self._camera_inputs(B, H, W, camera, xyz, masks_list, scores_list, embeddings, depth_z, center_votes, fg)
+        seed_x = seed_z if seed_z is not None else self._xyz_inputs(B, H, W, xyz, masks_list, scores_list, embeddings, depth_z, center_votes, fg)
         seeded = None
         # (with xyz=: a placeholder until the network has run, below, once every other check has passed)
         cluster_in = () if seed_x is not None else self._cluster_inputs(B, H, W, masks_list, scores_list, embeddings, depth_z, center_votes, fg)
@@ -1198,7 +1237,8 @@ class MaskRefinerPredictor:
         if cluster_in is None:
             counts = [len(m) for m in masks_list]
         elif gms:
-            counts = [min(self.cluster.num_seeds, 254, max(H * W // max(self.cluster.min_pixels, 1), 1))] * B
+            from ..uois_chain import mask_rows
+            counts = [mask_rows(self.cluster, H, W)] * B
         else:
             counts = [min(max(self.cluster.num_seeds - 1, 1), 254)] * B
         sc = None
@@ -1238,7 +1278,7 @@ class MaskRefinerPredictor:
             d_masks[:B].copy_(torch.from_numpy(mk))
         else:                                             # the first seeds: drawn last, so that a call that raised above has drawn nothing
             if seed_x is not None:
-                cluster_in, *seeded = self._seed(seed_x)
+                cluster_in, *seeded = self._seed(seed_x, camera)
             elif gms:
                 first, draws = self.cluster.draws([self.cluster.n_sub(int(f.sum())) for f in cluster_in[1]])
                 cluster_in = (cluster_in[0], cluster_in[1], first, draws.view(np.int32))
@@ -1249,7 +1289,8 @@ class MaskRefinerPredictor:
         rec = model.device_pass(eng, bgr, depth, d_masks, None if sc is None else torch.from_numpy(sc).to(self.device), B, may_stop=True,
                                 own=counts, gt=gt, cluster_in=cluster_in, scene_in=scene_in,
                                 region_in=None if self.region is None else (
-                                    self.region, seed_x[:, 2].contiguous() if seed_x is not None else torch.from_numpy(region_z).to(self.device)))
+                                    self.region, seed_z if seed_z is not None else seed_x[:, 2].contiguous() if seed_x is not None else
+                                    torch.from_numpy(region_z).to(self.device)))
         outs = model.results(rec, (bgr, depth))
         if seeded is not None:
             for b, r in enumerate(outs):

@@ -97,9 +97,12 @@ class RegionRefinement:
     """Options of ``MaskRefinerPredictor(region=...)``: the weights (a state dict, a checkpoint dict with it under 'model', or a path to one;
     DataParallel's ``module.`` prefix is stripped), the ROI padding (``padding_percentage``), the probability threshold, the crop side and
     how many crops go through the network at a time (the reference's step_size: only chunking, GroupNorm is per sample).  head: option key
-    54, None = the library's default."""
+    54, None = the library's default.  final_close_morphology (uois/src/segmentation.py:545-573, "for synthetically-trained RRN"): after
+    the paste every id of the refined map, in ascending order, is opened and then closed with OpenCV's ksize ellipse on the current map -
+    a later id paints over an earlier one where their closings meet - and the ids the opening removed are compacted away (the reference's
+    np.unique, eval/base_model.py:512).  It is the IMP of ``cluster=`` without the largest-component step, on the same kernel."""
 
-    def __init__(self, weights_or_path, padding=0.25, threshold=0.5, crop=224, chunk=20, head=None):
+    def __init__(self, weights_or_path, padding=0.25, threshold=0.5, crop=224, chunk=20, head=None, final_close_morphology=False, ksize=9):
         self.state_dict = rrn_arch.load_checkpoint(weights_or_path)
         rrn_arch.logit_threshold(threshold)
         if crop % 16 or crop < 16:
@@ -107,6 +110,13 @@ class RegionRefinement:
         if chunk < 1:
             raise ValueError("RegionRefinement: chunk must be at least 1")
         self.padding, self.threshold, self.crop, self.chunk, self.head = float(padding), float(threshold), int(crop), int(chunk), head
+        if not isinstance(final_close_morphology, (bool, np.bool_)):
+            raise ValueError("RegionRefinement: final_close_morphology must be a bool")
+        self.final_close_morphology = bool(final_close_morphology)
+        self.close_imp = None
+        if self.final_close_morphology:
+            from ..gms import IMP
+            self.close_imp = IMP(ksize, largest=False)
         self._engines = {}
         self._tables = {}
 
@@ -125,7 +135,9 @@ class RegionRefinement:
     def refine(self, eng, bytes_, ids, n_ids, counts, z):
         """The whole stage on the frame engine `eng`: bytes_ u8 [B,H,W,3], ids i32 [B,H,W] (compact, 1..n_ids), counts: the ids present
         per frame (host ints: frame b holds 1..counts[b]), z f32 [B,H,W], all tensors on the device -> the dict of Engine.rrn_paste plus
-        "rois", "slots", "refined" (u8 [T,S,S])."""
+        "rois", "slots", "refined" (u8 [T,S,S]).  With final_close_morphology "ids", "masks" and "source" are those after the close and
+        "report" is i32 [B,5]: the masks left, the initial masks the network emptied, pixels painted, pixels painted over (both by the
+        paste), the ids the close removed."""
         B, S = ids.shape[0], self.crop
         rois = eng.zoom_rois(ids, n_ids, self.padding)
         slots = torch.tensor([(b, i) for b in range(B) for i in range(1, int(counts[b]) + 1)], dtype=torch.int32).reshape(-1, 2).to(eng.device)
@@ -137,7 +149,14 @@ class RegionRefinement:
             for a in range(0, T, self.chunk):
                 e = min(T, a + self.chunk)
                 net.run(rgb[a:e], mask[a:e], self.threshold, logits=False, out={"refined": refined[a:e]})
-        o = eng.rrn_paste(refined, slots, rois, z, B, max(n_ids, 1))
+        N = max(n_ids, 1)
+        o = eng.rrn_paste(refined, slots, rois, z, B, N)
+        if self.close_imp is not None:
+            # the IMP compacts a [B,N,3] float table beside the ids: it carries the source ids (at most 254: exact in float32) along
+            src = o["source"].to(torch.float32)[:, :, None].expand(B, N, 3).contiguous()
+            imp = eng.gms_imp(o["ids"], N, self.close_imp, n_masks=N, masks=o["masks"], centers=src)
+            o["source"] = src[:, :, 0].to(torch.int32).contiguous()
+            o["report"] = torch.cat([imp["report"][:, 0:1], o["report"][:, 1:4], imp["report"][:, 4:5]], 1).contiguous()
         o.update(rois=rois, slots=slots, refined=refined)
         return o
 

@@ -50,39 +50,69 @@ class DsnEngine:
             raise ValueError(f"DsnEngine: batch {B} outside 1..{self.max_batch}")
         return B
 
-    def run(self, xyz, logits=False, offsets=False, votes=False, classes=False, fg=False):
-        """xyz f32 [B,3,H,W] (planar x, y, z; NaN allowed) -> dict of the requested outputs: "fg_logits" / "center_offsets" / "votes" f32
+    def _check_z(self, xyz, z, camera):
+        """the depth form of a call: z f32 [B,H,W] on the device (metres) and a quber_amd.camera.Camera -> (B, its four doubles)"""
+        from ..camera import Camera
+        if xyz is not None or z is None or camera is None:
+            raise ValueError("DsnEngine: either xyz, or z= together with camera=")
+        if not isinstance(camera, Camera):
+            raise ValueError(f"DsnEngine: camera={camera!r}, expected a quber_amd.camera.Camera")
+        B = z.shape[0] if isinstance(z, torch.Tensor) and z.dim() else 0
+        if not (isinstance(z, torch.Tensor) and z.dtype == torch.float32 and z.is_contiguous() and z.is_cuda and tuple(z.shape) == (B, self.H, self.W)):
+            raise ValueError(f"DsnEngine: z must be a contiguous float32 device tensor [B,{self.H},{self.W}]")
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"DsnEngine: batch {B} outside 1..{self.max_batch}")
+        return B, (C.c_double * 4)(*camera.params)
+
+    def run(self, xyz=None, logits=False, offsets=False, votes=False, classes=False, fg=False, z=None, camera=None):
+        """xyz f32 [B,3,H,W] (planar x, y, z; NaN allowed) - or z= f32 [B,H,W] (metres) with camera= (a quber_amd.camera.Camera): the plan's
+        first op then back-projects and packs in one kernel - -> dict of the requested outputs: "fg_logits" / "center_offsets" / "votes" f32
         [B,3,H,W], "fg_classes" / "fg" u8 [B,H,W]."""
-        B = self._check(xyz)
+        cam = None
+        if z is not None or camera is not None:
+            B, cam = self._check_z(xyz, z, camera)
+        else:
+            B = self._check(xyz)
         new = lambda want, c, dt: torch.empty((B, 3, self.H, self.W) if c else (B, self.H, self.W), dtype=dt, device=self.device) if want else None
         o = {"fg_logits": new(logits, 1, torch.float32), "center_offsets": new(offsets, 1, torch.float32), "votes": new(votes, 1, torch.float32),
              "fg_classes": new(classes, 0, torch.uint8), "fg": new(fg, 0, torch.uint8)}
         p = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        outs = (p(o["fg_logits"]), p(o["center_offsets"]), p(o["votes"]), p(o["fg_classes"]), p(o["fg"]), st)
         with torch.cuda.device(self.device):
-            _lib.check(self.eng.lib.quber_dsn_forward(self.eng.h, p(xyz), B, self.flags, p(o["fg_logits"]), p(o["center_offsets"]), p(o["votes"]),
-                                                      p(o["fg_classes"]), p(o["fg"]), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            if cam is None:
+                _lib.check(self.eng.lib.quber_dsn_forward(self.eng.h, p(xyz), B, self.flags, *outs))
+            else:
+                _lib.check(self.eng.lib.quber_dsn_forward_depth(self.eng.h, p(z), B, self.flags, cam, camera.convention_id, *outs))
         return {k: v for k, v in o.items() if v is not None}
 
-    def profile(self, xyz):
-        """One forward with an event pair around every op -> [(op name, ms)] in plan order; synchronises (tools/dsn_ab.py)."""
-        B = self._check(xyz)
+    def profile(self, xyz=None, z=None, camera=None):
+        """One forward with an event pair around every op -> [(op name, ms)] in plan order; synchronises (tools/dsn_ab.py, tools/xyz_ab.py)."""
+        cam = None
+        if z is not None or camera is not None:
+            B, cam = self._check_z(xyz, z, camera)
+        else:
+            B = self._check(xyz)
         plan = self.eng.plan()
         ms = (C.c_double * len(plan))()
         cls = torch.empty((B, self.H, self.W), dtype=torch.uint8, device=self.device)
+        tail = (None, None, None, C.c_void_p(cls.data_ptr()), None, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), ms)
         with torch.cuda.device(self.device):
-            _lib.check(self.eng.lib.quber_dsn_forward_profiled(self.eng.h, C.c_void_p(xyz.data_ptr()), B, self.flags, None, None, None, C.c_void_p(cls.data_ptr()),
-                                                               None, C.c_void_p(torch.cuda.current_stream().cuda_stream), ms))
+            if cam is None:
+                _lib.check(self.eng.lib.quber_dsn_forward_profiled(self.eng.h, C.c_void_p(xyz.data_ptr()), B, self.flags, *tail))
+            else:
+                _lib.check(self.eng.lib.quber_dsn_forward_depth_profiled(self.eng.h, C.c_void_p(z.data_ptr()), B, self.flags, cam, camera.convention_id, *tail))
         return [(p[0], ms[i]) for i, p in enumerate(plan)]
 
-    def forward(self, xyz):
+    def forward(self, xyz=None, z=None, camera=None):
         """-> (fg_logits, center_offsets), f32 [B,3,H,W] each: DepthSeedingNetwork.forward on the cleaned input"""
-        o = self.run(xyz, logits=True, offsets=True)
+        o = self.run(xyz, logits=True, offsets=True, z=z, camera=camera)
         return o["fg_logits"], o["center_offsets"]
 
-    def seed(self, xyz):
+    def seed(self, xyz=None, z=None, camera=None):
         """-> (votes f32 [B,3,H,W] = cleaned xyz + offsets, fg u8 [B,H,W] = (class == 2), fg_classes u8 [B,H,W] in 0 / 1 / 2): what
         Engine.gms reads, and the reference's fg_mask"""
-        o = self.run(xyz, votes=True, classes=True, fg=True)
+        o = self.run(xyz, votes=True, classes=True, fg=True, z=z, camera=camera)
         return o["votes"], o["fg"], o["fg_classes"]
 
 
