@@ -423,6 +423,38 @@ int quber_coco_match(quber_ctx* ctx, const uint8_t* dev_dt, const float* dev_sco
                      int32_t* dev_counts, int32_t* dev_order, float* dev_out_scores, double* dev_dt_area, double* dev_gt_area_used,
                      double* dev_iou, uint8_t* dev_dtm, uint8_t* dev_dtig, uint8_t* dev_gi, int32_t* dev_gorder, void* stream);
 
+/* Boundary AP, the per-frame half (csrc/cocoap.hip, csrc/boundaryap.hip): quber_coco_match with iou_type 0 under Boundary IoU (Cheng et al.;
+ * mask_to_boundary and COCOeval.computeBoundaryIoU of the published boundary-iou-api, restated - parity with that package is argued, not
+ * pinned by a test, as parity with pycocotools is).  The numpy statement is tests/test_boundary_ap_cpu.py: mask_boundary_np, boundary_iou_np,
+ * coco_frame_boundary_np; DESIGN.md "Boundary AP" has it in words.
+ *   boundary(m) = m & ~erode_d(m), d = dilation: d iterations of a 3 x 3 erosion with zeros outside the frame - a pixel survives the
+ *     erosion iff the whole (2d + 1) x (2d + 1) square around it lies inside the frame and inside m.  1 <= dilation <= 64; anything else is an
+ *     error, never clamped.  The caller derives it from the frame: max(1, round(0.02 * sqrt(H H + W W))) (coco_ap.boundary_dilation).
+ *   mask iou: exactly iou_type 0.  boundary iou: the same expression on the boundaries - i_b = pixels in both boundaries, db / gb = pixels of
+ *     each; 0 if i_b == 0, else i_b / db for a crowd, else i_b / (db + gb - i_b).  iou = min(mask iou, boundary iou).  The areas - dev_dt_area,
+ *     dev_gt_area_used and with them the area ranges - stay the MASK areas; ranking, gi / gorder, matching and the records are unchanged.
+ *   The arguments and outputs are quber_coco_match's, without iou_type and the boxes; dev_iou receives the minimum;
+ *   -> dev_mask_iou, dev_boundary_iou f64 [B][100][n_gt], either may be NULL (not wanted): the two ratios on their own, 0 behind n_top and for an
+ *      absent ground truth.
+ * Every output byte is written by every call; the limits are quber_coco_match's and are errors, never truncated.  Launches (rank, zero, pack,
+ * boundary, gram, gram, iou, gorder, match) on `stream`; no host copy, no synchronisation, no memset node, no floating-point atomics.  The
+ * workspace is quber_coco_match's, larger by the boundary planes, the second pair table and the boundary areas (lazy, counted by
+ * quber_workspace_bytes; the call that makes or grows it is not capturable into a graph).  Works on a context created with with_network = 0. */
+int quber_coco_match_boundary(quber_ctx* ctx, const uint8_t* dev_dt, const float* dev_scores, int32_t n_dt, const uint8_t* dev_gt,
+                              const uint8_t* dev_gt_flags, const double* dev_gt_area, int32_t n_gt, int32_t batch, int32_t dilation,
+                              const double* dev_iou_thrs, int32_t n_thrs, const double* dev_area_rng, int32_t n_rng, int32_t* dev_counts,
+                              int32_t* dev_order, float* dev_out_scores, double* dev_dt_area, double* dev_gt_area_used, double* dev_iou,
+                              double* dev_mask_iou, double* dev_boundary_iou, uint8_t* dev_dtm, uint8_t* dev_dtig, uint8_t* dev_gi,
+                              int32_t* dev_gorder, void* stream);
+
+/* The boundary kernel of quber_coco_match_boundary on its own (overlays, tests): dev_masks u8 [n][h][w] (non-zero = inside; any frame size,
+ * not only the context's) -> dev_out u8 [n][h][w] of 0 / 1 = boundary(m) as above, dev_area i32 [n][2] = (pixels of the mask, pixels of its
+ * boundary).  1 <= dilation <= 64 and h w <= 2^30, else an error that writes nothing.  dev_out may be dev_masks itself.  Launches (zero, pack,
+ * boundary, unpack) on `stream`; the bit planes live in the lazy workspace of quber_coco_match (the call that makes or grows it is not
+ * capturable into a graph).  Works on a context created with with_network = 0. */
+int quber_op_mask_boundary(quber_ctx* ctx, const uint8_t* dev_masks, int32_t n, int32_t h, int32_t w, int32_t dilation, uint8_t* dev_out,
+                           int32_t* dev_area, void* stream);
+
 /* Mean-shift clustering of pixel embeddings into initial masks (csrc/meanshift.hip): the UCN base model's clustering_features ->
  * mean_shift_smart_init (select_smart_seeds, seed_hill_climbing_ball, connected_components) and filter_labels_depth of the reference
  * (eval/base_model.py:622-840 and :34-47, cosine metric), which it runs as torch and Python loops per frame.  The numpy statement of

@@ -71,6 +71,8 @@ SIGNATURES = {
     "quber_mask_nms": (C.c_int, [_P, _P, _P, _I, _I, C.c_float, _I, _P, _P, _P, _P, _P, _P]),
     "quber_scene_perturb": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_double] + [_P] * 10),
     "quber_coco_match": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I] + [_P] * 11),
+    "quber_coco_match_boundary": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I] + [_P] * 13),
+    "quber_op_mask_boundary": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "quber_meanshift_seeds": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P]),
     "quber_meanshift_climb": (C.c_int, [_P, _P, _I, _I, _P, _I, C.c_float, _I, _P, _P]),
     "quber_meanshift_link": (C.c_int, [_P, _P, _I, _I, C.c_float, _P, _P]),

@@ -721,6 +721,38 @@ int quber_coco_match(quber_ctx* c, const uint8_t* dt, const float* scores, const
     return launch_coco_match(q, batch, H, W, c->lazy[WS_COCOAP].p, (hipStream_t)stream);
 }
 
+// ... under Boundary IoU (boundaryap.hip makes the boundary planes); the same lazy workspace, larger by the second set of planes, pair table and areas
+int quber_coco_match_boundary(quber_ctx* c, const uint8_t* dt, const float* scores, int32_t n_dt, const uint8_t* gt, const uint8_t* gt_flags,
+                              const double* gt_area, int32_t n_gt, int32_t batch, int32_t dilation, const double* iou_thrs, int32_t n_thrs,
+                              const double* area_rng, int32_t n_rng, int32_t* counts, int32_t* order, float* out_scores, double* dt_area,
+                              double* gt_area_used, double* iou, double* mask_iou, double* boundary_iou, uint8_t* dtm, uint8_t* dtig, uint8_t* gi,
+                              int32_t* gorder, void* stream) {
+    if (check_batch(c, batch)) return -1;
+    if (n_gt < 0 || n_gt > 1024) return fail("coco match: n_gt outside 0..1024");
+    if (dilation < 1 || dilation > mask_boundary_max_dilation()) return fail("coco match: dilation outside 1..64");
+    const int H = c->cfg.height, W = c->cfg.width;
+    if (ws_reserve(c, c->lazy[WS_COCOAP], coco_match_ws_bytes(batch, n_gt, H, W, 2))) return -1;
+    const CocoMatchArgs q{dt, scores, nullptr, n_dt, gt, gt_flags, gt_area, nullptr, n_gt, 0, iou_thrs, n_thrs, area_rng, n_rng,
+                          counts, order, out_scores, dt_area, gt_area_used, iou, dtm, dtig, gi, gorder};
+    return launch_coco_match_boundary(q, dilation, mask_iou, boundary_iou, batch, H, W, c->lazy[WS_COCOAP].p, (hipStream_t)stream);
+}
+
+// ---- the boundary of masks as Boundary AP takes it (boundaryap.hip): the kernel of quber_coco_match_boundary on its own; any frame size ----
+int quber_op_mask_boundary(quber_ctx* c, const uint8_t* masks, int32_t n, int32_t h, int32_t w, int32_t dilation, uint8_t* out, int32_t* area,
+                           void* stream) {
+    if (!c) return fail("null context");
+    if (h < 1 || w < 1 || (long)h * w > (1L << 30)) return fail("mask boundary: an empty frame or one of more than 2^30 pixels");
+    if (n < 0) return fail("mask boundary: negative n");
+    if (dilation < 1 || dilation > mask_boundary_max_dilation()) return fail("mask boundary: dilation outside 1..64");
+    if (n == 0) return 0;
+    if (!masks || !out || !area) return fail("mask boundary: null tensor");
+    const size_t bytes = (size_t)n * h * w;
+    if (out != masks && out < masks + bytes && masks < out + bytes) return fail("mask boundary: dev_out overlaps dev_masks partially");
+    // the planes live in the workspace of quber_coco_match: made on first use, kept, grown when a larger call comes
+    if (ws_reserve(c, c->lazy[WS_COCOAP], mask_boundary_ws_bytes(n, h, w))) return -1;
+    return launch_mask_boundary(masks, n, h, w, dilation, out, area, c->lazy[WS_COCOAP].p, (hipStream_t)stream);
+}
+
 // ---- mean-shift clustering of pixel embeddings into initial masks (meanshift.hip); usable on a context without a network ----
 static int meanshift_ws(quber_ctx* c) {      // the only allocation of the five entries: made by the first call, for max_batch frames, and kept
     return ws_reserve(c, c->lazy[WS_MEANSHIFT], meanshift_ws_bytes(c->cfg.max_batch, c->cfg.height, c->cfg.width));

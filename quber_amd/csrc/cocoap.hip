@@ -18,6 +18,9 @@
 //           odd: the 16 rows of a ds_read_b128 lane group start on 16 different 4-bank slots, lanes on one row read one address), one
 //           integer atomicAdd per (block, pair).
 //   iou     the float64 expressions of the contract, one division (__ddiv_rn) per pair; the areas as used.
+//   Boundary IoU (quber_coco_match_boundary): behind pack, boundaryap.hip writes m & ~erode_d(m) of every plane into a second set of planes with
+//           their areas, gram runs a second time on those into a second pair table (cleared by the same zero fill), and iou stores
+//           min(mask iou, boundary iou) - the same expression on the two sets of integers; the areas stay the mask areas.
 //   gorder  per (frame, area range): gi and the stable order "not ignored first" by counting.
 //   match   one wave per (frame, area range, threshold): the greedy matching, detections in rank order, the lanes scanning gorder.
 // Integer and bit arithmetic except the float64 expressions of `iou`; no floating-point atomics; every output byte is written by every call.
@@ -149,10 +152,15 @@ __global__ __launch_bounds__(256) void ca_gram_kernel(const unsigned* __restrict
 // grid (ceil((CA_TOP + n_gt + CA_TOP * n_gt) / 256), B).  Element e of a frame: a detection area, a ground-truth area, or a pair.
 //   dt_area f64 [B][CA_TOP] (0 behind n_top), gt_area f64 [B][n_gt] as used (the caller's where it is given and not NaN; 0 for an absent
 //   one), iou f64 [B][CA_TOP][n_gt] (0 behind n_top and for an absent ground truth)
+//   BOUNDARY: inter_b, area_b = the pair table and the areas of the boundary planes; iou = min(mask iou, boundary iou), the two ratios also
+//   to mask_iou / bnd_iou f64 [B][CA_TOP][n_gt] where those are not null
+template <bool BOUNDARY>
 __global__ __launch_bounds__(256) void ca_iou_kernel(int bbox, const unsigned* __restrict__ inter, const unsigned* __restrict__ area,
                                                      const double* __restrict__ boxes, const int* __restrict__ counts,
                                                      const uint8_t* __restrict__ gt_flags, const double* __restrict__ gt_area_in, int n_gt,
-                                                     double* __restrict__ dt_area, double* __restrict__ gt_area, double* __restrict__ iou) {
+                                                     double* __restrict__ dt_area, double* __restrict__ gt_area, double* __restrict__ iou,
+                                                     const unsigned* __restrict__ inter_b, const unsigned* __restrict__ area_b,
+                                                     double* __restrict__ mask_iou, double* __restrict__ bnd_iou) {
     const int b = blockIdx.y, P = CA_TOP + n_gt;
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long)P + (long)CA_TOP * n_gt) return;
@@ -194,6 +202,18 @@ __global__ __launch_bounds__(256) void ca_iou_kernel(int bbox, const unsigned* _
             const long long i = inter[((size_t)b * CA_TOP + d) * n_gt + g], da = ar[d], ga = ar[CA_TOP + g];
             if (i) v = __ddiv_rn((double)i, (double)(crowd ? da : da + ga - i));
         }
+    }
+    if (BOUNDARY) {
+        double vb = 0.0;
+        if (d < n_top && f != CA_ABSENT) {
+            const unsigned* ab = area_b + (size_t)b * P;
+            const long long i = inter_b[((size_t)b * CA_TOP + d) * n_gt + g], da = ab[d], ga = ab[CA_TOP + g];
+            if (i) vb = __ddiv_rn((double)i, (double)((f & 1) ? da : da + ga - i));
+        }
+        const size_t o = ((size_t)b * CA_TOP + d) * n_gt + g;
+        if (mask_iou) mask_iou[o] = v;
+        if (bnd_iou) bnd_iou[o] = vb;
+        v = vb < v ? vb : v;
     }
     iou[((size_t)b * CA_TOP + d) * n_gt + g] = v;
 }
@@ -285,18 +305,22 @@ __global__ __launch_bounds__(64) void ca_match_kernel(const double* __restrict__
     for (int d = n_top + lane; d < CA_TOP; d += 64) { dtm[out + d] = 0; dtig[out + d] = 0; }
 }
 
-// workspace layout: planes (segm only) | inter, area (zeroed together) | boxes
-struct CaWs { unsigned* planes; unsigned* inter; unsigned* area; double* boxes; size_t zero_bytes; };
+// workspace layout: planes (segm and boundary) | inter, area [, inter_b, area_b] (zeroed together) | boxes [| boundary planes]
+// mode: quber_coco_match's iou_type (0 segm, 1 bbox), 2 = Boundary IoU
+struct CaWs { unsigned* planes; unsigned* inter; unsigned* area; double* boxes; size_t zero_bytes; unsigned* inter_b; unsigned* area_b; unsigned* bplanes; };
 
-static size_t ca_layout(CaWs* out, void* ws, int B, int n_gt, int H, int W, int bbox) {
-    const size_t b = (size_t)B, P = CA_TOP + n_gt, pairs = b * CA_TOP * n_gt;
+static size_t ca_layout(CaWs* out, void* ws, int B, int n_gt, int H, int W, int mode) {
+    const size_t b = (size_t)B, P = CA_TOP + n_gt, pairs = b * CA_TOP * n_gt, sets = mode == 2 ? 2 : 1;
     CaWs none, &r = out ? *out : none;
     WsWalk w{static_cast<char*>(ws)};
-    r.planes = bbox ? nullptr : w.take<unsigned>(b * P * mn_plane_words(H, W));
-    r.inter = w.take<unsigned>(pairs + b * P);
+    r.planes = mode == 1 ? nullptr : w.take<unsigned>(b * P * mn_plane_words(H, W));
+    r.inter = w.take<unsigned>(sets * (pairs + b * P));
     r.area = r.inter ? r.inter + pairs : nullptr;
-    r.zero_bytes = (pairs + b * P) * 4;
+    r.inter_b = r.inter && mode == 2 ? r.inter + pairs + b * P : nullptr;
+    r.area_b = r.inter_b ? r.inter_b + pairs : nullptr;
+    r.zero_bytes = sets * (pairs + b * P) * 4;
     r.boxes = w.take<double>(b * P * 4);
+    r.bplanes = mode == 2 ? w.take<unsigned>(b * P * mn_plane_words(H, W)) : nullptr;
     return w.off;
 }
 
@@ -304,28 +328,31 @@ size_t coco_match_ws_bytes(int B, int n_gt, int H, int W, int bbox) { return ca_
 
 int coco_match_top() { return CA_TOP; }
 
-int launch_coco_match(const CocoMatchArgs& q, int B, int H, int W, void* ws, hipStream_t st) {
+// mode as in ca_layout; dilation, mask_iou, bnd_iou: mode 2 only
+static int ca_launch(const CocoMatchArgs& q, int mode, int dilation, double* mask_iou, double* bnd_iou, int B, int H, int W, void* ws,
+                     hipStream_t st) {
     if (B <= 0) return 0;
     if (H < 1 || W < 1) return fail("coco match: negative or empty frame");
-    const int n_dt = q.n_dt, n_gt = q.n_gt, T = q.n_thrs, A = q.n_rng, bbox = q.iou_type;
+    const int n_dt = q.n_dt, n_gt = q.n_gt, T = q.n_thrs, A = q.n_rng, bbox = mode == 1;
     if (n_dt < 0 || n_dt > CA_MAX) return fail("coco match: n_dt outside 0..1024");
     if (n_gt < 0 || n_gt > CA_MAX) return fail("coco match: n_gt outside 0..1024");
     if (T < 1 || T > CA_MAX_T) return fail("coco match: the number of IoU thresholds outside 1..16");
     if (A < 1 || A > CA_MAX_A) return fail("coco match: the number of area ranges outside 1..8");
-    if (bbox != 0 && bbox != 1) return fail("coco match: iou_type must be 0 (segm) or 1 (bbox)");
+    if (mode < 0 || mode > 2) return fail("coco match: iou_type must be 0 (segm) or 1 (bbox)");
+    if (mode == 2 && (dilation < 1 || dilation > mask_boundary_max_dilation())) return fail("coco match: dilation outside 1..64");
     if (!q.iou_thrs || !q.area_rng || !q.counts || !q.order || !q.out_scores || !q.dt_area || !q.dtm || !q.dtig || !ws)
         return fail("coco match: null tensor");
     if (n_dt > 0 && (!q.scores || (!q.dt && !(bbox && q.dt_boxes)))) return fail("coco match: null detections");
     if (n_gt > 0 && (!q.gt_flags || !q.gt_area_used || !q.iou || !q.gi || !q.gorder || (!q.gt && !(bbox && q.gt_boxes))))
         return fail("coco match: null ground truth");
     const uintptr_t a8 = (uintptr_t)q.dt_boxes | (uintptr_t)q.gt_boxes | (uintptr_t)q.gt_area | (uintptr_t)q.iou_thrs | (uintptr_t)q.area_rng |
-                         (uintptr_t)q.dt_area | (uintptr_t)q.gt_area_used | (uintptr_t)q.iou;
+                         (uintptr_t)q.dt_area | (uintptr_t)q.gt_area_used | (uintptr_t)q.iou | (uintptr_t)mask_iou | (uintptr_t)bnd_iou;
     const uintptr_t a4 = (uintptr_t)q.scores | (uintptr_t)q.counts | (uintptr_t)q.order | (uintptr_t)q.out_scores | (uintptr_t)q.gorder;
     if ((a8 & 7) || (a4 & 3)) return fail("coco match: a 64-bit tensor that is not 8-byte aligned, or a 32-bit one that is not 4-byte aligned");
     const long HW = (long)H * W;
     const int wpr = (W + 31) / 32, pw = (int)mn_plane_words(H, W), P = CA_TOP + n_gt;
     CaWs w;
-    ca_layout(&w, ws, B, n_gt, H, W, bbox);
+    ca_layout(&w, ws, B, n_gt, H, W, mode);
     {
         ProfScope prof("coco_rank", 4.0 * B * n_dt + 1.0 * B * n_gt, 0.0, st);
         hipLaunchKernelGGL(ca_rank_kernel, dim3(B), dim3(CA_MAX), 0, st, q.scores, q.gt_flags, n_dt, n_gt, q.counts, q.order, q.out_scores);
@@ -348,18 +375,27 @@ int launch_coco_match(const CocoMatchArgs& q, int B, int H, int W, void* ws, hip
                 hipLaunchKernelGGL(ca_pack_kernel<false>, grid, dim3(256), 0, st, q.dt, q.gt, q.order, q.gt_flags, n_dt, n_gt, H, W, wpr, pw, w.planes, w.area);
             QB_CHECK(hipGetLastError());
         }
+        if (mode == 2 && launch_boundary_planes(w.planes, (long)B * P, H, W, dilation, w.bplanes, w.area_b, 1, st)) return -1;
         if (n_gt > 0) {
             const int ntg = (n_gt + CA_TILE - 1) / CA_TILE;
-            ProfScope prof("coco_gram", 4.0 * B * pw * ((double)CA_TOP * ntg + (double)n_gt * CA_DT_TILES) + 4.0 * B * CA_TOP * n_gt, 0.0, st);
-            hipLaunchKernelGGL(ca_gram_kernel, dim3(CA_DT_TILES * ntg, (pw + CA_CHUNK - 1) / CA_CHUNK, B), dim3(256), 0, st, w.planes, w.inter, n_gt, pw);
+            ProfScope prof("coco_gram", (mode == 2 ? 2.0 : 1.0) * (4.0 * B * pw * ((double)CA_TOP * ntg + (double)n_gt * CA_DT_TILES) + 4.0 * B * CA_TOP * n_gt),
+                           0.0, st);
+            const dim3 grid(CA_DT_TILES * ntg, (pw + CA_CHUNK - 1) / CA_CHUNK, B);
+            hipLaunchKernelGGL(ca_gram_kernel, grid, dim3(256), 0, st, w.planes, w.inter, n_gt, pw);
+            if (mode == 2) hipLaunchKernelGGL(ca_gram_kernel, grid, dim3(256), 0, st, w.bplanes, w.inter_b, n_gt, pw);
             QB_CHECK(hipGetLastError());
         }
     }
     {
-        ProfScope prof("coco_iou", 12.0 * B * CA_TOP * n_gt, 0.0, st);
+        ProfScope prof("coco_iou", (mode == 2 ? 36.0 : 12.0) * B * CA_TOP * n_gt, 0.0, st);
         const long n = (long)P + (long)CA_TOP * n_gt;
-        hipLaunchKernelGGL(ca_iou_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, bbox, w.inter, w.area, w.boxes, q.counts, q.gt_flags,
-                           q.gt_area, n_gt, q.dt_area, q.gt_area_used, q.iou);
+        const dim3 grid((unsigned)((n + 255) / 256), B);
+        if (mode == 2)
+            hipLaunchKernelGGL(ca_iou_kernel<true>, grid, dim3(256), 0, st, 0, w.inter, w.area, w.boxes, q.counts, q.gt_flags, q.gt_area, n_gt, q.dt_area,
+                               q.gt_area_used, q.iou, w.inter_b, w.area_b, mask_iou, bnd_iou);
+        else
+            hipLaunchKernelGGL(ca_iou_kernel<false>, grid, dim3(256), 0, st, bbox, w.inter, w.area, w.boxes, q.counts, q.gt_flags, q.gt_area, n_gt,
+                               q.dt_area, q.gt_area_used, q.iou, nullptr, nullptr, nullptr, nullptr);
         QB_CHECK(hipGetLastError());
     }
     if (n_gt > 0) {
@@ -374,6 +410,17 @@ int launch_coco_match(const CocoMatchArgs& q, int B, int H, int W, void* ws, hip
         QB_CHECK(hipGetLastError());
     }
     return 0;
+}
+
+int launch_coco_match(const CocoMatchArgs& q, int B, int H, int W, void* ws, hipStream_t st) {
+    if (q.iou_type != 0 && q.iou_type != 1) return fail("coco match: iou_type must be 0 (segm) or 1 (bbox)");
+    return ca_launch(q, q.iou_type, 0, nullptr, nullptr, B, H, W, ws, st);
+}
+
+int launch_coco_match_boundary(const CocoMatchArgs& q, int dilation, double* mask_iou, double* boundary_iou, int B, int H, int W, void* ws,
+                               hipStream_t st) {
+    if (q.dt_boxes || q.gt_boxes) return fail("coco match: boxes come with iou_type 1 (bbox)");
+    return ca_launch(q, 2, dilation, mask_iou, boundary_iou, B, H, W, ws, st);
 }
 
 }  // namespace quber

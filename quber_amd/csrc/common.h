@@ -465,6 +465,19 @@ struct CocoMatchArgs {
 int launch_coco_match(const CocoMatchArgs& q, int B, int H, int W, void* ws, hipStream_t st);
 size_t coco_match_ws_bytes(int B, int n_gt, int H, int W, int bbox);
 int coco_match_top();
+// ... under Boundary IoU (quber_coco_match_boundary): rank -> zero -> pack -> boundary -> gram, gram -> iou -> gorder -> match; q.iou_type is not
+// read, q.iou receives min(mask iou, boundary iou); mask_iou / boundary_iou f64 [B][100][n_gt] or null; ws: coco_match_ws_bytes(.., 2) bytes
+int launch_coco_match_boundary(const CocoMatchArgs& q, int dilation, double* mask_iou, double* boundary_iou, int B, int H, int W, void* ws,
+                               hipStream_t st);
+// the boundary of bit planes (boundaryap.hip; bitplane.h's layout): out = m & ~erode_d(m) with zeros outside the frame, 1 <= d <= 64;
+// area[plane * area_stride] += the pixels of the boundary (the caller clears it).  launch_mask_boundary: the same on u8 masks [n][H][W] ->
+// 0 / 1 bytes and area i32 [n][2] = (mask, boundary) pixels; ws: mask_boundary_ws_bytes(>= n, H, W) bytes; out may be `masks` itself
+int launch_boundary_planes(const unsigned* planes, long n_planes, int H, int W, int d, unsigned* out, unsigned* area, int area_stride,
+                           hipStream_t st);
+int launch_mask_boundary(const uint8_t* masks, long n, int H, int W, int d, uint8_t* out, int* area, void* ws, hipStream_t st);
+size_t mask_boundary_ws_bytes(long n, int H, int W);
+int mask_boundary_max_dilation();
+int mask_boundary_band();
 // mean-shift clustering of an embedding map f32 [B][64][H][W] into masks (meanshift.hip), all on `st`; ws: meanshift_ws_bytes(cap_b >= B, H, W)
 // bytes.  S seeds <= 128 and <= H W; Z f32 [B][S][64]; N planes <= 254; depth_z f32 [B][H][W] or null (no depth filter)
 int launch_meanshift_seeds(const float* X, const int* first, int B, int S, int H, int W, int* idx, void* ws, int cap_b, hipStream_t st);

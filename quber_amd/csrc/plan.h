@@ -43,7 +43,7 @@ struct LazyWs { void* p = nullptr; size_t bytes = 0; };
 enum LazyId {
     WS_PERTURB,     // bit planes of quber_perturb_masks in its device-memory placement: grown on demand
     WS_MASKNMS,     // bit planes, pair table, rank map and per-frame tables of quber_mask_nms: for max_batch frames
-    WS_COCOAP,      // bit planes, pair table, areas and boxes of quber_coco_match: grown on demand
+    WS_COCOAP,      // bit planes, pair table(s), areas and boxes of quber_coco_match / _boundary, the planes of quber_op_mask_boundary: grown on demand
     WS_SCENE,       // bit planes, pair and touch tables, member sets, prefix sums of quber_scene_perturb: grown on demand
     WS_MEANSHIFT,   // seed slots, histograms, running minimum, raw labels, block partials of the mean-shift entries (meanshift.hip): for max_batch frames
     WS_GMS,         // counts, compacted points, running minimum, raw labels, tables, block partials of the Gaussian mean-shift entries (gms.hip): for max_batch frames

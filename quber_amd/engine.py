@@ -539,6 +539,21 @@ class Engine:
                                                _ptr(out_scores), _ptr(report), _stream()))
         return {"masks": out, "ids": ids, "source": source, "scores": out_scores, "report": report}
 
+    # ---- the boundary of masks as Boundary AP takes it (csrc/boundaryap.hip; INTEGRATION.md "Boundary AP") ----
+    def mask_boundary(self, masks, dilation, out=None, area=None):
+        """masks u8 [n,H,W] on the device (non-zero = inside; any frame size) -> (boundary u8 [n,H,W] of 0 / 1 = m & ~erode_d(m), d =
+        dilation in 1..64, zeros outside the frame; area i32 [n,2] = pixels of the mask, pixels of its boundary).  `out` may be `masks`
+        itself.  Nothing is copied to the host; a call that needs a larger workspace allocates and cannot be captured into a graph."""
+        assert masks.dtype == torch.uint8 and masks.is_contiguous() and masks.dim() == 3
+        n, h, w = masks.shape
+        out = torch.empty_like(masks) if out is None else out
+        area = torch.empty((n, 2), dtype=torch.int32, device=self.device) if area is None else area
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == masks.shape
+        assert area.dtype == torch.int32 and area.is_contiguous() and area.shape == (n, 2)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.quber_op_mask_boundary(self.h, _ptr(masks), n, h, w, int(dilation), _ptr(out), _ptr(area), _stream()))
+        return out, area
+
     # ---- scene-level perturbation of a frame's instance list (csrc/scene.hip; INTEGRATION.md "Scene-level perturbation") ----
     def scene_perturb(self, gt, props, n_gt, n_prop, draws, max_masks, min_mask_ratio=0.01, out=None, info=None, report=None):
         """gt u8 [B,N,H,W], props u8 [B,P,H,W] (non-zero = inside; N or P may be 0), n_gt / n_prop i32 [B]: the rows of each frame that

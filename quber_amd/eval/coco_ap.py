@@ -2,7 +2,11 @@
 period through detectron2's COCOEvaluator(use_fast_impl=False) and pycocotools (train_net.py:57, maskrefiner/evaluation/
 instance_evaluation.py).  The per-frame half - pairwise IoU, the top 100 by score, the greedy matching per threshold and area range - runs
 on the device (csrc/cocoap.hip: quber_coco_match), one small record per frame comes back; accumulate and summarize run here on those
-records.  The definition is tests/test_cocoap_cpu.py (numpy in plain loops) and DESIGN.md "COCO AP"; parity with pycocotools is unpinned."""
+records.  The definition is tests/test_cocoap_cpu.py (numpy in plain loops) and DESIGN.md "COCO AP"; parity with pycocotools is unpinned.
+iou_type "boundary" is Boundary AP (Cheng et al.; the reference's tools/evaluate_coco_boundary_ap.py): the same with iou = min(mask IoU,
+Boundary IoU), the boundaries made on the device (csrc/boundaryap.hip: quber_coco_match_boundary); tests/test_boundary_ap_cpu.py and
+DESIGN.md "Boundary AP" hold the definition, parity with the boundary_iou package is argued, not pinned."""
+import math
 import ctypes as C
 
 import numpy as np
@@ -22,6 +26,13 @@ ABSENT = 0xFF                      # gt_flags of a padding slot; bit 0 = crowd, 
 STAT_NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
 MAX_BATCH = 16                     # frames per call of an engine; a larger batch goes in pieces
 MAX_LABELS = 254                   # labels per frame of a label-map ground truth (quber_config.top_k's maximum)
+MAX_DILATION = 64                  # csrc/boundaryap.hip: CB_MAX_D
+
+
+def boundary_dilation(h, w, ratio=0.02):
+    """The dilation distance of Boundary IoU for an h x w frame (boundary-iou-api's mask_to_boundary): ratio x the diagonal, rounded with
+    Python's round, at least 1.  480 x 640 -> 16."""
+    return max(1, int(round(ratio * math.sqrt(h * h + w * w))))
 
 
 def accumulate_records(records, iou_thrs=IOU_THRS, rec_thrs=REC_THRS, max_dets=MAX_DETS):
@@ -91,15 +102,22 @@ class _Handle:
 
 
 class CocoAP:
-    """iou_type "segm" or "bbox".  update() / enqueue() + collect() per batch, then summarize() -> stats (12 floats), results() -> the
-    dict detectron2 reports.  One category; RLE / polygon inputs, COCO json and per-category tables are out of scope."""
+    """iou_type "segm", "bbox" or "boundary".  update() / enqueue() + collect() per batch, then summarize() -> stats (12 floats), results()
+    -> the dict detectron2 reports.  One category; RLE / polygon inputs, COCO json and per-category tables are out of scope.
+    "boundary": iou = min(mask IoU, Boundary IoU) with the dilation distance boundary_dilation(H, W, dilation_ratio) of every call's frame,
+    or `dilation` (1..64 pixels) where that is given; inputs and outputs are those of "segm"."""
 
-    def __init__(self, iou_type="segm", device="cuda:0"):
-        if iou_type not in ("segm", "bbox"):
-            raise ValueError(f"iou_type={iou_type!r}: expected 'segm' or 'bbox'")
+    def __init__(self, iou_type="segm", device="cuda:0", dilation_ratio=0.02, dilation=None):
+        if iou_type not in ("segm", "bbox", "boundary"):
+            raise ValueError(f"iou_type={iou_type!r}: expected 'segm', 'bbox' or 'boundary'")
+        if not (isinstance(dilation_ratio, (int, float)) and 0 < dilation_ratio < math.inf):
+            raise ValueError(f"dilation_ratio={dilation_ratio!r}: expected a positive number")
+        if dilation is not None and (isinstance(dilation, bool) or not isinstance(dilation, (int, np.integer)) or not 1 <= dilation <= MAX_DILATION):
+            raise ValueError(f"dilation={dilation!r}: expected an integer in 1..{MAX_DILATION}")
         if not torch.cuda.is_available():
             raise _lib.QuberError("CocoAP needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback")
         self.iou_type, self.device = iou_type, torch.device(device)
+        self.dilation_ratio, self.dilation = float(dilation_ratio), None if dilation is None else int(dilation)
         self._thrs = torch.from_numpy(IOU_THRS).to(self.device)
         self._rng = torch.from_numpy(AREA_RNG).to(self.device)
         self.reset()
@@ -162,7 +180,7 @@ class CocoAP:
         lead = (lambda x: x if x is None or not one else x[None])
         scores = self._dev(lead(dt_scores), torch.float32)
         db, gb = self._dev(lead(dt_boxes), torch.float64), self._dev(lead(gt_boxes), torch.float64)
-        if self.iou_type == "segm" and (db is not None or gb is not None):
+        if self.iou_type != "bbox" and (db is not None or gb is not None):
             raise ValueError("CocoAP: boxes come with iou_type='bbox'")
         if (dt_masks is None and db is None) or (gt_masks is None and gb is None):
             raise ValueError("CocoAP: masks may be None only in bbox mode, on a side whose boxes are given")
@@ -198,8 +216,14 @@ class CocoAP:
             if t is not None and tuple(t.shape) != shape:
                 raise ValueError(f"CocoAP: {name} of shape {tuple(t.shape)}, expected {shape}")
         T, A = len(IOU_THRS), len(AREA_RNG)
+        boundary = self.iou_type == "boundary"
+        if boundary:
+            d = self.dilation if self.dilation is not None else boundary_dilation(h, w, self.dilation_ratio)
+            if d > MAX_DILATION:
+                raise ValueError(f"CocoAP: a dilation distance of {d} pixels for a {h} x {w} frame; at most {MAX_DILATION} (pass dilation=)")
         # one buffer for the B records: sections with the frame axis first, the widest elements first (every section stays aligned)
-        sections = (("iou", np.float64, (TOP, n_gt)), ("dt_area", np.float64, (TOP,)), ("gt_area", np.float64, (n_gt,)),
+        both = (("mask_iou", np.float64, (TOP, n_gt)), ("boundary_iou", np.float64, (TOP, n_gt))) if boundary else ()
+        sections = (("iou", np.float64, (TOP, n_gt)),) + both + (("dt_area", np.float64, (TOP,)), ("gt_area", np.float64, (n_gt,)),
                     ("counts", np.int32, (2,)), ("order", np.int32, (TOP,)), ("gorder", np.int32, (A, n_gt)), ("scores", np.float32, (TOP,)),
                     ("dtm", np.uint8, (A, T, TOP)), ("dtIg", np.uint8, (A, T, TOP)), ("gi", np.uint8, (A, n_gt)))
         offs, total = {}, 0
@@ -226,6 +250,13 @@ class CocoAP:
         with torch.cuda.device(self.device):
             for b0 in range(0, B, MAX_BATCH):
                 b1 = min(B, b0 + MAX_BATCH)
+                if boundary:
+                    _lib.check(eng.lib.quber_coco_match_boundary(
+                        eng.h, part(dt, b0, b1), part(scores, b0, b1), n_dt, part(gt, b0, b1), part(flags, b0, b1), part(areas, b0, b1), n_gt,
+                        b1 - b0, d, _ptr(self._thrs), T, _ptr(self._rng), A, out("counts", b0), out("order", b0), out("scores", b0),
+                        out("dt_area", b0), out("gt_area", b0), out("iou", b0), out("mask_iou", b0), out("boundary_iou", b0), out("dtm", b0),
+                        out("dtIg", b0), out("gi", b0), out("gorder", b0), _stream()))
+                    continue
                 _lib.check(eng.lib.quber_coco_match(
                     eng.h, part(dt, b0, b1), part(scores, b0, b1), part(db, b0, b1), n_dt, part(gt, b0, b1), part(flags, b0, b1),
                     part(areas, b0, b1), part(gb, b0, b1), n_gt, b1 - b0, 0 if self.iou_type == "segm" else 1, _ptr(self._thrs), T,

@@ -326,16 +326,21 @@ class MaskRefiner:
         return {"frames": frames, "mean": mean_losses(frames), "n": len(frames)}
 
     # -- COCO AP of the initial and the refined masks (csrc/cocoap.hip; INTEGRATION.md "COCO AP of initial and refined masks") --
-    def validation_ap(self, items, anno_paths, workers=2, batch=1):
+    def validation_ap(self, items, anno_paths, workers=2, batch=1, boundary=False, dilation_ratio=0.02):
         """The number the reference's COCOEvaluator prints after an evaluation period, for the refined masks and for the initial masks
         they came from.  items: predict_stream's; anno_paths: one annotation file (or array) per item, read with load_annotation and
         renumbered 1..n in ascending label order (compact_labels): one ground truth per label.  The initial masks are scored with the
         item's mask_scores (else 1.0), the refined ones with the predictor's instance scores, taken with their masks from the device
-        tensors of the output dict.  -> {"initial": {"stats": f64 [12], "results": detectron2's dict}, "refined": {...}, "n": frames}."""
+        tensors of the output dict.  -> {"initial": {"stats": f64 [12], "results": detectron2's dict}, "refined": {...}, "n": frames}.
+        boundary=True: additionally "initial_boundary" and "refined_boundary" of the same shape, Boundary AP (CocoAP("boundary"), the
+        reference's tools/evaluate_coco_boundary_ap.py) of the same masks with the dilation distance dilation_ratio x the frame's diagonal."""
         from collections import deque
         from .coco_ap import CocoAP
         dev = self.refiner_predictor.device
         aps = {"initial": CocoAP("segm", dev), "refined": CocoAP("segm", dev)}
+        if boundary:
+            aps.update({k + "_boundary": CocoAP("boundary", dev, dilation_ratio=dilation_ratio) for k in ("initial", "refined")})
+        stages = [[ap for k, ap in aps.items() if k.startswith(s)] for s in ("initial", "refined")]
         seen = deque()                               # (initial masks, rgb path, mask scores) of the items predict_stream has pulled, in order
 
         def tee():
@@ -353,12 +358,14 @@ class MaskRefiner:
             init = np.asarray(init)
             init = (init != 0).reshape((-1,) + gt.shape)
             scores = np.ones(len(init), np.float32) if init_scores is None else check_scores(init_scores, len(init))
-            aps["initial"].update(init, scores, gt)
+            for ap in stages[0]:
+                ap.update(init, scores, gt)
             inst = res[1].get("instances")
-            if inst is not None:
-                aps["refined"].update(inst.pred_masks, inst.scores, gt)
-            else:
-                aps["refined"].update(np.zeros((0,) + gt.shape, np.uint8), np.zeros(0, np.float32), gt)
+            for ap in stages[1]:
+                if inst is not None:
+                    ap.update(inst.pred_masks, inst.scores, gt)
+                else:
+                    ap.update(np.zeros((0,) + gt.shape, np.uint8), np.zeros(0, np.float32), gt)
             n += 1
         return dict({k: {"stats": ap.summarize(), "results": ap.results()} for k, ap in aps.items()}, n=n)
 
